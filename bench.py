@@ -2,6 +2,8 @@
 """Headline benchmark: Monte-Carlo scenarios/s (= DG-SQP solves/s) of the 2-agent N=25 game (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]                   # N > 1 without a launcher: spawns its own N ranks
+    python bench.py --gpus 1 --steps K --warmup W --full                  # ... plus every other figure (see below)
+    python bench.py ... --dump-outputs DIR                                # ... plus the arrays of the last step as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path (DGSQP.solve(), reference DGSQP/solvers/DGSQP.py:302-507) over one batch of synthetic
@@ -12,9 +14,11 @@ bit-identical to separate launches), `--pipeline` launches in flight.  The timed
 (library stream synchronisation + RCCL barrier), max over ranks.  Scenarios shard over the ranks with no data-path collective
 (--scaling weak: fixed batch per GPU; strong: fixed total batch); the only exchange is ONE ncclAllGather of the 88-byte
 per-scenario record, issued by the HIP library (dgsqp_gather_stats).  No PyTorch: the launcher only provides RANK / LOCAL_RANK /
-WORLD_SIZE.  Rank 0 prints ONE JSON line; next to `value` (K pipelined steps) it carries `value_single_launch` (strictly one
-launch at a time -- the only figure in which a launch has the GPU to itself, and where roofline.kernel_ms comes from) and
-`value_host_inclusive` (dgsqp_solve_batch from host buffers: H2D + solve + D2H + gather).
+WORLD_SIZE.  Rank 0 prints ONE JSON line.  A plain run does only what `value` (K pipelined steps) needs: set-up, warm-up, the timed
+region, the line.  With `--full` the line also carries `value_single_launch` (strictly one launch at a time -- the only figure in
+which a launch has the GPU to itself, and where roofline.single_launch.kernel_ms comes from), `value_host_inclusive`
+(dgsqp_solve_batch from host buffers: H2D + solve + D2H + gather), `cpu_baseline`, and -- at the default
+workload -- the other configurations and QP arithmetic under `workloads` (EXTRA_LEGS).
 """
 import argparse
 import ctypes as C
@@ -193,15 +197,24 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=1024, help='scenarios per GPU per step (--scaling weak) or in total per step (strong)')
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak')
     ap.add_argument('--workload', default='dyn_curve_N25', choices=sorted(WORKLOADS))
-    ap.add_argument('--cpu-sample', type=int, default=64, help='scenarios timed on the host for cpu_baseline (0 disables)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything that is not the headline: steps one launch at a time (--single-steps), host-inclusive calls (--host-steps), the CPU '
+                         'baseline (--cpu-sample) and, at the default workload, the other configurations and QP arithmetic (--extras).  Without it those options must be off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed -- u, l, x, status, num_iters, qp_solves, cond, cost of its batch, as dgsqp_fetch_results '
+                         'hands them to a caller -- to DIR/<name>.npy in float64 (rank r > 0 of several: <name>.rank<r>.npy).  The last step is the last in issue order: step K - 1 '
+                         'solves staged batch (K - 1) mod distinct_batches, and a batch gives the same results whichever launch it rides in.  Every array is finite: the NaN '
+                         'and inf some solves end with are written as 0 and counted per scenario in nonfinite.npy.  More than 60 MB: a fixed seeded '
+                         'sample of the scenarios, their numbers in scenario_index.npy')
+    ap.add_argument('--cpu-sample', type=int, default=None, help='--full: scenarios timed on the host for cpu_baseline (default 64, 0 disables)')
     ap.add_argument('--pipeline', type=int, default=5,
                     help='launches in flight per GPU (each on its own HIP stream / hardware queue); 1 = strictly one launch at a time')
     ap.add_argument('--group', type=int, default=0, help='staged batches (= steps) solved by ONE launch with a shared ticket queue (dgsqp_launch_staged_group); '
                     '0 = auto: all of them in one cooperative launch when the timed region has at most 24 steps (a launch ends behind its slowest scenarios once, and its '
                     'deferral of long scenarios sees the whole job), otherwise 12 per launch, pipelined')
     ap.add_argument('--batches', type=int, default=0, help='distinct staged batches = handles the steps cycle through (default: (pipeline + 1) x group, so that a group never waits for the tail of a launch that still holds its handles)')
-    ap.add_argument('--single-steps', type=int, default=3, help='extra one-launch-at-a-time steps behind value_single_launch / roofline.kernel_ms (0 disables)')
-    ap.add_argument('--host-steps', type=int, default=2, help='extra dgsqp_solve_batch calls from host buffers behind value_host_inclusive (0 disables)')
+    ap.add_argument('--single-steps', type=int, default=None, help='--full: extra one-launch-at-a-time steps behind value_single_launch / roofline.single_launch.kernel_ms (default 3, 0 disables)')
+    ap.add_argument('--host-steps', type=int, default=None, help='--full: extra dgsqp_solve_batch calls from host buffers behind value_host_inclusive (default 2, 0 disables)')
     ap.add_argument('--coop', choices=('auto', 'off'), default='auto',
                     help='cooperative line search (dgsqp_set_cooperative): auto = in the LAST launch of the timed region and in launches that run alone -- idle '
                          'workgroups evaluate line-search trials of the scenarios still solving; results are bit-identical; off = never')
@@ -222,11 +235,50 @@ def parse_args(argv=None):
     ap.add_argument('--line', choices=('compact', 'full'), default='compact',
                     help='compact: the ONE stdout line holds the contract keys, config, roofline, cpu_baseline and the headline figures in under 4 KB (full records: bench_workloads.json); '
                          'full: the complete record of this workload (what the extra legs, run as child processes, hand back)')
-    ap.add_argument('--extras', choices=('auto', 'off'), default='auto',
-                    help="auto: the default invocation (configs[1], exact QP, one GPU) also times, in the same run, --qp osqp on configs[1] and BASELINE configs[2], [3], [4] "
+    ap.add_argument('--extras', choices=('auto', 'off'), default=None,
+                    help="--full: auto (default there): the default workload (configs[1], exact QP, one GPU) also times, in the same run, --qp osqp on configs[1] and BASELINE configs[2], [3], [4] "
                          "at the batch sizes BASELINE.json names -- each leg in a child process with a timeout, full records in bench_workloads.json, a four-column summary "
                          "in the line (key 'workloads'); off: only the workload asked for")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    full_only = dict(cpu_sample=64, single_steps=3, host_steps=2, extras='auto')
+    if args.full:
+        for k, v in full_only.items():
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+    else:
+        asked = ['--' + k.replace('_', '-') for k in full_only if getattr(args, k) not in (None, 0, 'off')]
+        if asked:
+            ap.error(f'{", ".join(asked)}: not part of a plain run, add --full')
+        args.cpu_sample, args.single_steps, args.host_steps, args.extras = 0, 0, 0, 'off'
+    return args
+
+
+DUMP_LIMIT = 60 * 10 ** 6           # bytes of one --dump-outputs (the arrays are small next to it at the default batch: 7 MB)
+
+
+def dump_outputs(path, lib, handle, d, B, rank=0):
+    """--dump-outputs: the results of the handle's last solve, as a caller of dgsqp_fetch_results receives them, one float64 .npy each
+    (finite throughout: see nonfinite.npy below)."""
+    from dgsqp_amd import _ffi
+    n, nc, M = int(d.n), int(d.n_c), int(d.M)
+    o = dict(u=np.empty((B, n)), l=np.empty((B, nc)), x=np.empty((B, int(d.N) + 1, int(d.n_q))), status=np.empty(B, np.int32), num_iters=np.empty(B, np.int32),
+             qp_solves=np.empty(B, np.int32), cond=np.empty((B, 3)), cost=np.empty((B, M)))
+    rc = lib.dgsqp_fetch_results(handle, _ffi.dptr(o['u']), _ffi.dptr(o['l']), _ffi.dptr(o['x']), _ffi.iptr(o['status']), _ffi.iptr(o['num_iters']),
+                                 _ffi.iptr(o['qp_solves']), _ffi.dptr(o['cond']), _ffi.dptr(o['cost']))
+    assert rc == 0, lib.dgsqp_last_error(handle)
+    # some solves end with NaN or inf in their iterates and costs (20 of the 1,024 scenarios of a default batch, flagged converged or
+    # max_it alike): a dump holds finite numbers only, so those values are
+    # written as 0 and counted, per scenario, in nonfinite.npy -- a value that turns non-finite from one build to the next shows in both
+    o['nonfinite'] = sum((~np.isfinite(a.reshape(B, -1))).sum(axis=1) for a in list(o.values()))
+    for a in o.values():
+        if a.dtype == np.float64:
+            a[~np.isfinite(a)] = 0.0
+    keep = DUMP_LIMIT // (8 * (sum(a.size // max(B, 1) for a in o.values()) + 1))
+    rows = np.arange(B) if B <= keep else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    o['scenario_index'] = np.arange(B)
+    os.makedirs(path, exist_ok=True)
+    for name, a in o.items():
+        np.save(os.path.join(path, name + (f'.rank{rank}' if rank else '') + '.npy'), np.ascontiguousarray(a[rows], dtype=np.float64))
 
 
 def run_workload(args, rank, local_rank, world):
@@ -387,6 +439,8 @@ def _run_workload(args, rank, local_rank, world, held):
     # the single stats gather: the records of one step (batch 0, solved by handle 0, which owns the communicator)
     rec = comm.gather_stats(B_pad)
     stats = stats_from_records(rec)
+    if getattr(args, 'dump_outputs', None):
+        dump_outputs(args.dump_outputs, lib, handles[(args.steps - 1) % n_batches], d, B, rank)
 
     # ---- one launch at a time (no overlap): per-launch kernel time, single-launch throughput
     single = None

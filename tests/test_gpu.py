@@ -2255,7 +2255,7 @@ def test_bench_line_contract():
     import sys
     root = pathlib.Path(__file__).resolve().parent.parent
     out = subprocess.run([sys.executable, str(root / 'bench.py'), '--workload', 'kb_curve_N25', '--batch', '64', '--steps', '3',
-                          '--warmup', '1', '--cpu-sample', '2', '--pipeline', '2', '--line', 'full'], capture_output=True, text=True, timeout=600, cwd=str(root))
+                          '--warmup', '1', '--full', '--cpu-sample', '2', '--pipeline', '2', '--line', 'full'], capture_output=True, text=True, timeout=600, cwd=str(root))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -2287,7 +2287,7 @@ def test_bench_line_contract():
     assert abs(d['value'] - 64 * 3 / (d['ms_per_step'] * 3e-3)) < 1e-6 * d['value']
     # the default (compact) line of the same workload: everything the contract names, in less than 4 KB, and nothing else on stdout
     out = subprocess.run([sys.executable, str(root / 'bench.py'), '--workload', 'kb_curve_N25', '--batch', '64', '--steps', '3',
-                          '--warmup', '1', '--cpu-sample', '2', '--pipeline', '2', '--single-steps', '1', '--host-steps', '1'], capture_output=True, text=True, timeout=600, cwd=str(root))
+                          '--warmup', '1', '--full', '--cpu-sample', '2', '--pipeline', '2', '--single-steps', '1', '--host-steps', '1'], capture_output=True, text=True, timeout=600, cwd=str(root))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 4096
@@ -2298,3 +2298,46 @@ def test_bench_line_contract():
     assert {'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'kernel', 'kernel_ms', 'hbm'} <= set(c['roofline']) and abs(c['roofline']['frac'] - c['roofline']['achieved'] / 78.6) < 1e-4 * c['roofline']['frac']
     assert {'value', 'unit', 'cores', 'kind', 'sample'} <= set(c['cpu_baseline']) and c['cpu_baseline']['kind'] == 'port' and c['steps'] == 3 and c['config']['workload'] == 'kb_curve_N25'
     assert 'workloads' not in c and abs(c['value'] - 64 * 3 / (c['ms_per_step'] * 3e-3)) < 1e-6 * c['value']
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the contract's line without the figures that take runs of their own, times exactly --steps steps,
+    and --dump-outputs writes the arrays of the last step: float64, finite (what a solve leaves non-finite is written as 0 and counted
+    in nonfinite.npy), the same from run to run, and equal to what solve_batch returns for that batch (staged batch (K - 1) mod distinct_batches,
+    sampled with seed 1 + 1000 * batch)."""
+    import json
+    import pathlib
+    import subprocess
+    import sys
+    root = pathlib.Path(__file__).resolve().parent.parent
+    dumps = []
+    for tag in ('a', 'b'):
+        out = subprocess.run([sys.executable, str(root / 'bench.py'), '--gpus', '1', '--workload', 'kb_curve_N25', '--batch', '64', '--steps', '5', '--warmup', '1',
+                              '--dump-outputs', str(tmp_path / tag)], capture_output=True, text=True, timeout=600, cwd=str(root))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and len(lines[0]) < 4096
+        c = json.loads(lines[0])
+        for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline'):
+            assert key in c, key
+        assert c['steps'] == 5 and c['warmup'] == 1 and c['dtype'] == 'f64' and c['unit'] == 'scenarios/s' and c['higher_is_better'] is True
+        assert abs(c['value'] - 64 * 5 / (c['ms_per_step'] * 5e-3)) < 1e-6 * c['value'] and abs(c['roofline']['solves_per_launch'] * c['roofline']['launches_timed'] - 64 * 5) < 1e-9
+        assert 'cpu_baseline' not in c and 'workloads' not in c and c['value_single_launch'] is None and c['value_host_inclusive'] is None
+        dumps.append({f.name[:-4]: np.load(f) for f in (tmp_path / tag).iterdir()})
+        n_batches = c['config']['distinct_batches']
+    a, b = dumps
+    assert set(a) == set(b) == {'u', 'l', 'x', 'status', 'num_iters', 'qp_solves', 'cond', 'cost', 'nonfinite', 'scenario_index'}
+    assert all(a[k].dtype == np.float64 and len(a[k]) == 64 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]) for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    sys.path.insert(0, str(root))
+    import bench
+    from dgsqp_amd.montecarlo import sample_scenarios
+    from dgsqp_amd.solver import DGSQP
+    game = bench.make_game('kb_curve_N25')
+    solver = DGSQP(*game.solver_args(), print_method=None)
+    x0, u_ws = sample_scenarios(game, 64, seed=1 + 1000 * ((5 - 1) % n_batches), solver=solver if game.sampler == 'first_segment' else None)
+    res = solver.solve_batch(x0, u_ws)
+    assert np.array_equal(res['status'], a['status']) and np.array_equal(res['num_iters'], a['num_iters']) and np.array_equal(res['qp_solves'], a['qp_solves'])
+    finite = lambda v: np.where(np.isfinite(v), v, 0.0)
+    assert all(np.array_equal(finite(res[k]).reshape(a[k].shape), a[k]) for k in ('u', 'l', 'x', 'cond', 'cost'))
+    assert np.array_equal(sum((~np.isfinite(res[k].reshape(64, -1))).sum(axis=1) for k in ('u', 'l', 'x', 'cond', 'cost')), a['nonfinite'])

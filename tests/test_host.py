@@ -146,11 +146,11 @@ def test_half_arena_build_exports_and_plans():
     assert out['b256']['kb_chicane_N25'] == ['refused', 'True']
 
 
-def test_struct_layouts_match_the_header():
+def test_struct_layouts_match_the_header(tmp_path):
     """ctypes mirrors and the C structs agree in size (checked by compiling a tiny C program)."""
     from dgsqp_amd import _ffi
     src = '#include <stdio.h>\n#include "dgsqp.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(dgsqp_agent_t), sizeof(dgsqp_problem_t), sizeof(dgsqp_params_t), sizeof(dgsqp_dims_t), sizeof(dgsqp_timing_t), sizeof(dgsqp_pid_t), sizeof(dgsqp_sampler_t));return 0;}\n'
-    exe = pathlib.Path('/tmp/dgsqp_sizeof')
+    exe = tmp_path / 'dgsqp_sizeof'
     subprocess.run(['gcc', '-x', 'c', '-', '-I', str(ROOT / 'include'), '-o', str(exe)], input=src.encode(), check=True)
     sizes = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     from dgsqp_amd.sampler import SamplerT
@@ -536,10 +536,10 @@ OUT_OF_SCOPE_NAMES = {'IBRParams', 'ALGAMESParams', 'CALTVMPCParams', 'PATHMCPPa
                       'CasadiKinematicUnicycleCombined', 'load_tum_raceline', 'load_mpclab_raceline'}
 
 
-def test_reference_module_paths_resolve_to_this_package():
+def test_reference_module_paths_resolve_to_this_package(tmp_path):
     """the scripts' import block (scripts/DGSQP_ALGAMES_monte_carlo_curve.py:5-15, minus IBR / ALGAMES /
     casadi, which are out of scope) works unchanged against this repo, and the names are this package's.  Run in a fresh
-    interpreter: other tests import the REFERENCE's DGSQP package from /root/reference under the same name."""
+    interpreter, away from the repository's directory: only PYTHONPATH leads to the package."""
     block = '''
 from DGSQP.solvers.DGSQP import DGSQP
 from DGSQP.solvers.PID import PIDLaneFollower
@@ -565,26 +565,20 @@ assert (joint.n_q, joint.n_u) == (12, 4)
 p = DGSQPParams(dt=0.1, N=25, nonmono_ls=True, reg=0.0, beta=0.01)
 print('ok')
 '''
-    out = subprocess.run([sys.executable, '-c', block], cwd='/tmp', env=dict(os.environ, PYTHONPATH=str(ROOT)), capture_output=True, text=True)
+    out = subprocess.run([sys.executable, '-c', block], cwd=str(tmp_path), env=dict(os.environ, PYTHONPATH=str(ROOT)), capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip().endswith('ok'), out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not pathlib.Path('/root/reference/scripts').exists(), reason='reference tree only exists in the build container')
-def test_every_in_scope_import_of_the_reference_scripts_resolves():
+def test_every_in_scope_import_of_the_reference_scripts_resolves(tmp_path):
     """Every ``from DGSQP.<in-scope module> import a, b, c`` line of the reference's scripts resolves against the alias package,
-    except the names that belong to components SURVEY.md section 2 leaves out (listed above, each must really be absent)."""
-    pat = re.compile(r'^from (DGSQP[\w.]*) import (.+)$')
-    wanted = {}
-    for f in sorted(pathlib.Path('/root/reference/scripts').rglob('*.py')):
-        for line in f.read_text().splitlines():
-            m = pat.match(line.strip())
-            if m and m.group(1) in IN_SCOPE_MODULES and m.group(2).strip() != '*':
-                for nm in m.group(2).split(','):
-                    wanted.setdefault(m.group(1), set()).add(nm.split(' as ')[0].strip())
-    assert len(wanted) >= 7
-    code = 'import importlib, json, sys\nw = json.loads(sys.argv[1])\nmissing = [m + "." + n for m in w for n in w[m] if not hasattr(importlib.import_module(m), n)]\nprint(json.dumps(missing))'
+    except the names that belong to components SURVEY.md section 2 leaves out (listed above, each must really be absent).  The
+    modules and names of those lines are recorded in tests/golden/reference_script_imports.json (tools/make_golden.py reference)."""
     import json
-    out = subprocess.run([sys.executable, '-c', code, json.dumps({k: sorted(v) for k, v in wanted.items()})], cwd='/tmp',
+    recorded = json.loads((ROOT / 'tests' / 'golden' / 'reference_script_imports.json').read_text())
+    wanted = {m: set(names) for m, names in recorded.items() if m in IN_SCOPE_MODULES}
+    assert len(wanted) >= 7 and all(wanted.values())
+    code = 'import importlib, json, sys\nw = json.loads(sys.argv[1])\nmissing = [m + "." + n for m in w for n in w[m] if not hasattr(importlib.import_module(m), n)]\nprint(json.dumps(missing))'
+    out = subprocess.run([sys.executable, '-c', code, json.dumps({k: sorted(v) for k, v in wanted.items()})], cwd=str(tmp_path),
                          env=dict(os.environ, PYTHONPATH=str(ROOT)), capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     missing = {m.rsplit('.', 1)[1] for m in json.loads(out.stdout)}
@@ -661,7 +655,7 @@ def test_bench_flop_model_fingerprint_and_extra_legs(tmp_path, games):
 
 
 def test_bench_extra_legs_respect_the_wall_budget(monkeypatch, capsys, tmp_path):
-    """bench.py's default invocation: ONE stdout line of less than 4 KB (the driver keeps an 8 KB tail: round 5's 30 KB line came back
+    """bench.py --full at the default workload: ONE stdout line of less than 4 KB (the driver keeps an 8 KB tail: round 5's 30 KB line came back
     unparsed) with the contract's keys, roofline, cpu_baseline and a four-column summary per extra leg; the legs run as CHILD PROCESSES
     with a timeout each (run_leg) after the headline is safe in the side file; a leg that fails or times out is reported in the line, legs
     that would start after --extras-budget seconds are named as skipped -- none takes the headline down (no GPU needed: run_workload and
@@ -701,7 +695,7 @@ def test_bench_extra_legs_respect_the_wall_budget(monkeypatch, capsys, tmp_path)
     monkeypatch.setattr(bench, 'run_workload', stub)
     monkeypatch.setattr(bench, 'run_leg', leg_stub)
     monkeypatch.setattr(bench, 'SIDECAR', str(tmp_path / 'bench_workloads.json'))
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         monkeypatch.delenv(k, raising=False)
     bench.main()
@@ -744,6 +738,70 @@ def test_bench_extra_legs_respect_the_wall_budget(monkeypatch, capsys, tmp_path)
     bench.main()
     line = json.loads(capsys.readouterr().out.splitlines()[-1])
     assert line['roofline']['flop_model']['pad'] and 'status_fractions' in line
+
+
+def test_bench_plain_run_times_the_headline_only_and_full_adds_the_rest(capsys):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does nothing but the K timed steps: the one-at-a-time steps, the host-inclusive calls, the
+    CPU baseline and the extra legs are off, and asking for one of them without --full is an error (not a silently longer run); --full
+    restores the former defaults, explicit values hold there.  --steps is the number of timed steps as given."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    a = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert (a.single_steps, a.host_steps, a.cpu_sample, a.extras) == (0, 0, 0, 'off')
+    a = bench.parse_args(['--single-steps', '0', '--host-steps', '0', '--cpu-sample', '0', '--extras', 'off', '--dump-outputs', 'somewhere'])      # (what run_leg sends)
+    assert (a.single_steps, a.host_steps, a.cpu_sample, a.extras, a.dump_outputs) == (0, 0, 0, 'off', 'somewhere')
+    for argv in (['--cpu-sample', '2'], ['--single-steps', '1'], ['--host-steps', '1'], ['--extras', 'auto']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+        assert '--full' in capsys.readouterr().err
+    a = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    assert (a.steps, a.single_steps, a.host_steps, a.cpu_sample, a.extras) == (20, 3, 2, 64, 'auto')
+    a = bench.parse_args(['--full', '--cpu-sample', '2', '--extras', 'off', '--host-steps', '0'])
+    assert (a.single_steps, a.host_steps, a.cpu_sample, a.extras) == (3, 0, 2, 'off')
+
+
+def test_bench_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per array a caller of dgsqp_fetch_results receives; a batch that is larger than the limit is cut to
+    a fixed seeded sample of its scenarios, the same one every time, named in scenario_index.npy; every array is finite -- the NaN and inf some
+    solves end with are written as 0 and counted per scenario in nonfinite.npy (stub library: no GPU)."""
+    import types
+    sys.path.insert(0, str(ROOT))
+    import bench
+    d = types.SimpleNamespace(n=6, n_c=9, N=2, n_q=4, M=2)
+    B = 50
+
+    class Lib:
+        def dgsqp_fetch_results(self, h, u, l, x, st, it, qp, cond, cost):
+            for ptr, cnt in ((u, B * 6), (l, B * 9), (x, B * 12), (cond, B * 3), (cost, B * 2)):
+                np.ctypeslib.as_array(ptr, (cnt,))[:] = np.arange(cnt) + 0.5
+            for ptr in (st, it, qp):
+                np.ctypeslib.as_array(ptr, (B,))[:] = np.arange(B) % 5
+            np.ctypeslib.as_array(cost, (B * 2,))[[6, 7]] = np.nan, np.inf          # scenario 3 ended non-finite: both costs
+            np.ctypeslib.as_array(u, (B * 6,))[6 * 3 + 1] = -np.inf                 # ... and one input of its iterate
+            np.ctypeslib.as_array(x, (B * 12,))[12 * 41] = np.nan                   # scenario 41: one state
+            return 0
+
+    bench.dump_outputs(str(tmp_path / 'a'), Lib(), None, d, B)
+    names = {'u': (B, 6), 'l': (B, 9), 'x': (B, 3, 4), 'status': (B,), 'num_iters': (B,), 'qp_solves': (B,), 'cond': (B, 3), 'cost': (B, 2), 'nonfinite': (B,),
+             'scenario_index': (B,)}
+    got = {f.name[:-4]: np.load(f) for f in (tmp_path / 'a').iterdir()}
+    assert set(got) == set(names) and all(got[k].shape == names[k] and got[k].dtype == np.float64 for k in names)
+    assert got['x'][1, 0, 0] == 12.5 and got['status'][7] == 2.0 and (got['scenario_index'] == np.arange(B)).all()
+    assert all(np.isfinite(a).all() for a in got.values())
+    assert (got['cost'][3] == 0).all() and got['u'][3, 1] == 0 and got['u'][3, 0] == 18.5 and got['x'][41, 0, 0] == 0 and got['cost'][4, 0] == 8.5
+    assert got['nonfinite'][3] == 3 and got['nonfinite'][41] == 1 and got['nonfinite'].sum() == 4
+    row_bytes = 8 * (6 + 9 + 12 + 3 + 3 + 2 + 1 + 1)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 20 * row_bytes + 5)
+    bench.dump_outputs(str(tmp_path / 'b'), Lib(), None, d, B)
+    bench.dump_outputs(str(tmp_path / 'c'), Lib(), None, d, B, rank=3)
+    cut = {f.name[:-4]: np.load(f) for f in (tmp_path / 'b').iterdir()}
+    idx = cut['scenario_index'].astype(int)
+    assert len(idx) == 20 and (np.diff(idx) > 0).all() and sum(a.nbytes for a in cut.values()) <= bench.DUMP_LIMIT
+    assert all((cut[k] == got[k][idx]).all() for k in names)
+    assert sorted(f.name for f in (tmp_path / 'c').iterdir()) == sorted(k + '.rank3.npy' for k in names)
+    assert all((np.load(tmp_path / 'c' / (k + '.rank3.npy')) == cut[k]).all() for k in names)
+    assert bench.DUMP_LIMIT <= 64 * 10 ** 6
 
 
 def test_bench_compact_line_of_a_multi_rank_run():

@@ -1,6 +1,7 @@
-"""Regenerates tests/golden/*.  Run in the BUILD container (needs /root/reference for the parameter
-defaults; everything else comes from the repo's own CPU oracle, since the reference solver cannot run
-without CasADi+OSQP -- parity is unpinned, see oracle/dgsqp_oracle.cpp)."""
+"""Regenerates tests/golden/*.  The parameter defaults and the scripts' import lists are read from a checkout of the
+reference (environment variable DGSQP_REFERENCE = its root; `make_golden.py reference` writes these two only);
+everything else comes from the repo's own CPU oracle, since the reference solver cannot run
+without CasADi+OSQP -- parity is unpinned, see oracle/dgsqp_oracle.cpp."""
 import dataclasses
 import json
 import os
@@ -19,8 +20,26 @@ def defaults(cls):
     return {f.name: (None if f.default is dataclasses.MISSING else f.default) for f in dataclasses.fields(cls)}
 
 
+def reference_root():
+    return pathlib.Path(os.environ['DGSQP_REFERENCE'])
+
+
+def script_imports():
+    """{module: names} of every ``from DGSQP... import a, b`` line of the reference's scripts (names only; the test picks the in-scope modules)."""
+    import re
+    pat = re.compile(r'^from (DGSQP[\w.]*) import (.+)$')
+    wanted = {}
+    for f in sorted((reference_root() / 'scripts').rglob('*.py')):
+        for line in f.read_text().splitlines():
+            m = pat.match(line.strip())
+            if m and m.group(2).strip() != '*':
+                for nm in m.group(2).split(','):
+                    wanted.setdefault(m.group(1), set()).add(nm.split(' as ')[0].strip())
+    (GOLD / 'reference_script_imports.json').write_text(json.dumps({k: sorted(v) for k, v in sorted(wanted.items())}, indent=1))
+
+
 def param_defaults():
-    ref = pathlib.Path('/root/reference')
+    ref = reference_root()
     sys.path.insert(0, str(ref))
     os.environ.setdefault('MPLBACKEND', 'Agg')
     from DGSQP.solvers import solver_types as rst
@@ -28,7 +47,9 @@ def param_defaults():
     sys.path.remove(str(ref))
     out = {'DGSQPParams': defaults(rst.DGSQPParams), 'DGSQPV2Params': defaults(rst.DGSQPV2Params), 'PIDParams': defaults(rst.PIDParams),
            'KinematicBicycleConfig': defaults(rmt.KinematicBicycleConfig),
-           'DynamicBicycleConfig': defaults(rmt.DynamicBicycleConfig)}
+           'DynamicBicycleConfig': defaults(rmt.DynamicBicycleConfig),
+           # values a constructor computes from the defaults (__post_init__), as the instance holds them
+           'post_init': {'DynamicBicycleConfig.pacejka_d_front': rmt.DynamicBicycleConfig().pacejka_d_front}}
     (GOLD / 'param_defaults.json').write_text(json.dumps(out, indent=1, sort_keys=True))
     for m in [k for k in sys.modules if k == 'DGSQP' or k.startswith('DGSQP.')]:
         del sys.modules[m]
@@ -77,6 +98,8 @@ def solve_fixtures(only=None):
 
 if __name__ == '__main__':
     only = sys.argv[1:]
-    if not only:
+    if not only or only == ['reference']:
         param_defaults()
-    solve_fixtures(only)
+        script_imports()
+    if only != ['reference']:
+        solve_fixtures(only)

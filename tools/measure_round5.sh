@@ -21,9 +21,9 @@ step() {   # step <name> <stdout file> <command...>: run, record the exit code n
 nproc > $O/nproc.txt
 if [[ $PART == *1* ]]; then
 # the driver's own command: the headline AND, in the same line, --qp osqp + configs[2], [3], [4] at BASELINE's batch sizes (key "workloads")
-step bench_driver $O/bench_driver_steps20_warmup5.json python bench.py --gpus 1 --steps 20 --warmup 5
-step bench_steady $O/bench_dyn_curve_N25_steps120.json python bench.py --cpu-sample 0 --extras off
-step bench_kb_curve_N25 $O/bench_kb_curve_N25.json python bench.py --workload kb_curve_N25 --cpu-sample 0
+step bench_driver $O/bench_driver_steps20_warmup5.json python bench.py --gpus 1 --steps 20 --warmup 5 --full
+step bench_steady $O/bench_dyn_curve_N25_steps120.json python bench.py --full --cpu-sample 0 --extras off
+step bench_kb_curve_N25 $O/bench_kb_curve_N25.json python bench.py --full --workload kb_curve_N25 --cpu-sample 0
 # OSQP's arithmetic on the XL layout (round 5): configs[2], [3], [4] with qp_method = osqp
 step bench_barc3_osqp $O/bench_kb_barc3_N25_B4096_qp_osqp.json python bench.py --workload kb_barc3_N25 --qp osqp --batch 4096 --steps 1 --warmup 0 --pipeline 1 --batches 1 --single-steps 0 --host-steps 0 --cpu-sample 0
 step bench_curve3_osqp $O/bench_kb_curve3_N25_B4096_qp_osqp.json python bench.py --workload kb_curve3_N25 --qp osqp --batch 4096 --steps 1 --warmup 0 --pipeline 1 --batches 1 --single-steps 0 --host-steps 0 --cpu-sample 0
