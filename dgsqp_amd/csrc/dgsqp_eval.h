@@ -219,11 +219,8 @@ __device__ inline void dyn_fc_pair(DynLane& Z, const double* q, double ua, doubl
   dq[7] = vx * se + vy * ce;
 }
 typedef volatile __attribute__((address_space(3))) double vlds_d;
-__device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, clptr ub, clptr du, double alpha, lptr x, lptr prog = nullptr) {
+__device__ inline void dyn_lane_init(DynLane& Z, const DgProb& D, const dgsqp_agent_t& ag, int role) {
   const dgsqp_problem_t& P = D.P;
-  const dgsqp_agent_t& ag = P.agents[a];
-  const int nq = D.nq, qo = D.qoff[a];
-  DynLane Z;
   Z.role = role; Z.simple_slip = ag.simple_slip; Z.pacejka = ag.tire_model == 0; Z.nsegs = P.n_segs;
   Z.L_f = ag.L_f; Z.L_r = ag.L_r; Z.Ll = role == 0 ? ag.L_f : -ag.L_r;
   Z.Bc = role == 0 ? ag.pac_Bf : ag.pac_Br; Z.Cc = role == 0 ? ag.pac_Cf : ag.pac_Cr; Z.Dc = role == 0 ? ag.pac_Df : ag.pac_Dr;
@@ -233,6 +230,13 @@ __device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, cl
   Z.fr = ag.drive_wheels == 0 ? 0.5 : 1.0; Z.ff = ag.drive_wheels == 0 ? 0.5 : 0.0;
   Z.L = P.track_L; Z.invL = D.inv_track_L;
   Z.lo = 1.0; Z.hi = 0.0;   // empty interval: first use seeks
+}
+__device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, clptr ub, clptr du, double alpha, lptr x, lptr prog = nullptr) {
+  const dgsqp_problem_t& P = D.P;
+  const dgsqp_agent_t& ag = P.agents[a];
+  const int nq = D.nq, qo = D.qoff[a];
+  DynLane Z;
+  dyn_lane_init(Z, D, ag, role);
   double q[8], k1[8], k2[8], t[8];
   for (int i = 0; i < 8; i++) q[i] = x[qo + i];
   const double h = P.dt / P.substeps, h2 = 0.5 * h, h6 = h / 6.0;
@@ -280,24 +284,196 @@ __device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, cl
     }
   }
 }
+// ------------------------------------------------------------------------------------------------
+// The pair rollout split along the model's cascade.  The rates of (vx, vy, w) depend on (vx, vy, w) and the held inputs only; the
+// track look-up, the two heading sincos, 1 / (1 - e_y c) and v_lon feed nothing but the rates of (x, y, e_psi, s, e_y).  So the
+// VELOCITY chain (tyre chain, drag, three RK accumulations) runs on wavefront 0 and publishes the (vx, vy, w) it evaluates f_c at;
+// the POSE chain (five RK accumulations) runs on wavefront 1 -- another SIMD -- on the same lane layout and integrates the pose from
+// those stage inputs.  Every value is the same function of the same operands as in dev_rollout_dyn_pair: bit-identical trajectories,
+// and the instruction stream whose length is the latency of the rollout loses everything that touches the pose.
+// Hand-off: a ring of 2^d evaluations in the (dead between two dev_chains) stage-gradient slot e_dJ, three doubles per pair and
+// evaluation, and two progress words counting evaluations published / consumed.  LDS serves one wavefront's accesses in order;
+// the fences keep the compiler from moving the data accesses across the progress words.
+// ------------------------------------------------------------------------------------------------
+#define DG_VPROG 14   // scal slot: f_c evaluations whose (vx, vy, w) the velocity chain has published
+#define DG_PPROG 15   // scal slot: ... the pose chain has taken out of the ring
+struct DynRing { lptr buf, vprog, pprog; int mask, stride, off; };
+// false: the slot cannot hold one evaluation of every pair (tiny horizons with many concurrent trajectories) -- the caller keeps the
+// single-wavefront rollout
+__device__ inline bool dyn_ring_setup(const DgProb& D, int npairs, int pair, DynRing& R) {
+  const int depth = (D.N + 1) * D.nq / (3 * npairs);
+  if (depth < 1 || NT < 128) return false;
+  int d = 1;
+  while (2 * d <= depth && d < 8) d *= 2;
+  R.buf = LP(D.L.e_dJ); R.vprog = LP(D.L.scal) + DG_VPROG; R.pprog = LP(D.L.scal) + DG_PPROG;
+  R.mask = d - 1; R.stride = 3 * npairs; R.off = 3 * pair;
+  return true;
+}
+__device__ inline void dyn_vel_publish(const DynRing& R, int e, int& pseen, const double* v, bool writer) {
+  if (pseen < e - R.mask)      // the ring slot still holds evaluation e - depth: wait until the pose chain has read it
+    while ((pseen = (int)*(vlds_d*)R.pprog) < e - R.mask) __builtin_amdgcn_s_sleep(1);
+  lptr s = R.buf + (e & R.mask) * R.stride + R.off;
+  if (writer) { s[0] = v[0]; s[1] = v[1]; s[2] = v[2]; }
+  __threadfence_block();
+  if (threadIdx.x == 0) *(vlds_d*)R.vprog = (double)(e + 1);
+}
+__device__ inline void dyn_pose_wait(const DynRing& R, int e) {
+  while ((int)*(vlds_d*)R.vprog < e + 1) __builtin_amdgcn_s_sleep(1);
+  __threadfence_block();
+}
+__device__ inline void dyn_pose_take(const DynRing& R, int e, double* v) {
+  dyn_pose_wait(R, e);
+  clptr s = R.buf + (e & R.mask) * R.stride + R.off;
+  v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+  __threadfence_block();
+  if (threadIdx.x == 64) *(vlds_d*)R.pprog = (double)(e + 1);
+}
+// rates of (vx, vy, w): dq[2..4] of dyn_fc_pair
+__device__ inline void dyn_fc_vel(const DynLane& Z, const double* v, double ua, double sd, double cd, double* dv) {
+  const double vx = v[0], vy = v[1], w = v[2];
+  const double vyl = __builtin_fma(w, Z.Ll, vy);
+  const double ay_ = __builtin_fma(vyl, Z.cdl, -vx * Z.sdl), ax_ = __builtin_fma(vx, Z.cdl, vyl * Z.sdl);
+  const double alpha = Z.add - roll_atan2(ay_, ax_);
+  double F;
+  if (Z.pacejka) F = Z.Dc * roll_sin(Z.Cc * roll_atan(Z.Bc * alpha));
+  else F = alpha * Z.lin;
+  const double fyf = dpp_f64<0xA0>(F), fyr = dpp_f64<0xF5>(F);
+  const double avx = __builtin_fabs(vx);
+  double Fx = vx * (-Z.c_da) - vx * avx * Z.c_dr;
+  if (Z.c_r != 0.0) Fx = Fx - pow(avx, Z.p_r) * (vx / sqrt(vx * vx + 1e-6)) * Z.c_r;
+  const double a_r = ua * Z.fr, a_f = ua * Z.ff;
+  const double ax = a_r + a_f * cd + (Fx - fyf * sd) * Z.inv_mass;
+  const double ay = a_f * sd + (fyf * cd + fyr) * Z.inv_mass;
+  dv[0] = ax + w * vy;
+  dv[1] = ay - w * vx;
+  dv[2] = (fyf * cd * Z.L_f - fyr * Z.L_r) * Z.inv_Iz;
+}
+// rates of p = (x, y, e_psi, s, e_y) at the stage input v = (vx, vy, w): dq[0, 1, 5, 6, 7] of dyn_fc_pair
+__device__ inline void dyn_fc_pose(DynLane& Z, const double* p, const double* v, double* dp) {
+  const double vx = v[0], vy = v[1], w = v[2];
+  const double sbar = wrap_s(p[3], Z.L, Z.invL);
+  if (!(sbar >= Z.lo && sbar < Z.hi)) dyn_lane_seek(Z, sbar);     // rare: s crossed a segment boundary
+  const double c = Z.curv;
+  const double psit = (p[3] + (sbar - p[3] - Z.lo)) * Z.slope + Z.ang0;
+  double sa, ca;
+  roll_sincos(Z.role == 0 ? p[2] : p[2] + psit, sa, ca);
+  const double se = dpp_f64<0xA0>(sa), ce = dpp_f64<0xA0>(ca), st = dpp_f64<0xF5>(sa), ct = dpp_f64<0xF5>(ca);
+  const double vlon = (vx * ce - vy * se) * fast_rcp(1.0 - p[4] * c);
+  dp[0] = vx * ct - vy * st;
+  dp[1] = vy * ct + vx * st;
+  dp[2] = w - vlon * c;
+  dp[3] = vlon;
+  dp[4] = vx * se + vy * ce;
+}
+// one substep of the integrator on NC components: the accumulations of dev_rollout_dyn_pair, written the same way
+template <int NC, class FC>
+__device__ __forceinline__ void dyn_rk_substep(int integ, double* q, double h, double h2, double h6, double dt, FC&& fc) {
+  double k1[NC], k2[NC], t[NC];
+  if (integ == DGSQP_INT_RK4) {
+    fc(q, k1);
+    for (int i = 0; i < NC; i++) t[i] = __builtin_fma(k1[i], h2, q[i]);
+    fc(t, k2);
+    for (int i = 0; i < NC; i++) { t[i] = __builtin_fma(k2[i], h2, q[i]); k1[i] = __builtin_fma(k2[i], 2.0, k1[i]); }
+    fc(t, k2);
+    for (int i = 0; i < NC; i++) { t[i] = __builtin_fma(k2[i], h, q[i]); k1[i] = __builtin_fma(k2[i], 2.0, k1[i]); }
+    fc(t, k2);
+    for (int i = 0; i < NC; i++) q[i] = __builtin_fma(k1[i] + k2[i], h6, q[i]);
+  } else if (integ == DGSQP_INT_RK3) {
+    double k3[NC];
+    fc(q, k1);
+    for (int i = 0; i < NC; i++) { k1[i] = k1[i] * h; t[i] = q[i] + k1[i] * 0.5; }
+    fc(t, k2);
+    for (int i = 0; i < NC; i++) { k2[i] = k2[i] * h; t[i] = q[i] - k1[i] + k2[i] * 2.0; }
+    fc(t, k3);
+    for (int i = 0; i < NC; i++) q[i] = q[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
+  } else if (integ == DGSQP_INT_RK2) {
+    fc(q, k1);
+    for (int i = 0; i < NC; i++) t[i] = q[i] + k1[i] * h;
+    fc(t, k2);
+    for (int i = 0; i < NC; i++) q[i] = q[i] + (k1[i] + k2[i]) * h2;
+  } else {
+    fc(q, k1);
+    for (int i = 0; i < NC; i++) q[i] = q[i] + k1[i] * dt;
+  }
+}
+// POSE = false: wavefront 0, POSE = true: wavefront 1, lane 2 * pair + role in both.  prog (fused pass): the pose chain publishes
+// the number of finished stages once BOTH halves of x_{k+1} are in LDS.
+template <bool POSE>
+__device__ inline void dev_rollout_dyn_split(const DgProb& D, int a, int role, const DynRing& R, clptr ub, clptr du, double alpha, lptr x, lptr prog) {
+  const dgsqp_problem_t& P = D.P;
+  const dgsqp_agent_t& ag = P.agents[a];
+  constexpr int NC = POSE ? 5 : 3;
+  const int nq = D.nq, qo = D.qoff[a];
+  DynLane Z;
+  dyn_lane_init(Z, D, ag, role);
+  double q[NC];
+  for (int i = 0; i < NC; i++) q[i] = x[qo + (POSE ? (i < 2 ? i : i + 3) : i + 2)];
+  const double h = P.dt / P.substeps, h2 = 0.5 * h, h6 = h / 6.0;
+  const int integ = P.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : P.substeps;
+  int e = 0, pseen = 0;      // f_c evaluations so far ; the pose chain's progress as last read
+  for (int k = 0; k < D.N; k++) {
+    double ua = 0.0, sd = 0.0, cd = 1.0;
+    if constexpr (!POSE) {
+      const int i0 = am_col(D, a, k, 0);
+      ua = du ? step_u(ub[i0], alpha, du[i0]) : ub[i0];
+      const double us = du ? step_u(ub[i0 + 1], alpha, du[i0 + 1]) : ub[i0 + 1];
+      dev_sincos(us, sd, cd);
+      const bool rot = role == 0 && !ag.simple_slip;
+      Z.cdl = rot ? cd : 1.0; Z.sdl = rot ? sd : 0.0; Z.add = (role == 0 && ag.simple_slip) ? us : 0.0;
+    }
+    for (int m = 0; m < nsub; m++)
+      dyn_rk_substep<NC>(integ, q, h, h2, h6, P.dt, [&](const double* s, double* ds) {
+        if constexpr (POSE) {
+          double v[3];
+          dyn_pose_take(R, e, v);
+          dyn_fc_pose(Z, s, v, ds);
+        } else {
+          dyn_vel_publish(R, e, pseen, s, role == 0);
+          dyn_fc_vel(Z, s, ua, sd, cd, ds);
+        }
+        e++;
+      });
+    // the velocity chain's part of x_{k+1} precedes its next progress word (evaluation e, or the closing one below)
+    if (POSE && prog) dyn_pose_wait(R, e);
+    if (role == 0)
+      for (int i = 0; i < NC; i++) x[(k + 1) * nq + qo + (POSE ? (i < 2 ? i : i + 3) : i + 2)] = q[i];
+    if (POSE && prog) {      // fused rollout + derivative pass: x_{k+1} of every agent is in LDS, tell the other wavefronts
+      __threadfence_block();
+      if (threadIdx.x == 64) *(vlds_d*)prog = (double)(k + 1);
+    }
+  }
+  if constexpr (!POSE) {
+    __threadfence_block();
+    if (threadIdx.x == 0) *(vlds_d*)R.vprog = (double)(e + 1);
+  }
+}
 // K trajectories x^(j) = rollout(ub + alpha_j du), alpha_j = alpha0 tau^j, j < K, on K * (lanes per trajectory) lanes of
 // wavefront 0 (one instruction stream: K trajectories cost the latency of one).  xs[j] has stride xstride doubles.
+// Dynamic bicycles on an arc track: velocity chains on wavefront 0, pose chains on the same lanes of wavefront 1.
 __device__ __noinline__ void dev_rollout_multi(const Ctx& c, clptr ub, clptr du, double alpha0, double tau, int K, lptr xs, int xstride,
                                               int K1 = 1 << 30, lptr xs2 = nullptr) {
   const DgProb& D = dg_prob;
   __syncthreads();
   // trajectory j lives at xs + j xstride for j < K1 and at xs2 + (j - K1) xstride beyond
   for (int i = TID; i < K * D.nq; i += NT) { const int j = i / D.nq; (j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride)[i % D.nq] = c.x0[i % D.nq]; }
+  if (TID == 0) { LP(D.L.scal)[DG_VPROG] = 0.0; LP(D.L.scal)[DG_PPROG] = 0.0; }
   __syncthreads();
   bool all_dyn = D.P.track_kind == DGSQP_TRACK_ARCS;      // the pair rollout caches the arc segment of the track in registers
   for (int a = 0; a < D.M; a++) all_dyn = all_dyn && D.nqa[a] == 8;
   const int per = all_dyn ? 2 * D.M : D.M;
+  DynRing R;
+  const bool split = all_dyn && dyn_ring_setup(D, K * D.M, (TID & 63) >> 1, R);
+  if (split && TID >= 64 && TID - 64 < K * per) {      // pose chains (the progress words were cleared before the barrier above)
+    const int j = (TID - 64) / per, w = (TID - 64) % per;
+    dev_rollout_dyn_split<true>(D, w >> 1, w & 1, R, ub, du, 0.0, j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride, nullptr);
+  }
   if (TID < K * per) {
     const int j = TID / per, w = TID % per;
     double alpha = alpha0;
     for (int t = 0; t < j; t++) alpha *= tau;           // same products as the sequential alpha *= tau
     lptr x = j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride;
-    if (all_dyn) dev_rollout_dyn_pair(D, w >> 1, w & 1, ub, du, alpha, x);
+    if (split) dev_rollout_dyn_split<false>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
+    else if (all_dyn) dev_rollout_dyn_pair(D, w >> 1, w & 1, ub, du, alpha, x);
     else if (D.P.track_kind == DGSQP_TRACK_SPLINE && D.nqa[w] != 4) {
       if (D.nqa[w] == 8) dev_rollout_agent<8, true>(D, w, ub, du, alpha, x); else dev_rollout_agent<6, true>(D, w, ub, du, alpha, x);
     }
@@ -438,9 +614,9 @@ __device__ __noinline__ void dev_dyn_derivs(const Ctx& c, clptr ue) {
 // Fused rollout + derivative pass (dynamic bicycles under a multi-stage integrator).  The rollout is one dependent chain of
 // N x substeps x stages f_c evaluations on a handful of lanes of wavefront 0 (~1.7 M cycles at N = 25, rk4, M = 10) during
 // which the other seven wavefronts of the scenario would sit at a barrier; the derivative items of stage k need nothing but
-// x_k.  Wavefront 0 publishes the number of finished stages in an LDS slot; the other wavefronts pull 64-item tasks in
-// stage order from an LDS ticket and start on a task as soon as its last stage is there; wavefront 0 joins them when its
-// rollout is done.  The second-order items also deliver A_k, B_k, so a point evaluated this way needs no further derivative
+// x_k.  The rollout runs split (dev_rollout_dyn_split: velocity chains on wavefront 0, pose chains on wavefront 1); the pose
+// chain publishes the number of finished stages in an LDS slot; the other wavefronts pull 64-item tasks in stage order from
+// an LDS ticket and start on a task as soon as its last stage is there; wavefronts 0 and 1 join them when their chains are done.  The second-order items also deliver A_k, B_k, so a point evaluated this way needs no further derivative
 // pass (tag 2.0 in scal[DG_XVALID]) -- neither for a trial merit nor for the Hessian of the next linearisation at the same
 // point (the Taylor tensor does not depend on the multipliers).  Same arithmetic as dev_rollout + dev_dyn_derivs<2>.
 // ------------------------------------------------------------------------------------------------
@@ -458,7 +634,7 @@ __device__ __noinline__ void dev_rollout_with_derivs(const Ctx& c, clptr ue, lpt
   lptr sc = LP(L.scal);
   __syncthreads();
   for (int i = TID; i < D.nq; i += NT) x[i] = c.x0[i];
-  if (TID == 0) { sc[DG_PROG] = 0.0; sc[DG_TASK] = 0.0; }
+  if (TID == 0) { sc[DG_PROG] = 0.0; sc[DG_TASK] = 0.0; sc[DG_VPROG] = 0.0; sc[DG_PPROG] = 0.0; }
   for (int a = 0; a < D.M; a++) {
     const int nqa = D.nqa[a];
     for (int it = TID; it < D.N * nqa; it += NT) {       // columns of x, y: identity (they never enter fc)
@@ -470,7 +646,11 @@ __device__ __noinline__ void dev_rollout_with_derivs(const Ctx& c, clptr ue, lpt
   }
   __syncthreads();
   const int wave = TID >> 6, lane = TID & 63;
-  if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn_pair(D, lane >> 1, lane & 1, ue, nullptr, 0.0, x, sc + DG_PROG);
+  DynRing R;
+  if (dyn_ring_setup(D, D.M, lane >> 1, R)) {      // velocity chains on wavefront 0, pose chains on wavefront 1; both join the items afterwards
+    if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn_split<false>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
+    if (wave == 1 && lane < 2 * D.M) dev_rollout_dyn_split<true>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
+  } else if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn_pair(D, lane >> 1, lane & 1, ue, nullptr, 0.0, x, sc + DG_PROG);
   const int nd = D.ndir[0], per_agent = (D.N * nd + 63) >> 6, ntask = per_agent * D.M;
   __attribute__((address_space(3))) unsigned int* ticket = (__attribute__((address_space(3))) unsigned int*)(sc + DG_TASK);
   while (true) {
