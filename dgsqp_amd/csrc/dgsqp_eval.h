@@ -103,8 +103,10 @@ __device__ inline void dev_rollout_agent(const DgProb& D, int a, clptr ub, clptr
 // are the same instruction stream on different data, so lane 2a handles (front axle, e_psi) and lane 2a+1 (rear axle,
 // e_psi + psi_t); results are exchanged inside the quad with DPP.  sincos(delta) is constant over the step and hoisted.
 // Same arithmetic as dev_fc_dyn<0> (dynamics_models.py:2008-2062), evaluated redundantly on both lanes otherwise.
+// f_c is stated once, in the two halves of the model's cascade (dyn_fc_vel, dyn_fc_pose), and so is the integrator (dyn_rk_substep);
+// dev_rollout_dyn runs them as two chains on two wavefronts or, where the hand-off ring does not fit, as one chain on one.
 struct DynLane {
-  // per-lane constants of the pair rollout, loaded once (agent parameters are lane-dependent, i.e. vector loads otherwise)
+  // per-lane constants of the rollout, loaded once (agent parameters are lane-dependent, i.e. vector loads otherwise)
   double L_f, L_r, Bc, Cc, Dc, lin, c_da, c_dr, c_r, p_r, inv_mass, inv_Iz, fr, ff, L, invL;
   int role, simple_slip, pacejka, nsegs;
   double Ll, cdl, sdl, add;      // axle offset (+L_f / -L_r) and, per stage, the rotation into the wheel frame and the slip offset of this lane's axle
@@ -181,43 +183,6 @@ __device__ inline void dyn_lane_seek(DynLane& Z, double sbar) {
   Z.lo = tt[seg]; Z.hi = seg + 1 < Z.nsegs ? tt[seg + 1] : 1e300;
   Z.curv = tt[S1 + seg]; Z.ang0 = tt[2 * S1 + seg]; Z.slope = tt[3 * S1 + seg];
 }
-__device__ inline void dyn_fc_pair(DynLane& Z, const double* q, double ua, double us, double sd, double cd, double* dq) {
-  const double vx = q[2], vy = q[3], w = q[4];
-  const double sbar = wrap_s(q[6], Z.L, Z.invL);
-  if (!(sbar >= Z.lo && sbar < Z.hi)) dyn_lane_seek(Z, sbar);     // rare: s crossed a segment boundary
-  const double c = Z.curv;
-  const double psit = (q[6] + (sbar - q[6] - Z.lo)) * Z.slope + Z.ang0;
-  // role 0: front axle and e_psi ; role 1: rear axle and e_psi + psi_t.  Even / odd lanes differ only in per-lane constants: the axle
-  // offset, the rotation into the wheel frame (identity except for a steered front axle with the exact slip formula) and the offset
-  // of the simple slip formula -- no selects in the chain
-  const bool front = Z.role == 0;
-  const double vyl = __builtin_fma(w, Z.Ll, vy);
-  const double ay_ = __builtin_fma(vyl, Z.cdl, -vx * Z.sdl), ax_ = __builtin_fma(vx, Z.cdl, vyl * Z.sdl);
-  const double alpha = Z.add - roll_atan2(ay_, ax_);
-  double F;
-  if (Z.pacejka) F = Z.Dc * roll_sin(Z.Cc * roll_atan(Z.Bc * alpha));
-  else F = alpha * Z.lin;
-  double sa, ca;
-  roll_sincos(front ? q[5] : q[5] + psit, sa, ca);
-  // exchange inside the pair: quad_perm [0,0,2,2] takes the even lane's value, [1,1,3,3] the odd lane's
-  const double fyf = dpp_f64<0xA0>(F), fyr = dpp_f64<0xF5>(F);
-  const double se = dpp_f64<0xA0>(sa), ce = dpp_f64<0xA0>(ca), st = dpp_f64<0xF5>(sa), ct = dpp_f64<0xF5>(ca);
-  const double avx = __builtin_fabs(vx);
-  double Fx = vx * (-Z.c_da) - vx * avx * Z.c_dr;
-  if (Z.c_r != 0.0) Fx = Fx - pow(avx, Z.p_r) * (vx / sqrt(vx * vx + 1e-6)) * Z.c_r;
-  const double a_r = ua * Z.fr, a_f = ua * Z.ff;
-  const double ax = a_r + a_f * cd + (Fx - fyf * sd) * Z.inv_mass;
-  const double ay = a_f * sd + (fyf * cd + fyr) * Z.inv_mass;
-  const double vlon = (vx * ce - vy * se) * fast_rcp(1.0 - q[7] * c);
-  dq[0] = vx * ct - vy * st;
-  dq[1] = vy * ct + vx * st;
-  dq[2] = ax + w * vy;
-  dq[3] = ay - w * vx;
-  dq[4] = (fyf * cd * Z.L_f - fyr * Z.L_r) * Z.inv_Iz;
-  dq[5] = w - vlon * c;
-  dq[6] = vlon;
-  dq[7] = vx * se + vy * ce;
-}
 typedef volatile __attribute__((address_space(3))) double vlds_d;
 __device__ inline void dyn_lane_init(DynLane& Z, const DgProb& D, const dgsqp_agent_t& ag, int role) {
   const dgsqp_problem_t& P = D.P;
@@ -231,66 +196,14 @@ __device__ inline void dyn_lane_init(DynLane& Z, const DgProb& D, const dgsqp_ag
   Z.L = P.track_L; Z.invL = D.inv_track_L;
   Z.lo = 1.0; Z.hi = 0.0;   // empty interval: first use seeks
 }
-__device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, clptr ub, clptr du, double alpha, lptr x, lptr prog = nullptr) {
-  const dgsqp_problem_t& P = D.P;
-  const dgsqp_agent_t& ag = P.agents[a];
-  const int nq = D.nq, qo = D.qoff[a];
-  DynLane Z;
-  dyn_lane_init(Z, D, ag, role);
-  double q[8], k1[8], k2[8], t[8];
-  for (int i = 0; i < 8; i++) q[i] = x[qo + i];
-  const double h = P.dt / P.substeps, h2 = 0.5 * h, h6 = h / 6.0;
-  const int integ = P.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : P.substeps;
-  for (int k = 0; k < D.N; k++) {
-    const int i0 = am_col(D, a, k, 0);
-    const double ua = du ? step_u(ub[i0], alpha, du[i0]) : ub[i0], us = du ? step_u(ub[i0 + 1], alpha, du[i0 + 1]) : ub[i0 + 1];
-    double sd, cd;
-    dev_sincos(us, sd, cd);
-    const bool rot = role == 0 && !ag.simple_slip;
-    Z.cdl = rot ? cd : 1.0; Z.sdl = rot ? sd : 0.0; Z.add = (role == 0 && ag.simple_slip) ? us : 0.0;
-    for (int m = 0; m < nsub; m++) {
-      if (integ == DGSQP_INT_RK4) {
-        dyn_fc_pair(Z, q, ua, us, sd, cd, k1);
-        for (int i = 0; i < 8; i++) t[i] = __builtin_fma(k1[i], h2, q[i]);
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k2);
-        for (int i = 0; i < 8; i++) { t[i] = __builtin_fma(k2[i], h2, q[i]); k1[i] = __builtin_fma(k2[i], 2.0, k1[i]); }
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k2);
-        for (int i = 0; i < 8; i++) { t[i] = __builtin_fma(k2[i], h, q[i]); k1[i] = __builtin_fma(k2[i], 2.0, k1[i]); }
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k2);
-        for (int i = 0; i < 8; i++) q[i] = __builtin_fma(k1[i] + k2[i], h6, q[i]);
-      } else if (integ == DGSQP_INT_RK3) {
-        double k3[8];
-        dyn_fc_pair(Z, q, ua, us, sd, cd, k1);
-        for (int i = 0; i < 8; i++) { k1[i] = k1[i] * h; t[i] = q[i] + k1[i] * 0.5; }
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k2);
-        for (int i = 0; i < 8; i++) { k2[i] = k2[i] * h; t[i] = q[i] - k1[i] + k2[i] * 2.0; }
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k3);
-        for (int i = 0; i < 8; i++) q[i] = q[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
-      } else if (integ == DGSQP_INT_RK2) {
-        dyn_fc_pair(Z, q, ua, us, sd, cd, k1);
-        for (int i = 0; i < 8; i++) t[i] = q[i] + k1[i] * h;
-        dyn_fc_pair(Z, t, ua, us, sd, cd, k2);
-        for (int i = 0; i < 8; i++) q[i] = q[i] + (k1[i] + k2[i]) * h2;
-      } else {
-        dyn_fc_pair(Z, q, ua, us, sd, cd, k1);
-        for (int i = 0; i < 8; i++) q[i] = q[i] + k1[i] * P.dt;
-      }
-    }
-    if (role == 0)
-      for (int i = 0; i < 8; i++) x[(k + 1) * nq + qo + i] = q[i];
-    if (prog) {      // fused rollout + derivative pass: x_{k+1} of every agent is in LDS, tell the other wavefronts
-      __threadfence_block();
-      if (threadIdx.x == 0) *(vlds_d*)prog = (double)(k + 1);
-    }
-  }
-}
 // ------------------------------------------------------------------------------------------------
-// The pair rollout split along the model's cascade.  The rates of (vx, vy, w) depend on (vx, vy, w) and the held inputs only; the
+// The two-lanes-per-agent rollout split along the model's cascade.  The rates of (vx, vy, w) depend on (vx, vy, w) and the held inputs only; the
 // track look-up, the two heading sincos, 1 / (1 - e_y c) and v_lon feed nothing but the rates of (x, y, e_psi, s, e_y).  So the
 // VELOCITY chain (tyre chain, drag, three RK accumulations) runs on wavefront 0 and publishes the (vx, vy, w) it evaluates f_c at;
 // the POSE chain (five RK accumulations) runs on wavefront 1 -- another SIMD -- on the same lane layout and integrates the pose from
-// those stage inputs.  Every value is the same function of the same operands as in dev_rollout_dyn_pair: bit-identical trajectories,
-// and the instruction stream whose length is the latency of the rollout loses everything that touches the pose.
+// those stage inputs: the instruction stream whose length is the latency of the rollout loses everything that touches the pose.
+// Where the ring below does not fit, ONE chain on wavefront 0 carries all eight components (DYN_BOTH): the same two f_c halves, the
+// pose half fed from the chain's own stage input -- every value is the same function of the same operands: bit-identical trajectories.
 // Hand-off: a ring of 2^d evaluations in the (dead between two dev_chains) stage-gradient slot e_dJ, three doubles per pair and
 // evaluation, and two progress words counting evaluations published / consumed.  LDS serves one wavefront's accesses in order;
 // the fences keep the compiler from moving the data accesses across the progress words.
@@ -298,8 +211,9 @@ __device__ inline void dev_rollout_dyn_pair(const DgProb& D, int a, int role, cl
 #define DG_VPROG 14   // scal slot: f_c evaluations whose (vx, vy, w) the velocity chain has published
 #define DG_PPROG 15   // scal slot: ... the pose chain has taken out of the ring
 struct DynRing { lptr buf, vprog, pprog; int mask, stride, off; };
-// false: the slot cannot hold one evaluation of every pair (tiny horizons with many concurrent trajectories) -- the caller keeps the
-// single-wavefront rollout
+// false: the slot cannot hold one evaluation of every pair (tiny horizons with many concurrent trajectories) -- the caller runs the
+// single-wavefront rollout (DYN_BOTH).  (3 K M > (N + 1) nq: with nq = 8 M that is K > 8 (N + 1) / 3, N <= 4 -- where the layout's
+// ls_spec is 0 for the two-car games: a safety net no game of the package reaches today)
 __device__ inline bool dyn_ring_setup(const DgProb& D, int npairs, int pair, DynRing& R) {
   const int depth = (D.N + 1) * D.nq / (3 * npairs);
   if (depth < 1 || NT < 128) return false;
@@ -328,15 +242,19 @@ __device__ inline void dyn_pose_take(const DynRing& R, int e, double* v) {
   __threadfence_block();
   if (threadIdx.x == 64) *(vlds_d*)R.pprog = (double)(e + 1);
 }
-// rates of (vx, vy, w): dq[2..4] of dyn_fc_pair
+// rates of (vx, vy, w): the tyre chain of this lane's axle, drag, the held inputs
 __device__ inline void dyn_fc_vel(const DynLane& Z, const double* v, double ua, double sd, double cd, double* dv) {
   const double vx = v[0], vy = v[1], w = v[2];
+  // role 0: front axle ; role 1: rear axle.  Even / odd lanes differ only in per-lane constants: the axle offset, the rotation into the
+  // wheel frame (identity except for a steered front axle with the exact slip formula) and the offset of the simple slip formula -- no
+  // selects in the chain
   const double vyl = __builtin_fma(w, Z.Ll, vy);
   const double ay_ = __builtin_fma(vyl, Z.cdl, -vx * Z.sdl), ax_ = __builtin_fma(vx, Z.cdl, vyl * Z.sdl);
   const double alpha = Z.add - roll_atan2(ay_, ax_);
   double F;
   if (Z.pacejka) F = Z.Dc * roll_sin(Z.Cc * roll_atan(Z.Bc * alpha));
   else F = alpha * Z.lin;
+  // exchange inside the pair: quad_perm [0,0,2,2] takes the even lane's value, [1,1,3,3] the odd lane's
   const double fyf = dpp_f64<0xA0>(F), fyr = dpp_f64<0xF5>(F);
   const double avx = __builtin_fabs(vx);
   double Fx = vx * (-Z.c_da) - vx * avx * Z.c_dr;
@@ -348,7 +266,7 @@ __device__ inline void dyn_fc_vel(const DynLane& Z, const double* v, double ua, 
   dv[1] = ay - w * vx;
   dv[2] = (fyf * cd * Z.L_f - fyr * Z.L_r) * Z.inv_Iz;
 }
-// rates of p = (x, y, e_psi, s, e_y) at the stage input v = (vx, vy, w): dq[0, 1, 5, 6, 7] of dyn_fc_pair
+// rates of p = (x, y, e_psi, s, e_y) at the stage input v = (vx, vy, w): track look-up, this lane's heading sincos, v_lon
 __device__ inline void dyn_fc_pose(DynLane& Z, const double* p, const double* v, double* dp) {
   const double vx = v[0], vy = v[1], w = v[2];
   const double sbar = wrap_s(p[3], Z.L, Z.invL);
@@ -356,7 +274,7 @@ __device__ inline void dyn_fc_pose(DynLane& Z, const double* p, const double* v,
   const double c = Z.curv;
   const double psit = (p[3] + (sbar - p[3] - Z.lo)) * Z.slope + Z.ang0;
   double sa, ca;
-  roll_sincos(Z.role == 0 ? p[2] : p[2] + psit, sa, ca);
+  roll_sincos(Z.role == 0 ? p[2] : p[2] + psit, sa, ca);      // role 0: e_psi ; role 1: e_psi + psi_t
   const double se = dpp_f64<0xA0>(sa), ce = dpp_f64<0xA0>(ca), st = dpp_f64<0xF5>(sa), ct = dpp_f64<0xF5>(ca);
   const double vlon = (vx * ce - vy * se) * fast_rcp(1.0 - p[4] * c);
   dp[0] = vx * ct - vy * st;
@@ -365,7 +283,7 @@ __device__ inline void dyn_fc_pose(DynLane& Z, const double* p, const double* v,
   dp[3] = vlon;
   dp[4] = vx * se + vy * ce;
 }
-// one substep of the integrator on NC components: the accumulations of dev_rollout_dyn_pair, written the same way
+// one substep of the integrator on NC components (component by component: the chains may split the state any way)
 template <int NC, class FC>
 __device__ __forceinline__ void dyn_rk_substep(int integ, double* q, double h, double h2, double h6, double dt, FC&& fc) {
   double k1[NC], k2[NC], t[NC];
@@ -396,24 +314,30 @@ __device__ __forceinline__ void dyn_rk_substep(int integ, double* q, double h, d
     for (int i = 0; i < NC; i++) q[i] = q[i] + k1[i] * dt;
   }
 }
-// POSE = false: wavefront 0, POSE = true: wavefront 1, lane 2 * pair + role in both.  prog (fused pass): the pose chain publishes
-// the number of finished stages once BOTH halves of x_{k+1} are in LDS.
-template <bool POSE>
-__device__ inline void dev_rollout_dyn_split(const DgProb& D, int a, int role, const DynRing& R, clptr ub, clptr du, double alpha, lptr x, lptr prog) {
+// DYN_VEL: wavefront 0, DYN_POSE: wavefront 1, lane 2 * pair + role in both; DYN_BOTH: wavefront 0 alone, state (vx, vy, w | x, y, e_psi, s,
+// e_y), no ring (R is not read).  prog (fused pass): the chain that finishes x_{k+1} publishes the number of finished stages once ALL
+// of x_{k+1} is in LDS -- the pose chain, after waiting for the velocity chain's half, or the only chain.
+enum { DYN_VEL = 0, DYN_POSE = 1, DYN_BOTH = 2 };
+// where component i of a chain's state sits in the agent's state (x, y, vx, vy, w, e_psi, s, e_y)
+__device__ constexpr int dyn_pose_comp(int i) { return i < 2 ? i : i + 3; }
+template <int MODE>
+__device__ constexpr int dyn_comp(int i) { return MODE == DYN_POSE ? dyn_pose_comp(i) : (i < 3 ? i + 2 : dyn_pose_comp(i - 3)); }
+template <int MODE>
+__device__ inline void dev_rollout_dyn(const DgProb& D, int a, int role, const DynRing& R, clptr ub, clptr du, double alpha, lptr x, lptr prog) {
   const dgsqp_problem_t& P = D.P;
   const dgsqp_agent_t& ag = P.agents[a];
-  constexpr int NC = POSE ? 5 : 3;
+  constexpr int NC = MODE == DYN_POSE ? 5 : (MODE == DYN_VEL ? 3 : 8);
   const int nq = D.nq, qo = D.qoff[a];
   DynLane Z;
   dyn_lane_init(Z, D, ag, role);
   double q[NC];
-  for (int i = 0; i < NC; i++) q[i] = x[qo + (POSE ? (i < 2 ? i : i + 3) : i + 2)];
+  for (int i = 0; i < NC; i++) q[i] = x[qo + dyn_comp<MODE>(i)];
   const double h = P.dt / P.substeps, h2 = 0.5 * h, h6 = h / 6.0;
   const int integ = P.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : P.substeps;
-  int e = 0, pseen = 0;      // f_c evaluations so far ; the pose chain's progress as last read
+  int e = 0, pseen = 0;      // f_c evaluations so far ; the pose chain's progress as last read  (the ring's bookkeeping: unused in DYN_BOTH)
   for (int k = 0; k < D.N; k++) {
     double ua = 0.0, sd = 0.0, cd = 1.0;
-    if constexpr (!POSE) {
+    if constexpr (MODE != DYN_POSE) {
       const int i0 = am_col(D, a, k, 0);
       ua = du ? step_u(ub[i0], alpha, du[i0]) : ub[i0];
       const double us = du ? step_u(ub[i0 + 1], alpha, du[i0 + 1]) : ub[i0 + 1];
@@ -423,26 +347,29 @@ __device__ inline void dev_rollout_dyn_split(const DgProb& D, int a, int role, c
     }
     for (int m = 0; m < nsub; m++)
       dyn_rk_substep<NC>(integ, q, h, h2, h6, P.dt, [&](const double* s, double* ds) {
-        if constexpr (POSE) {
+        if constexpr (MODE == DYN_POSE) {
           double v[3];
           dyn_pose_take(R, e, v);
           dyn_fc_pose(Z, s, v, ds);
-        } else {
+        } else if constexpr (MODE == DYN_VEL) {
           dyn_vel_publish(R, e, pseen, s, role == 0);
           dyn_fc_vel(Z, s, ua, sd, cd, ds);
+        } else {
+          dyn_fc_vel(Z, s, ua, sd, cd, ds);
+          dyn_fc_pose(Z, s + 3, s, ds + 3);
         }
-        e++;
+        if constexpr (MODE != DYN_BOTH) e++;
       });
     // the velocity chain's part of x_{k+1} precedes its next progress word (evaluation e, or the closing one below)
-    if (POSE && prog) dyn_pose_wait(R, e);
+    if (MODE == DYN_POSE && prog) dyn_pose_wait(R, e);
     if (role == 0)
-      for (int i = 0; i < NC; i++) x[(k + 1) * nq + qo + (POSE ? (i < 2 ? i : i + 3) : i + 2)] = q[i];
-    if (POSE && prog) {      // fused rollout + derivative pass: x_{k+1} of every agent is in LDS, tell the other wavefronts
+      for (int i = 0; i < NC; i++) x[(k + 1) * nq + qo + dyn_comp<MODE>(i)] = q[i];
+    if (MODE != DYN_VEL && prog) {      // fused rollout + derivative pass: x_{k+1} of every agent is in LDS, tell the other wavefronts
       __threadfence_block();
-      if (threadIdx.x == 64) *(vlds_d*)prog = (double)(k + 1);
+      if (threadIdx.x == (MODE == DYN_POSE ? 64 : 0)) *(vlds_d*)prog = (double)(k + 1);
     }
   }
-  if constexpr (!POSE) {
+  if constexpr (MODE == DYN_VEL) {
     __threadfence_block();
     if (threadIdx.x == 0) *(vlds_d*)R.vprog = (double)(e + 1);
   }
@@ -465,15 +392,15 @@ __device__ __noinline__ void dev_rollout_multi(const Ctx& c, clptr ub, clptr du,
   const bool split = all_dyn && dyn_ring_setup(D, K * D.M, (TID & 63) >> 1, R);
   if (split && TID >= 64 && TID - 64 < K * per) {      // pose chains (the progress words were cleared before the barrier above)
     const int j = (TID - 64) / per, w = (TID - 64) % per;
-    dev_rollout_dyn_split<true>(D, w >> 1, w & 1, R, ub, du, 0.0, j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride, nullptr);
+    dev_rollout_dyn<DYN_POSE>(D, w >> 1, w & 1, R, ub, du, 0.0, j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride, nullptr);
   }
   if (TID < K * per) {
     const int j = TID / per, w = TID % per;
     double alpha = alpha0;
     for (int t = 0; t < j; t++) alpha *= tau;           // same products as the sequential alpha *= tau
     lptr x = j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride;
-    if (split) dev_rollout_dyn_split<false>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
-    else if (all_dyn) dev_rollout_dyn_pair(D, w >> 1, w & 1, ub, du, alpha, x);
+    if (split) dev_rollout_dyn<DYN_VEL>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
+    else if (all_dyn) dev_rollout_dyn<DYN_BOTH>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
     else if (D.P.track_kind == DGSQP_TRACK_SPLINE && D.nqa[w] != 4) {
       if (D.nqa[w] == 8) dev_rollout_agent<8, true>(D, w, ub, du, alpha, x); else dev_rollout_agent<6, true>(D, w, ub, du, alpha, x);
     }
@@ -614,7 +541,7 @@ __device__ __noinline__ void dev_dyn_derivs(const Ctx& c, clptr ue) {
 // Fused rollout + derivative pass (dynamic bicycles under a multi-stage integrator).  The rollout is one dependent chain of
 // N x substeps x stages f_c evaluations on a handful of lanes of wavefront 0 (~1.7 M cycles at N = 25, rk4, M = 10) during
 // which the other seven wavefronts of the scenario would sit at a barrier; the derivative items of stage k need nothing but
-// x_k.  The rollout runs split (dev_rollout_dyn_split: velocity chains on wavefront 0, pose chains on wavefront 1); the pose
+// x_k.  The rollout runs split (dev_rollout_dyn: velocity chains on wavefront 0, pose chains on wavefront 1); the pose
 // chain publishes the number of finished stages in an LDS slot; the other wavefronts pull 64-item tasks in stage order from
 // an LDS ticket and start on a task as soon as its last stage is there; wavefronts 0 and 1 join them when their chains are done.  The second-order items also deliver A_k, B_k, so a point evaluated this way needs no further derivative
 // pass (tag 2.0 in scal[DG_XVALID]) -- neither for a trial merit nor for the Hessian of the next linearisation at the same
@@ -648,9 +575,9 @@ __device__ __noinline__ void dev_rollout_with_derivs(const Ctx& c, clptr ue, lpt
   const int wave = TID >> 6, lane = TID & 63;
   DynRing R;
   if (dyn_ring_setup(D, D.M, lane >> 1, R)) {      // velocity chains on wavefront 0, pose chains on wavefront 1; both join the items afterwards
-    if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn_split<false>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
-    if (wave == 1 && lane < 2 * D.M) dev_rollout_dyn_split<true>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
-  } else if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn_pair(D, lane >> 1, lane & 1, ue, nullptr, 0.0, x, sc + DG_PROG);
+    if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn<DYN_VEL>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
+    if (wave == 1 && lane < 2 * D.M) dev_rollout_dyn<DYN_POSE>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
+  } else if (wave == 0 && lane < 2 * D.M) dev_rollout_dyn<DYN_BOTH>(D, lane >> 1, lane & 1, R, ue, nullptr, 0.0, x, sc + DG_PROG);
   const int nd = D.ndir[0], per_agent = (D.N * nd + 63) >> 6, ntask = per_agent * D.M;
   __attribute__((address_space(3))) unsigned int* ticket = (__attribute__((address_space(3))) unsigned int*)(sc + DG_TASK);
   while (true) {

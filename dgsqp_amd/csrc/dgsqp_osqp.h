@@ -12,6 +12,11 @@
 // Stated deviations (shared with the two CPU restatements): adaptive-rho interval fixed at 25 iterations (OSQP derives it from the
 // wall-clock time of its first factorisation), every call starts from rho = 0.1 (inside CasADi's plugin the adapted rho persists).
 //
+// This file holds (a) the LDS layout's own code -- n <= 128, vectors in LDS: products, index tables, W, the register-resident K^-1, the
+// iteration block, the polish -- and (b), at its end, the algorithm itself, stated ONCE for this layout and the XL layout of
+// dgsqp_osqp_xl.h (128 < n <= 320): setup with Ruiz equilibration, the termination check, the driver.  (b) is templated on a layout struct
+// (OsqpLayout here, OxLayout there) that bundles the layout's pointers and the operations of (a).
+//
 // One workgroup per QP; what differs from the literal algorithm is algebra that is exact in exact arithmetic
 // (tools/osqp_reduced_proto.py checks this formulation against the literal one on QPs harvested from SQP runs):
 //   * nothing is ever scaled in place.  Ruiz equilibration carries D (n), E_I (identity rows), E (G rows) and c; column / row norms
@@ -110,12 +115,14 @@ __device__ inline void osqp_m_pass(cgptr M, int n, clptr v, lptr part, lptr out)
   __syncthreads();
 }
 
-// out[d] = max over the entries of dense gradient d of |gd_p| Dv[column(p)]  (same chunk tasks as qp_dense_dots)
-__device__ inline void osqp_dense_absmax(const DgProb& D, clptr gd, clptr Dv, lptr part, lptr out) {
+// out[d] = max over the entries of dense gradient d of |gd_p| Dv[column(p)]  (same chunk tasks as qp_dense_dots).  GP: where the packed
+// gradients live (LDS, or the scratch for the largest games of the XL layout)
+template <class GP>
+__device__ inline void osqp_dense_absmax(const DgProb& D, GP gd, clptr Dv, lptr part, lptr out) {
   __syncthreads();
   for (int t = TID; t < D.ntask; t += NT) {
     const DgTask T = ld_task(t);
-    clptr p = gd + T.p0;
+    const GP p = gd + T.p0;
     clptr w = Dv + T.v0;
     double s = 0.0;
 #pragma unroll
@@ -132,8 +139,9 @@ __device__ inline void osqp_dense_absmax(const DgProb& D, clptr gd, clptr Dv, lp
   }
   __syncthreads();
 }
-// out[col] = max_r E_r |G_r,col|  (structure of gt_mul_t with max for the sum)
-__device__ inline void osqp_gt_absmax(const DgProb& D, clptr gd, clptr E, lptr yd, lptr out) {
+// out[col] = max_r E_r |G_r,col|  (structure of gt_mul_t with max for the sum).  EP: where the row scaling lives (LDS, or the scratch)
+template <class GP, class EP>
+__device__ inline void osqp_gt_absmax(const DgProb& D, GP gd, EP E, lptr yd, lptr out) {
   __syncthreads();
   for (int d = TID; d < D.ndense; d += NT) {
     const DgDense dd = ld_dense(d);
@@ -350,73 +358,6 @@ __device__ inline void osqp_build_tables(const DgProb& D, const OsqpTabs& T) {
   }
   __syncthreads();
 }
-// ------------------------------------------------------------------------------------------------
-// _solve_qp core with OSQP's arithmetic.  In: M (scratch, ws_xM), q, g, packed G.  Out: du (L.o_du), lhat (L.o_lhat).
-// Returns 0 when OSQP hands back a point (solved, solved inaccurate, or the iteration limit: the reference continues from whatever
-// OSQP returns), 1 when it reports primal / dual infeasibility or non-finite data, or when the point is not finite (a NaN step:
-// DGSQP.py:566-585 raises).
-// ------------------------------------------------------------------------------------------------
-// Setup of one OSQP call (no registers shared with the ADMM loop: its own function keeps that loop's register allocation clean):
-// finite-data check, Ruiz equilibration (section 5.1; OSQP scale_data(): 10 passes) into o.Dv / o.EI / o.E, W = Gs' Gs, the index tables.
-// Returns the cost scaling c, or a NaN when the data is not finite.
-__device__ __noinline__ double osqp_setup(const Ctx& c) {
-  const DgProb& D = dg_prob;
-  const int n = D.n, nc = D.nc;
-  const OsqpPtrs o = osqp_ptrs(c);
-  // ---- data must be finite (the conic plugin returns NaN otherwise)
-  {
-    int bad = 0;
-    for (int e = TID; e < n * n; e += NT) bad |= !(__builtin_fabs(o.M[e]) < INFINITY);
-    for (int j = TID; j < n; j += NT) bad |= !(__builtin_fabs(o.q[j]) < INFINITY);
-    for (int r = TID; r < nc; r += NT) bad |= (o.g[r] != o.g[r]);
-    for (int p = TID; p < D.ngd; p += NT) bad |= !(__builtin_fabs(o.gd[p]) < INFINITY);
-    if (__syncthreads_or(bad)) return __builtin_nan("");
-  }
-  // ---- Ruiz equilibration (section 5.1; OSQP scale_data()): 10 passes
-  PROF_BEGIN(po1);
-  for (int j = TID; j < n; j += NT) { o.Dv[j] = 1.0; o.EI[j] = 1.0; }
-  for (int r = TID; r < nc; r += NT) o.E[r] = 1.0;
-  double cc = 1.0;
-  for (int it = 0; it < 10; it++) {
-    osqp_m_pass<true>(o.M, n, o.Dv, o.part, o.tmp);                 // tmp_j = max_i |M_ij| D_i
-    osqp_dense_absmax(D, o.gd, o.Dv, o.dpart, o.ddx);               // ddx_d = max_p |gd_p| D_col(p)
-    for (int r = TID; r < nc; r += NT) {
-      const DgRow R = ld_row(r);
-      double rm;
-      if (R.dense >= 0) rm = o.ddx[R.dense];
-      else {
-        const int c1 = am_col(D, R.a, R.k, R.idx);
-        rm = o.Dv[c1];
-        if ((R.type == DG_R_RATE_UB || R.type == DG_R_RATE_LB) && R.k > 0) rm = fmax(rm, o.Dv[c1 - DGSQP_NUA]);
-      }
-      o.w[r] = 1.0 / sqrt(osqp_limit(o.E[r] * rm));
-    }
-    osqp_gt_absmax(D, o.gd, o.E, o.yd, o.xt);                       // xt_j = max_r E_r |G_rj|
-    for (int j = TID; j < n; j += NT) {
-      const double dj = o.Dv[j], aI = o.EI[j] * dj;
-      const double dn = fmax(cc * dj * o.tmp[j], fmax(aI, dj * o.xt[j]));
-      o.Dv[j] = dj * (1.0 / sqrt(osqp_limit(dn)));
-      o.EI[j] *= 1.0 / sqrt(osqp_limit(aI));
-    }
-    for (int r = TID; r < nc; r += NT) o.E[r] *= o.w[r];
-    osqp_m_pass<true>(o.M, n, o.Dv, o.part, o.tmp);                 // with the new D (barriers inside)
-    double cm = 0, qn = 0;
-    for (int j = TID; j < n; j += NT) { cm += cc * o.Dv[j] * o.tmp[j]; qn = fmax(qn, __builtin_fabs(cc * o.Dv[j] * o.q[j])); }
-    cm = block_sum(cm, o.red);
-    qn = block_max(qn, o.red);
-    const double ct = osqp_limit(cm / n);
-    qn = qn < OSQP_MIN_SCALING ? 1.0 : fmin(qn, OSQP_MAX_SCALING);
-    cc *= 1.0 / fmax(ct, qn);
-  }
-  PROF_END(PH_O_SCALE, po1);
-  // ---- W = Gs' Gs (once per call)
-  PROF_BEGIN(po2);
-  osqp_build_w(D, o);
-  PROF_END(PH_O_W, po2);
-  osqp_build_tables(D, osqp_tabs());
-  return cc;
-}
-
 // Polish (section 4) of the ADMM point held in o.z / o.y (scaled), in unscaled variables (see the header).  On acceptance du / lhat are
 // overwritten with the polished point.  Returns 1 accepted, -1 rejected (or not attempted: more active rows than the T slot holds, a
 // pivot that was not positive); *na_out = active rows.
@@ -598,7 +539,8 @@ __device__ inline void osqp_pmul_fused(PT Pp, clptr t, lptr part, int n, F&& fin
 }
 
 #define DG_OSQP_CHK 40    // scal slots 40..46: what osqp_check hands back -- pri_res, dua_res, eps_pri, eps_dua, the two ratios of the rho rule, flags (1 primal, 2 dual infeasible)
-__device__ inline double osqp_rho_I(const OsqpPtrs& o, int j, double rho) { return o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING ? OSQP_RHO_MIN : rho; }   // "loose" identity row: both bounds beyond 1e26 after scaling
+template <class P>
+__device__ inline double osqp_rho_I(const P& o, int j, double rho) { return o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING ? OSQP_RHO_MIN : rho; }   // "loose" identity row: both bounds beyond 1e26 after scaling
 
 // K(rho)^-1 = (Ps + sigma I + rho_I (E_I D)^2 + rho W)^-1 into the packed-P slot.  Its own function (as are the iteration, the check and
 // the polish below): each piece gets a register allocation of its own -- inlined into one function the sweep's 150 live registers
@@ -787,141 +729,253 @@ __device__ __noinline__ void osqp_iterate_block(const Ctx& c, double rho, double
   }
 }
 
+// The LDS layout as the algorithm below sees it: its pointers and the operations that depend on where the data lives.  (The XL layout's
+// counterpart is OxLayout, dgsqp_osqp_xl.h.)  The size class of n is picked per call of the three pieces that are compiled per class.
+struct OsqpLayout {
+  const Ctx& c;
+  const OsqpPtrs o;
+  static constexpr bool in_place = false;      // the answer is written to du / lhat, next to the scaled iterate
+  __device__ explicit OsqpLayout(const Ctx& c_) : c(c_), o(osqp_ptrs(c_)) {}
+  template <class F>
+  __device__ static auto by_size(F&& f) {
+    const int n = dg_prob.n;
+    if (n <= 32) return f(std::integral_constant<int, 32 / DG_NH>());
+    if (n <= 64) return f(std::integral_constant<int, 64 / DG_NH>());
+    if (n <= 100) return f(std::integral_constant<int, 100 / DG_NH>());
+    return f(std::integral_constant<int, 128 / DG_NH>());
+  }
+  __device__ static void sync() { __syncthreads(); }      // after writes to the row vectors (all in LDS here)
+  __device__ clptr gd() const { return o.gd; }
+  template <bool ABSMAX>
+  __device__ void m_pass(clptr v, lptr out) const { osqp_m_pass<ABSMAX>(o.M, dg_prob.n, v, o.part, out); }
+  __device__ void gt_absmax(lptr out) const { osqp_gt_absmax(dg_prob, o.gd, (clptr)o.E, o.yd, out); }
+  __device__ void gs_mul(clptr v, lptr out) const { osqp_gs_mul(o, v, out); }
+  __device__ void gst_mul(clptr w, lptr sc, lptr out) const { osqp_gst_mul(c, o, w, sc, out); }
+  __device__ lptr ey_slot() const { return o.dy; }        // E y of the check (delta y is free there: its last use was the infeasibility test)
+  __device__ void build_tables_and_w() const {
+    PROF_BEGIN(po2);
+    osqp_build_w(dg_prob, o);
+    PROF_END(PH_O_W, po2);
+    osqp_build_tables(dg_prob, osqp_tabs());
+  }
+  __device__ bool build_k(double rho, double cc) const {
+    if (!by_size([&](auto rpt) { return osqp_build_kinv<decltype(rpt)::value>(c, rho, cc); })) return false;
+    // (the sweep's column buffers lie over delta y and w)
+    for (int r = TID; r < dg_prob.nc; r += NT) { o.dy[r] = 0.0; o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]); }
+    __syncthreads();
+    return true;
+  }
+  __device__ void iterate(double rho, double cc, int count) const {
+    by_size([&](auto rpt) {      // columns of K^-1 per thread (RPT * DG_NH = the size class of n)
+      osqp_iterate_block<(decltype(rpt)::value * DG_NH + NT / 128 - 1) / (NT / 128)>(c, rho, cc, count);
+      return 0;
+    });
+  }
+  __device__ int polish(double cc, double pri_res, double dua_res, int* na) const {
+    return by_size([&](auto rpt) { return osqp_polish<decltype(rpt)::value>(c, cc, pri_res, dua_res, na); });
+  }
+  __device__ void write_iterate(double cinv) const {
+    lptr du = LP(dg_prob.L.o_du), lhat = LP(dg_prob.L.o_lhat);
+    for (int j = TID; j < dg_prob.n; j += NT) du[j] = o.Dv[j] * o.x[j];
+    for (int r = TID; r < dg_prob.nc; r += NT) lhat[r] = cinv * o.E[r] * o.y[r];
+  }
+};
+
+// ================================================================================================
+// OSQP's algorithm, stated once for both layouts.  LT is the layout (OsqpLayout above, OxLayout<GP> of dgsqp_osqp_xl.h): the pointer
+// struct `o` (o.E[r], o.dy[r] read the same for LDS and scratch pointers) and the operations that differ -- the products, the tables and
+// W, K(rho), the iteration block, the polish, where the answer goes, and the barrier after writes to row vectors (LT::sync()).  Each piece
+// below is its own function so that the iteration blocks keep a register allocation of their own.
+// ================================================================================================
+// Setup of one OSQP call: finite-data check, Ruiz equilibration (section 5.1; OSQP scale_data(): 10 passes) into o.Dv / o.EI / o.E, then
+// the layout's index tables and W = Gs' Gs.  Returns the cost scaling c, or a NaN when the data is not finite.
+template <class LT>
+__device__ __noinline__ double osqp_setup(const Ctx& c) {
+  const DgProb& D = dg_prob;
+  const int n = D.n, nc = D.nc;
+  const LT l(c);
+  const auto& o = l.o;
+  const auto gd = l.gd();
+  // ---- data must be finite (the conic plugin returns NaN otherwise)
+  {
+    int bad = 0;
+    for (int e = TID; e < n * n; e += NT) bad |= !(__builtin_fabs(o.M[e]) < INFINITY);
+    for (int j = TID; j < n; j += NT) bad |= !(__builtin_fabs(o.q[j]) < INFINITY);
+    for (int r = TID; r < nc; r += NT) bad |= (o.g[r] != o.g[r]);
+    for (int p = TID; p < D.ngd; p += NT) bad |= !(__builtin_fabs(gd[p]) < INFINITY);
+    if (__syncthreads_or(bad)) return __builtin_nan("");
+  }
+  PROF_BEGIN(po1);
+  for (int j = TID; j < n; j += NT) { o.Dv[j] = 1.0; o.EI[j] = 1.0; }
+  for (int r = TID; r < nc; r += NT) o.E[r] = 1.0;
+  LT::sync();
+  double cc = 1.0;
+  for (int it = 0; it < 10; it++) {
+    l.template m_pass<true>(o.Dv, o.tmp);                           // tmp_j = max_i |M_ij| D_i
+    osqp_dense_absmax(D, gd, o.Dv, o.dpart, o.ddx);                 // ddx_d = max_p |gd_p| D_col(p)
+    for (int r = TID; r < nc; r += NT) {
+      const DgRow R = ld_row(r);
+      double rm;
+      if (R.dense >= 0) rm = o.ddx[R.dense];
+      else {
+        const int c1 = am_col(D, R.a, R.k, R.idx);
+        rm = o.Dv[c1];
+        if ((R.type == DG_R_RATE_UB || R.type == DG_R_RATE_LB) && R.k > 0) rm = fmax(rm, o.Dv[c1 - DGSQP_NUA]);
+      }
+      o.w[r] = 1.0 / sqrt(osqp_limit(o.E[r] * rm));
+    }
+    l.gt_absmax(o.xt);                                              // xt_j = max_r E_r |G_rj|
+    for (int j = TID; j < n; j += NT) {
+      const double dj = o.Dv[j], aI = o.EI[j] * dj;
+      const double dn = fmax(cc * dj * o.tmp[j], fmax(aI, dj * o.xt[j]));
+      o.Dv[j] = dj * (1.0 / sqrt(osqp_limit(dn)));
+      o.EI[j] *= 1.0 / sqrt(osqp_limit(aI));
+    }
+    for (int r = TID; r < nc; r += NT) o.E[r] *= o.w[r];
+    LT::sync();
+    l.template m_pass<true>(o.Dv, o.tmp);                           // with the new D
+    double cm = 0, qn = 0;
+    for (int j = TID; j < n; j += NT) { cm += cc * o.Dv[j] * o.tmp[j]; qn = fmax(qn, __builtin_fabs(cc * o.Dv[j] * o.q[j])); }
+    cm = block_sum(cm, o.red);
+    qn = block_max(qn, o.red);
+    const double ct = osqp_limit(cm / n);
+    qn = qn < OSQP_MIN_SCALING ? 1.0 : fmin(qn, OSQP_MAX_SCALING);
+    cc *= 1.0 / fmax(ct, qn);
+  }
+  PROF_END(PH_O_SCALE, po1);
+  l.build_tables_and_w();
+  return cc;
+}
+
 // The termination tests of a check iteration (section 3.4) and the ratios of the rho rule (5.2); results in scal[DG_OSQP_CHK ..].
 // `approx`: the check at the iteration limit -- OSQP then repeats check_termination with every tolerance times ten
 // (check_termination(work, approximate = 1)); the infeasibility certificates at 10 x eps_inf come out of the same products: flags 4, 8.
+// w is used as work vector and rebuilt by the caller.
+template <class LT>
 __device__ __noinline__ void osqp_check(const Ctx& c, double cc, bool approx) {
   const DgProb& D = dg_prob;
   const int n = D.n, nc = D.nc;
-  const OsqpPtrs o = osqp_ptrs(c);
+  const LT l(c);
+  const auto& o = l.o;
   const double eps_abs = 1e-3, eps_rel = 1e-3, eps_inf = 1e-4, cinv = 1.0 / cc;
   PROF_BEGIN(po5);
-    // primal infeasibility certificate (uses delta y, which the residual products overwrite)
-    bool pinf = false, pinf10 = false, dinf10 = false;
-    {
-      double nrm = 0, lhs = 0;
-      for (int r = TID; r < nc; r += NT) {
-        const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er;
-        const bool inf_u = us > OSQP_INFTY * OSQP_MIN_SCALING, inf_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING;
-        double v = o.dy[r];
-        v = (inf_u && inf_l) ? 0.0 : (inf_u ? fmin(v, 0.0) : (inf_l ? fmax(v, 0.0) : v));
-        o.w[r] = v;
-        nrm = fmax(nrm, __builtin_fabs(er * v));
-        if (!inf_u) lhs += us * fmax(v, 0.0);
-        if (!inf_l) lhs += ls * fmin(v, 0.0);
-      }
-      nrm = block_max(nrm, o.red);
-      lhs = block_sum(lhs, o.red);
-      if (nrm > 1.0 / OSQP_INFTY && lhs < -eps_inf * nrm) {
-        osqp_gst_mul(c, o, o.w, o.w, o.xt);                          // As' dy; the test divides by D again
-        double mx = 0;
-        for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(o.xt[j] / o.Dv[j]));
-        mx = block_max(mx, o.red);
-        pinf = mx < eps_inf * nrm;
-        pinf10 = approx && lhs < -10.0 * eps_inf * nrm && mx < 10.0 * eps_inf * nrm;
-      }
+  // primal infeasibility certificate (uses delta y)
+  bool pinf = false, pinf10 = false, dinf10 = false;
+  {
+    double nrm = 0, lhs = 0;
+    for (int r = TID; r < nc; r += NT) {
+      const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er;
+      const bool inf_u = us > OSQP_INFTY * OSQP_MIN_SCALING, inf_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING;
+      double v = o.dy[r];
+      v = (inf_u && inf_l) ? 0.0 : (inf_u ? fmin(v, 0.0) : (inf_l ? fmax(v, 0.0) : v));
+      o.w[r] = v;
+      nrm = fmax(nrm, __builtin_fabs(er * v));
+      if (!inf_u) lhs += us * fmax(v, 0.0);
+      if (!inf_l) lhs += ls * fmin(v, 0.0);
     }
-    // Ax (G rows) -> w, Px -> rhs, A'y -> xt
-    osqp_gs_mul(o, o.x, o.w);
-    osqp_m_pass<false>(o.M, n, o.tmp, o.part, o.rhs);               // (o.tmp = D x after osqp_gs_mul)
-    for (int j = TID; j < n; j += NT) o.rhs[j] *= cc * o.Dv[j];
-    __syncthreads();
-    osqp_gst_mul(c, o, o.y, o.dy, o.xt);                            // (dy is free here: its last use was the infeasibility test)
-    double pri_res, dua_res, eps_p, eps_d, ad_pr, ad_dr;
-    {
-      double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int r = TID; r < nc; r += NT) {
-        const double ei = 1.0 / o.E[r], ax = o.w[r], zz = o.z[r];
-        v[0] = fmax(v[0], __builtin_fabs(ei * (ax - zz))); v[1] = fmax(v[1], __builtin_fabs(ei * zz)); v[2] = fmax(v[2], __builtin_fabs(ei * ax));
-        v[3] = fmax(v[3], __builtin_fabs(ax - zz)); v[4] = fmax(v[4], __builtin_fabs(zz)); v[5] = fmax(v[5], __builtin_fabs(ax));
-      }
-      for (int j = TID; j < n; j += NT) {
-        const double di = 1.0 / o.Dv[j], px = o.rhs[j], aty = o.xt[j], qs = cc * o.Dv[j] * o.q[j];
-        v[6] = fmax(v[6], __builtin_fabs(o.Dv[j] * o.x[j]));                    // identity rows: |z / E| = |Ax / E| = |D x|
-        v[7] = fmax(v[7], __builtin_fabs(o.EI[j] * o.Dv[j] * o.x[j]));          // ... and |z| = |Ax| scaled
-        u[0] = fmax(u[0], __builtin_fabs(di * (px + qs + aty))); u[1] = fmax(u[1], __builtin_fabs(di * qs)); u[2] = fmax(u[2], __builtin_fabs(di * aty));
-        u[3] = fmax(u[3], __builtin_fabs(di * px)); u[4] = fmax(u[4], __builtin_fabs(px + qs + aty)); u[5] = fmax(u[5], __builtin_fabs(qs));
-        u[6] = fmax(u[6], __builtin_fabs(aty)); u[7] = fmax(u[7], __builtin_fabs(px));
-      }
-      block_max8(v, o.red);
-      block_max8(u, o.red);
-      pri_res = v[0];
-      dua_res = cinv * u[0];
-      eps_p = eps_abs + eps_rel * fmax(fmax(v[1], v[6]), fmax(v[2], v[6]));
-      eps_d = eps_abs + eps_rel * cinv * fmax(u[1], fmax(u[2], u[3]));
-      ad_pr = v[3] / (fmax(fmax(v[4], v[7]), fmax(v[5], v[7])) + 1e-10);
-      ad_dr = u[4] / (fmax(u[5], fmax(u[6], u[7])) + 1e-10);
+    nrm = block_max(nrm, o.red);
+    lhs = block_sum(lhs, o.red);
+    if (nrm > 1.0 / OSQP_INFTY && lhs < -eps_inf * nrm) {
+      l.gst_mul(o.w, o.w, o.xt);                                    // As' dy; the test divides by D again
+      double mx = 0;
+      for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(o.xt[j] / o.Dv[j]));
+      mx = block_max(mx, o.red);
+      pinf = mx < eps_inf * nrm;
+      pinf10 = approx && lhs < -10.0 * eps_inf * nrm && mx < 10.0 * eps_inf * nrm;
     }
-    bool dinf = false;
-    if (!(pri_res <= eps_p && dua_res <= eps_d) && !pinf)
-    {
-      // dual infeasibility certificate
-      double nrm = 0, qdx = 0;
-      for (int j = TID; j < n; j += NT) { nrm = fmax(nrm, __builtin_fabs(o.Dv[j] * o.dx[j])); qdx += cc * o.Dv[j] * o.q[j] * o.dx[j]; }
-      nrm = block_max(nrm, o.red);
-      qdx = block_sum(qdx, o.red);
-      if (nrm > 1.0 / OSQP_INFTY && qdx < -cc * eps_inf * nrm) {
-        osqp_gs_mul(o, o.dx, o.w);                                   // w = As dx; o.tmp = D dx
-        osqp_m_pass<false>(o.M, n, o.tmp, o.part, o.rhs);
-        double mx = 0;
-        for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(cc * o.rhs[j]));      // |Dinv (Ps dx)| = |c M D dx|
-        mx = block_max(mx, o.red);
-        if (mx < cc * eps_inf * nrm) {
-          int viol = 0;
-          for (int r = TID; r < nc; r += NT) {
-            const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er, adx = o.w[r] / er;
-            const bool ok_u = us > OSQP_INFTY * OSQP_MIN_SCALING || adx < eps_inf * nrm;
-            const bool ok_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING || adx > -eps_inf * nrm;
-            viol |= !(ok_u && ok_l);
-          }
-          for (int j = TID; j < n; j += NT) {
-            const bool inf_b = o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING;
-            const double adx = o.Dv[j] * o.dx[j];
-            viol |= !((inf_b || adx < eps_inf * nrm) && (inf_b || adx > -eps_inf * nrm));
-          }
-          dinf = !__syncthreads_or(viol);
+  }
+  // Ax (G rows) -> w, Px -> rhs, A'y -> xt
+  l.gs_mul(o.x, o.w);
+  l.template m_pass<false>(o.tmp, o.rhs);                           // (o.tmp = D x after gs_mul)
+  for (int j = TID; j < n; j += NT) o.rhs[j] *= cc * o.Dv[j];
+  __syncthreads();
+  l.gst_mul(o.y, l.ey_slot(), o.xt);
+  double pri_res, dua_res, eps_p, eps_d, ad_pr, ad_dr;
+  {
+    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int r = TID; r < nc; r += NT) {
+      const double ei = 1.0 / o.E[r], ax = o.w[r], zz = o.z[r];
+      v[0] = fmax(v[0], __builtin_fabs(ei * (ax - zz))); v[1] = fmax(v[1], __builtin_fabs(ei * zz)); v[2] = fmax(v[2], __builtin_fabs(ei * ax));
+      v[3] = fmax(v[3], __builtin_fabs(ax - zz)); v[4] = fmax(v[4], __builtin_fabs(zz)); v[5] = fmax(v[5], __builtin_fabs(ax));
+    }
+    for (int j = TID; j < n; j += NT) {
+      const double di = 1.0 / o.Dv[j], px = o.rhs[j], aty = o.xt[j], qs = cc * o.Dv[j] * o.q[j];
+      v[6] = fmax(v[6], __builtin_fabs(o.Dv[j] * o.x[j]));                    // identity rows: |z / E| = |Ax / E| = |D x|
+      v[7] = fmax(v[7], __builtin_fabs(o.EI[j] * o.Dv[j] * o.x[j]));          // ... and |z| = |Ax| scaled
+      u[0] = fmax(u[0], __builtin_fabs(di * (px + qs + aty))); u[1] = fmax(u[1], __builtin_fabs(di * qs)); u[2] = fmax(u[2], __builtin_fabs(di * aty));
+      u[3] = fmax(u[3], __builtin_fabs(di * px)); u[4] = fmax(u[4], __builtin_fabs(px + qs + aty)); u[5] = fmax(u[5], __builtin_fabs(qs));
+      u[6] = fmax(u[6], __builtin_fabs(aty)); u[7] = fmax(u[7], __builtin_fabs(px));
+    }
+    block_max8(v, o.red);
+    block_max8(u, o.red);
+    pri_res = v[0];
+    dua_res = cinv * u[0];
+    eps_p = eps_abs + eps_rel * fmax(fmax(v[1], v[6]), fmax(v[2], v[6]));
+    eps_d = eps_abs + eps_rel * cinv * fmax(u[1], fmax(u[2], u[3]));
+    ad_pr = v[3] / (fmax(fmax(v[4], v[7]), fmax(v[5], v[7])) + 1e-10);
+    ad_dr = u[4] / (fmax(u[5], fmax(u[6], u[7])) + 1e-10);
+  }
+  bool dinf = false;
+  if (!(pri_res <= eps_p && dua_res <= eps_d) && !pinf) {
+    // dual infeasibility certificate
+    double nrm = 0, qdx = 0;
+    for (int j = TID; j < n; j += NT) { nrm = fmax(nrm, __builtin_fabs(o.Dv[j] * o.dx[j])); qdx += cc * o.Dv[j] * o.q[j] * o.dx[j]; }
+    nrm = block_max(nrm, o.red);
+    qdx = block_sum(qdx, o.red);
+    if (nrm > 1.0 / OSQP_INFTY && qdx < -cc * eps_inf * nrm) {
+      l.gs_mul(o.dx, o.w);                                          // w = As dx; o.tmp = D dx
+      l.template m_pass<false>(o.tmp, o.rhs);
+      double mx = 0;
+      for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(cc * o.rhs[j]));      // |Dinv (Ps dx)| = |c M D dx|
+      mx = block_max(mx, o.red);
+      auto cert = [&](double e) {        // no row, no identity row moves against a finite bound by more than e |dx|  (block-uniform calls)
+        int viol = 0;
+        for (int r = TID; r < nc; r += NT) {
+          const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er, adx = o.w[r] / er;
+          const bool ok_u = us > OSQP_INFTY * OSQP_MIN_SCALING || adx < e * nrm;
+          const bool ok_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING || adx > -e * nrm;
+          viol |= !(ok_u && ok_l);
         }
-        if (approx && qdx < -cc * 10.0 * eps_inf * nrm && mx < cc * 10.0 * eps_inf * nrm) {      // block-uniform
-          const double e10 = 10.0 * eps_inf;
-          int viol = 0;
-          for (int r = TID; r < nc; r += NT) {
-            const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er, adx = o.w[r] / er;
-            const bool ok_u = us > OSQP_INFTY * OSQP_MIN_SCALING || adx < e10 * nrm;
-            const bool ok_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING || adx > -e10 * nrm;
-            viol |= !(ok_u && ok_l);
-          }
-          for (int j = TID; j < n; j += NT) {
-            const bool inf_b = o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING;
-            const double adx = o.Dv[j] * o.dx[j];
-            viol |= !((inf_b || adx < e10 * nrm) && (inf_b || adx > -e10 * nrm));
-          }
-          dinf10 = !__syncthreads_or(viol);
+        for (int j = TID; j < n; j += NT) {
+          const bool inf_b = o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING;
+          const double adx = o.Dv[j] * o.dx[j];
+          viol |= !((inf_b || adx < e * nrm) && (inf_b || adx > -e * nrm));
         }
-      }
+        return !__syncthreads_or(viol);
+      };
+      if (mx < cc * eps_inf * nrm) dinf = cert(eps_inf);
+      if (approx && qdx < -cc * 10.0 * eps_inf * nrm && mx < cc * 10.0 * eps_inf * nrm) dinf10 = cert(10.0 * eps_inf);
     }
-    __syncthreads();
-    if (TID == 0) {
-      o.scal[DG_OSQP_CHK] = pri_res; o.scal[DG_OSQP_CHK + 1] = dua_res; o.scal[DG_OSQP_CHK + 2] = eps_p; o.scal[DG_OSQP_CHK + 3] = eps_d;
-      o.scal[DG_OSQP_CHK + 4] = ad_pr; o.scal[DG_OSQP_CHK + 5] = ad_dr; o.scal[DG_OSQP_CHK + 6] = (pinf ? 1.0 : 0.0) + (dinf ? 2.0 : 0.0) + (pinf10 ? 4.0 : 0.0) + (dinf10 ? 8.0 : 0.0);
-    }
-    __syncthreads();
-    PROF_END(PH_O_CHECK, po5);
+  }
+  __syncthreads();
+  if (TID == 0) {
+    o.scal[DG_OSQP_CHK] = pri_res; o.scal[DG_OSQP_CHK + 1] = dua_res; o.scal[DG_OSQP_CHK + 2] = eps_p; o.scal[DG_OSQP_CHK + 3] = eps_d;
+    o.scal[DG_OSQP_CHK + 4] = ad_pr; o.scal[DG_OSQP_CHK + 5] = ad_dr;
+    o.scal[DG_OSQP_CHK + 6] = (pinf ? 1.0 : 0.0) + (dinf ? 2.0 : 0.0) + (pinf10 ? 4.0 : 0.0) + (dinf10 ? 8.0 : 0.0);
+  }
+  __syncthreads();
+  PROF_END(PH_O_CHECK, po5);
 }
 
-template <int RPT>
+// ------------------------------------------------------------------------------------------------
+// _solve_qp core with OSQP's arithmetic.  In: M (scratch), q, g, packed G.  Out: du (L.o_du), lhat (L.o_lhat).
+// Returns 0 when OSQP hands back a point (solved, solved inaccurate, or the iteration limit: the reference continues from whatever
+// OSQP returns), 1 when it reports primal / dual infeasibility or non-finite data, or when the point is not finite (a NaN step:
+// DGSQP.py:566-585 raises).
+// ------------------------------------------------------------------------------------------------
+template <class LT>
 __device__ __noinline__ int dev_qp_osqp_t(const Ctx& c) {
   const DgProb& D = dg_prob;
-  const DgLds& L = D.L;
-  lptr lds = LP(0);
   const int n = D.n, nc = D.nc;
-  const OsqpPtrs o = osqp_ptrs(c);
-  lptr du = lds + L.o_du, lhat = lds + L.o_lhat;
+  const LT l(c);
+  const auto& o = l.o;
+  clptr du = LP(D.L.o_du), lhat = LP(D.L.o_lhat);
   const int max_iter = 4000, check_every = 25;
   __syncthreads();
   PROF_BEGIN(pt_qp);
   if (TID == 0) { o.scal[DG_QP_NPREV] = 0.0; o.scal[DG_XVALID] = 0.0; }
   // ---- setup: finite data, Ruiz equilibration, W = Gs' Gs, index tables
-  const double cc = osqp_setup(c);
+  const double cc = osqp_setup<LT>(c);
   if (cc != cc) {        // non-finite data: the conic plugin returns NaN
     if (TID == 0) { o.scal[DG_OSQP_INFO] = OSQP_NAN_DATA; o.scal[DG_OSQP_INFO + 1] = 0; o.scal[DG_OSQP_INFO + 2] = 0; }
     __syncthreads();
@@ -932,27 +986,23 @@ __device__ __noinline__ int dev_qp_osqp_t(const Ctx& c) {
   int rho_updates = 0;
   for (int j = TID; j < n; j += NT) { o.x[j] = 0.0; o.dx[j] = 0.0; }
   for (int r = TID; r < nc; r += NT) { o.z[r] = 0.0; o.y[r] = 0.0; o.dy[r] = 0.0; o.w[r] = 0.0; }
-  __syncthreads();
+  LT::sync();
   // The G rows have  l = -inf -> -1e30 E_r,  u = E_r min(-g_r, 1e30):  never equalities (rho_vec = rho on all of them), never "loose"
   // unless -g_r >= 1e26 / E_r (then OSQP gives the row rho_min; not reproduced: no game produces such a row)
   int status = OSQP_MAX_ITER, iters = 0, approx_flags = 0;
   double pri_res = INFINITY, dua_res = INFINITY, eps_p = 0, eps_d = 0;
-  bool need_kinv = true;
+  bool need_k = true;
   PROF_BEGIN(po4);
   static_assert(4000 % 25 == 0, "the iteration limit falls on a termination check");
-  constexpr int PLEN = (RPT * DG_NH + NT / 128 - 1) / (NT / 128);      // columns of K^-1 per thread (RPT * DG_NH = the size class of n)
   for (int it = check_every; it <= max_iter; it += check_every) {       // one block of iterations, then a termination check
-    if (need_kinv) {      // first iteration, or rho was changed by the previous check
-      need_kinv = false;
-      if (!osqp_build_kinv<RPT>(c, rho, cc)) { status = OSQP_NAN_DATA; break; }
-      // (the sweep's column buffers lie over delta y and w)
-      for (int r = TID; r < nc; r += NT) { o.dy[r] = 0.0; o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]); }
-      __syncthreads();
+    if (need_k) {         // first iteration, or rho was changed by the previous check
+      need_k = false;
+      if (!l.build_k(rho, cc)) { status = OSQP_NAN_DATA; break; }        // (leaves w = E (rho z - y): its work buffers lie over w)
     }
-    osqp_iterate_block<PLEN>(c, rho, cc, check_every);
+    l.iterate(rho, cc, check_every);
     iters = it;
     // ---- termination (section 3.4) every 25 iterations; the same products serve the rho adaptation (section 5.2)
-    osqp_check(c, cc, it == max_iter);
+    osqp_check<LT>(c, cc, it == max_iter);
     pri_res = o.scal[DG_OSQP_CHK]; dua_res = o.scal[DG_OSQP_CHK + 1]; eps_p = o.scal[DG_OSQP_CHK + 2]; eps_d = o.scal[DG_OSQP_CHK + 3];
     const double ad_pr = o.scal[DG_OSQP_CHK + 4], ad_dr = o.scal[DG_OSQP_CHK + 5];
     const int flags = (int)o.scal[DG_OSQP_CHK + 6];
@@ -963,11 +1013,7 @@ __device__ __noinline__ int dev_qp_osqp_t(const Ctx& c) {
     // rho adaptation (interval fixed at 25)
     {
       const double rho_new = fmin(fmax(rho * sqrt(ad_pr / (ad_dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-      if (rho_new > rho * 5.0 || rho_new < rho / 5.0) {
-        rho = rho_new;
-        rho_updates++;
-        need_kinv = true;
-      }
+      if (rho_new > rho * 5.0 || rho_new < rho / 5.0) { rho = rho_new; rho_updates++; need_k = true; }
     }
     // (the check used w; the next iteration needs w = E (rho z - y), with the rho just chosen)
     for (int r = TID; r < nc; r += NT) o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]);
@@ -984,12 +1030,16 @@ __device__ __noinline__ int dev_qp_osqp_t(const Ctx& c) {
     else if (approx_flags & 8) status = OSQP_DUAL_INFEASIBLE_INACCURATE;
   }
   __syncthreads();
-  // ---- the ADMM iterate, unscaled, is the answer unless the polish improves on it
-  for (int j = TID; j < n; j += NT) du[j] = o.Dv[j] * o.x[j];
-  for (int r = TID; r < nc; r += NT) lhat[r] = cinv * o.E[r] * o.y[r];
+  // ---- the ADMM iterate, unscaled, is the answer unless the polish improves on it: written next to the scaled iterate before the polish,
+  // or, where x / y ARE the output slots (in_place), over it once the polish has not replaced it
+  if (!LT::in_place) l.write_iterate(cinv);
   int polished = 0, na = 0;
-  if (status == OSQP_SOLVED) polished = osqp_polish<RPT>(c, cc, pri_res, dua_res, &na);
+  if (status == OSQP_SOLVED) polished = l.polish(cc, pri_res, dua_res, &na);
   __syncthreads();
+  if (LT::in_place) {
+    if (polished != 1) l.write_iterate(cinv);
+    __syncthreads();
+  }
   if (TID == 0) {
     o.scal[DG_OSQP_INFO] = (double)status; o.scal[DG_OSQP_INFO + 1] = (double)iters; o.scal[DG_OSQP_INFO + 2] = (double)polished; o.scal[DG_OSQP_INFO + 3] = rho;
     atomicAdd(&dg_osqp_count[0], 1ULL); atomicAdd(&dg_osqp_count[1], (unsigned long long)iters);
@@ -1005,10 +1055,4 @@ __device__ __noinline__ int dev_qp_osqp_t(const Ctx& c) {
   return (nonfinite || status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE ||
           status == OSQP_DUAL_INFEASIBLE_INACCURATE || status == OSQP_NAN_DATA) ? 1 : 0;
 }
-__device__ inline int dev_qp_osqp(const Ctx& c) {
-  const int n = dg_prob.n;
-  if (n <= 32) return dev_qp_osqp_t<32 / DG_NH>(c);
-  if (n <= 64) return dev_qp_osqp_t<64 / DG_NH>(c);
-  if (n <= 100) return dev_qp_osqp_t<100 / DG_NH>(c);
-  return dev_qp_osqp_t<128 / DG_NH>(c);
-}
+__device__ inline int dev_qp_osqp(const Ctx& c) { return dev_qp_osqp_t<OsqpLayout>(c); }

@@ -1,9 +1,13 @@
 // OSQP's arithmetic (dgsqp_osqp.h: the restated ADMM + polish of ca.conic('qp', 'osqp', {polish: True}), DGSQP.py:183-201, 246-249) for
 // the XL layout: 128 < n <= 320 decision variables, BASELINE configs[2], [3], [4] (n = 150, 200, 300; up to 1,587 rows).
 //
-// Same algorithm, same algebra as dgsqp_osqp.h (Ruiz equilibration carried as D, E_I, E, c; the reduced ADMM system
+// The algorithm is literally the code of dgsqp_osqp.h: osqp_setup (finite-data test, Ruiz equilibration), osqp_check (termination tests,
+// infeasibility certificates, the ratios of the rho rule) and dev_qp_osqp_t (initialisation, the block / check / rho loop, the status
+// ladder, the info record, the return rule), with osqp_dense_absmax, osqp_gt_absmax and osqp_rho_I, are templates instantiated here with
+// OxLayout (end of this file).  The algebra is the same too (Ruiz equilibration carried as D, E_I, E, c; the reduced ADMM system
 // K xt = sigma x - qs + As' (rho z - y), K = Ps + sigma I + rho_I (E_I D)^2 + rho W, W = Gs' Gs; identity rows not stored; polish in unscaled
-// variables in range-space form) -- what changes is where the data lives and how K is inverted:
+// variables in range-space form).  What this file holds is layout code -- the products, the tables and W, the K(rho) builder, the iteration
+// block and the polish -- because what changes is where the data lives and how K is inverted:
 //   * the n x n matrices (M, W, the factor J of K / Hu, K^-1, the polish's Y and Schur complement) sit in the workgroup's L2 scratch.  K is
 //     factored by the blocked elimination of dgsqp_xl.h (xl_eliminate_blocked: 16 pivots per pass on the matrix cores) and K^-1 = J J' is
 //     then formed EXPLICITLY, again on the matrix cores (ox_inverse_from_factor): an ADMM iteration streams one n x n matrix, not two;
@@ -72,63 +76,6 @@ __device__ inline void ox_m_pass(cgptr M, int n, clptr v, lptr part, lptr out) {
   __syncthreads();
 }
 
-template <class GP>
-__device__ inline void ox_dense_absmax(const DgProb& D, GP gd, clptr Dv, lptr part, lptr out) {
-  __syncthreads();
-  for (int t = TID; t < D.ntask; t += NT) {
-    const DgTask T = ld_task(t);
-    const GP p = gd + T.p0;
-    clptr w = Dv + T.v0;
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < DG_CHUNK; i++) { const double pv = p[i], wv = w[i]; s = i < T.len ? fmax(s, __builtin_fabs(pv) * wv) : s; }
-    part[t] = s;
-  }
-  __syncthreads();
-  for (int d = TID; d < D.ndense; d += NT) {
-    const DgDense dd = ld_dense(d);
-    const int ts = dd.t0lo + 256 * dd.t0hi;
-    double s = 0;
-    for (int i = 0; i < dd.nt; i++) s = fmax(s, part[ts + i]);
-    out[d] = s;
-  }
-  __syncthreads();
-}
-// out[col] = max_r E_r |G_r,col|
-template <class GP>
-__device__ inline void ox_gt_absmax(const DgProb& D, GP gd, cgptr E, lptr yd, lptr out) {
-  __syncthreads();
-  for (int d = TID; d < D.ndense; d += NT) {
-    const DgDense dd = ld_dense(d);
-    yd[d] = fmax(dd.r_pos >= 0 ? E[dd.r_pos] : 0.0, dd.r_neg >= 0 ? E[dd.r_neg] : 0.0);
-  }
-  __syncthreads();
-  for (int it = TID; it < 4 * D.n; it += NT) {
-    const int col = it >> 2, part = it & 3;
-    const int a = col / (D.N * DGSQP_NUA), rem = col % (D.N * DGSQP_NUA), t = rem / DGSQP_NUA, j = rem % DGSQP_NUA;
-    double s = 0;
-    if (part == 0) {
-      int r;
-      if ((r = D.r_in_ub[a][t][j]) >= 0) s = fmax(s, E[r]);
-      if ((r = D.r_in_lb[a][t][j]) >= 0) s = fmax(s, E[r]);
-      if ((r = D.r_rate_ub[a][t][j]) >= 0) s = fmax(s, E[r]);
-      if ((r = D.r_rate_lb[a][t][j]) >= 0) s = fmax(s, E[r]);
-      if (t + 1 < D.N) {
-        if ((r = D.r_rate_ub[a][t + 1][j]) >= 0) s = fmax(s, E[r]);
-        if ((r = D.r_rate_lb[a][t + 1][j]) >= 0) s = fmax(s, E[r]);
-      }
-    }
-    for (int d = D.stage_dense0[t + 1] + part; d < D.ndense; d += 4) {
-      const DgDense dd = ld_dense(d);
-      if (dd.a == a) s = fmax(s, yd[d] * __builtin_fabs(gd[dd.off + t * DGSQP_NUA + j]));
-      else if (dd.kind == 1 && dd.b == a) s = fmax(s, yd[d] * __builtin_fabs(gd[dd.off + 2 * dd.k + t * DGSQP_NUA + j]));
-    }
-    s = fmax(s, dpp_f64<0xB1>(s));
-    s = fmax(s, dpp_f64<0x4E>(s));
-    if (part == 0) out[col] = s;
-  }
-  __syncthreads();
-}
 // W = Gs' Gs = D G' E^2 G D into the scratch, column by column through the transposed table (ox_build_tables, below): column j's
 // (gradient, value) pairs are scattered into an LDS vector indexed by gradient -- weighted with the E^2 of the rows sharing the gradient --,
 // then every row i >= j gathers its own pairs against it (four lanes per row, independent loads).  Box rows add to the diagonal, rate
@@ -416,8 +363,6 @@ __device__ inline void ox_inverse_from_factor(cgptr J, OT* Ainv, int m) {
   XSYNC();
 }
 
-__device__ inline double ox_rho_I(const OxPtrs& o, int j, double rho) { return o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING ? OSQP_RHO_MIN : rho; }
-
 // out_i = sum_j Kinv_ij v_j for the symmetric matrix held in fp32 (dgsqp_params_t.mixed_precision): fp64 accumulation, half the bytes
 typedef __attribute__((address_space(1))) float glb_f;
 __device__ inline void ox_m_pass_f32(const glb_f* M, int n, clptr v, lptr part, lptr out) {
@@ -446,72 +391,13 @@ __device__ inline void ox_m_pass_f32(const glb_f* M, int n, clptr v, lptr part, 
   __syncthreads();
 }
 
-// Setup: finite-data check, Ruiz equilibration (10 passes), W.  Returns c, or NaN for non-finite data.
-template <class GP>
-__device__ __noinline__ double ox_setup(const Ctx& c, GP gd) {
-  const DgProb& D = dg_prob;
-  const int n = D.n, nc = D.nc;
-  const OxPtrs o = ox_ptrs(c);
-  {
-    int bad = 0;
-    for (int e = TID; e < n * n; e += NT) bad |= !(__builtin_fabs(o.M[e]) < INFINITY);
-    for (int j = TID; j < n; j += NT) bad |= !(__builtin_fabs(o.q[j]) < INFINITY);
-    for (int r = TID; r < nc; r += NT) bad |= (o.g[r] != o.g[r]);
-    for (int p = TID; p < D.ngd; p += NT) bad |= !(__builtin_fabs(gd[p]) < INFINITY);
-    if (__syncthreads_or(bad)) return __builtin_nan("");
-  }
-  PROF_BEGIN(po1);
-  for (int j = TID; j < n; j += NT) { o.Dv[j] = 1.0; o.EI[j] = 1.0; }
-  for (int r = TID; r < nc; r += NT) o.E[r] = 1.0;
-  XSYNC();
-  double cc = 1.0;
-  for (int it = 0; it < 10; it++) {
-    ox_m_pass<true>(o.M, n, o.Dv, o.part, o.tmp);
-    ox_dense_absmax<GP>(D, gd, o.Dv, o.dpart, o.ddx);
-    for (int r = TID; r < nc; r += NT) {
-      const DgRow R = ld_row(r);
-      double rm;
-      if (R.dense >= 0) rm = o.ddx[R.dense];
-      else {
-        const int c1 = am_col(D, R.a, R.k, R.idx);
-        rm = o.Dv[c1];
-        if ((R.type == DG_R_RATE_UB || R.type == DG_R_RATE_LB) && R.k > 0) rm = fmax(rm, o.Dv[c1 - DGSQP_NUA]);
-      }
-      o.w[r] = 1.0 / sqrt(osqp_limit(o.E[r] * rm));
-    }
-    ox_gt_absmax<GP>(D, gd, o.E, o.yd2, o.xt);
-    for (int j = TID; j < n; j += NT) {
-      const double dj = o.Dv[j], aI = o.EI[j] * dj;
-      const double dn = fmax(cc * dj * o.tmp[j], fmax(aI, dj * o.xt[j]));
-      o.Dv[j] = dj * (1.0 / sqrt(osqp_limit(dn)));
-      o.EI[j] *= 1.0 / sqrt(osqp_limit(aI));
-    }
-    for (int r = TID; r < nc; r += NT) o.E[r] *= o.w[r];
-    XSYNC();
-    ox_m_pass<true>(o.M, n, o.Dv, o.part, o.tmp);
-    double cm = 0, qn = 0;
-    for (int j = TID; j < n; j += NT) { cm += cc * o.Dv[j] * o.tmp[j]; qn = fmax(qn, __builtin_fabs(cc * o.Dv[j] * o.q[j])); }
-    cm = block_sum(cm, o.red);
-    qn = block_max(qn, o.red);
-    const double ct = osqp_limit(cm / n);
-    qn = qn < OSQP_MIN_SCALING ? 1.0 : fmin(qn, OSQP_MAX_SCALING);
-    cc *= 1.0 / fmax(ct, qn);
-  }
-  PROF_END(PH_O_SCALE, po1);
-  ox_build_tables<GP>(c, o, gd);
-  PROF_BEGIN(po2);
-  ox_build_w<GP>(c, o, gd);
-  PROF_END(PH_O_W, po2);
-  return cc;
-}
-
 // factor of K(rho) = Ps + sigma I + rho_I (E_I D)^2 + rho W into o.J
 __device__ __noinline__ bool ox_build_k(const Ctx& c, double rho, double cc) {
   const DgProb& D = dg_prob;
   const int n = D.n;
   const OxPtrs o = ox_ptrs(c);
   __syncthreads();
-  for (int j = TID; j < n; j += NT) { const double aI = o.EI[j] * o.Dv[j]; o.tmp[j] = 1e-6 + ox_rho_I(o, j, rho) * aI * aI; }
+  for (int j = TID; j < n; j += NT) { const double aI = o.EI[j] * o.Dv[j]; o.tmp[j] = 1e-6 + osqp_rho_I(o, j, rho) * aI * aI; }
   __syncthreads();
   PROF_BEGIN(po3);
   const bool ok = ox_factor(o.J, n, o.Mm, o.part, o.tv, [&](int i, int k) {
@@ -697,7 +583,7 @@ __device__ __noinline__ void ox_iterate_block(const Ctx& c, GP gd, double rho, d
     }
     for (int j = TID; j < n; j += NT) {
       const double dj = o.Dv[j], aI = o.EI[j] * dj, xj = o.x[j];
-      o.rhs[j] = sigma * xj - cc * dj * o.q[j] + dj * o.xt[j] + aI * ox_rho_I(o, j, rho) * (aI * xj);
+      o.rhs[j] = sigma * xj - cc * dj * o.q[j] + dj * o.xt[j] + aI * osqp_rho_I(o, j, rho) * (aI * xj);
     }
     __syncthreads();
     PROF_END(PH_O_GT, pa1);
@@ -765,111 +651,6 @@ __device__ __noinline__ void ox_iterate_block(const Ctx& c, GP gd, double rho, d
     XSYNC();
     PROF_END(PH_O_UPD, pa4);
   }
-}
-
-// Termination tests of a check iteration and the ratios of the rho rule (osqp_check of dgsqp_osqp.h; delta y is read from the scratch and
-// survives, w is used as work vector and rebuilt by the caller)
-template <class GP>
-__device__ __noinline__ void ox_check(const Ctx& c, GP gd, double cc, bool approx) {
-  const DgProb& D = dg_prob;
-  const int n = D.n, nc = D.nc;
-  const OxPtrs o = ox_ptrs(c);
-  const double eps_abs = 1e-3, eps_rel = 1e-3, eps_inf = 1e-4, cinv = 1.0 / cc;
-  PROF_BEGIN(po5);
-  bool pinf = false, pinf10 = false, dinf10 = false;
-  {
-    double nrm = 0, lhs = 0;
-    for (int r = TID; r < nc; r += NT) {
-      const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er;
-      const bool inf_u = us > OSQP_INFTY * OSQP_MIN_SCALING, inf_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING;
-      double v = o.dy[r];
-      v = (inf_u && inf_l) ? 0.0 : (inf_u ? fmin(v, 0.0) : (inf_l ? fmax(v, 0.0) : v));
-      o.w[r] = v;
-      nrm = fmax(nrm, __builtin_fabs(er * v));
-      if (!inf_u) lhs += us * fmax(v, 0.0);
-      if (!inf_l) lhs += ls * fmin(v, 0.0);
-    }
-    nrm = block_max(nrm, o.red);
-    lhs = block_sum(lhs, o.red);
-    if (nrm > 1.0 / OSQP_INFTY && lhs < -eps_inf * nrm) {
-      ox_gst_mul<GP>(c, o, gd, o.w, o.w, o.xt);
-      double mx = 0;
-      for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(o.xt[j] / o.Dv[j]));
-      mx = block_max(mx, o.red);
-      pinf = mx < eps_inf * nrm;
-      pinf10 = approx && lhs < -10.0 * eps_inf * nrm && mx < 10.0 * eps_inf * nrm;
-    }
-  }
-  // Ax (G rows) -> w, Px -> rhs, A'y -> xt
-  ox_gs_mul<GP>(o, gd, o.x, o.w);
-  ox_m_pass<false>(o.M, n, o.tmp, o.part, o.rhs);                  // (o.tmp = D x after ox_gs_mul)
-  for (int j = TID; j < n; j += NT) o.rhs[j] *= cc * o.Dv[j];
-  __syncthreads();
-  ox_gst_mul<GP>(c, o, gd, o.y, o.dpart, o.xt);                           // (E y into the slot behind w -- at least n_c doubles, dgsqp_layout.h: the dense-dot partials, rebuilt by every product)
-  double pri_res, dua_res, eps_p, eps_d, ad_pr, ad_dr;
-  {
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = TID; r < nc; r += NT) {
-      const double ei = 1.0 / o.E[r], ax = o.w[r], zz = o.z[r];
-      v[0] = fmax(v[0], __builtin_fabs(ei * (ax - zz))); v[1] = fmax(v[1], __builtin_fabs(ei * zz)); v[2] = fmax(v[2], __builtin_fabs(ei * ax));
-      v[3] = fmax(v[3], __builtin_fabs(ax - zz)); v[4] = fmax(v[4], __builtin_fabs(zz)); v[5] = fmax(v[5], __builtin_fabs(ax));
-    }
-    for (int j = TID; j < n; j += NT) {
-      const double di = 1.0 / o.Dv[j], px = o.rhs[j], aty = o.xt[j], qs = cc * o.Dv[j] * o.q[j];
-      v[6] = fmax(v[6], __builtin_fabs(o.Dv[j] * o.x[j]));
-      v[7] = fmax(v[7], __builtin_fabs(o.EI[j] * o.Dv[j] * o.x[j]));
-      u[0] = fmax(u[0], __builtin_fabs(di * (px + qs + aty))); u[1] = fmax(u[1], __builtin_fabs(di * qs)); u[2] = fmax(u[2], __builtin_fabs(di * aty));
-      u[3] = fmax(u[3], __builtin_fabs(di * px)); u[4] = fmax(u[4], __builtin_fabs(px + qs + aty)); u[5] = fmax(u[5], __builtin_fabs(qs));
-      u[6] = fmax(u[6], __builtin_fabs(aty)); u[7] = fmax(u[7], __builtin_fabs(px));
-    }
-    block_max8(v, o.red);
-    block_max8(u, o.red);
-    pri_res = v[0];
-    dua_res = cinv * u[0];
-    eps_p = eps_abs + eps_rel * fmax(fmax(v[1], v[6]), fmax(v[2], v[6]));
-    eps_d = eps_abs + eps_rel * cinv * fmax(u[1], fmax(u[2], u[3]));
-    ad_pr = v[3] / (fmax(fmax(v[4], v[7]), fmax(v[5], v[7])) + 1e-10);
-    ad_dr = u[4] / (fmax(u[5], fmax(u[6], u[7])) + 1e-10);
-  }
-  bool dinf = false;
-  if (!(pri_res <= eps_p && dua_res <= eps_d) && !pinf) {
-    double nrm = 0, qdx = 0;
-    for (int j = TID; j < n; j += NT) { nrm = fmax(nrm, __builtin_fabs(o.Dv[j] * o.dx[j])); qdx += cc * o.Dv[j] * o.q[j] * o.dx[j]; }
-    nrm = block_max(nrm, o.red);
-    qdx = block_sum(qdx, o.red);
-    if (nrm > 1.0 / OSQP_INFTY && qdx < -cc * eps_inf * nrm) {
-      ox_gs_mul<GP>(o, gd, o.dx, o.w);                             // w = As dx; o.tmp = D dx
-      ox_m_pass<false>(o.M, n, o.tmp, o.part, o.rhs);
-      double mx = 0;
-      for (int j = TID; j < n; j += NT) mx = fmax(mx, __builtin_fabs(cc * o.rhs[j]));
-      mx = block_max(mx, o.red);
-      auto cert = [&](double e) {
-        int viol = 0;
-        for (int r = TID; r < nc; r += NT) {
-          const double er = o.E[r], us = er * fmin(-o.g[r], OSQP_INFTY), ls = -OSQP_INFTY * er, adx = o.w[r] / er;
-          const bool ok_u = us > OSQP_INFTY * OSQP_MIN_SCALING || adx < e * nrm;
-          const bool ok_l = ls < -OSQP_INFTY * OSQP_MIN_SCALING || adx > -e * nrm;
-          viol |= !(ok_u && ok_l);
-        }
-        for (int j = TID; j < n; j += NT) {
-          const bool inf_b = o.EI[j] * OSQP_INFTY > OSQP_INFTY * OSQP_MIN_SCALING;
-          const double adx = o.Dv[j] * o.dx[j];
-          viol |= !((inf_b || adx < e * nrm) && (inf_b || adx > -e * nrm));
-        }
-        return !__syncthreads_or(viol);
-      };
-      if (mx < cc * eps_inf * nrm) dinf = cert(eps_inf);
-      if (approx && qdx < -cc * 10.0 * eps_inf * nrm && mx < cc * 10.0 * eps_inf * nrm) dinf10 = cert(10.0 * eps_inf);
-    }
-  }
-  __syncthreads();
-  if (TID == 0) {
-    o.scal[DG_OSQP_CHK] = pri_res; o.scal[DG_OSQP_CHK + 1] = dua_res; o.scal[DG_OSQP_CHK + 2] = eps_p; o.scal[DG_OSQP_CHK + 3] = eps_d;
-    o.scal[DG_OSQP_CHK + 4] = ad_pr; o.scal[DG_OSQP_CHK + 5] = ad_dr;
-    o.scal[DG_OSQP_CHK + 6] = (pinf ? 1.0 : 0.0) + (dinf ? 2.0 : 0.0) + (pinf10 ? 4.0 : 0.0) + (dinf10 ? 8.0 : 0.0);
-  }
-  __syncthreads();
-  PROF_END(PH_O_CHECK, po5);
 }
 
 // Polish (section 4) of the ADMM point in o.z / o.y (scaled), in unscaled variables; on acceptance du / lhat (= o.x / o.y slots) hold the
@@ -1042,87 +823,47 @@ __device__ __noinline__ int ox_polish(const Ctx& c, GP gd, double cc, double pri
   return polished;
 }
 
+// The XL layout as the algorithm of dgsqp_osqp.h sees it (the counterpart of OsqpLayout).  GP: where the packed gradients live -- LDS, or the
+// scratch for the largest games (DgProb.gd_global).
 template <class GP>
-__device__ __noinline__ int dev_qp_osqp_xl_t(const Ctx& c, GP gd) {
-  const DgProb& D = dg_prob;
-  const int n = D.n, nc = D.nc;
-  const OxPtrs o = ox_ptrs(c);
-  const int max_iter = 4000, check_every = 25;
-  __syncthreads();
-  PROF_BEGIN(pt_qp);
-  if (TID == 0) { o.scal[DG_QP_NPREV] = 0.0; o.scal[DG_XVALID] = 0.0; }
-  const double cc = ox_setup<GP>(c, gd);
-  if (cc != cc) {
-    if (TID == 0) { o.scal[DG_OSQP_INFO] = OSQP_NAN_DATA; o.scal[DG_OSQP_INFO + 1] = 0; o.scal[DG_OSQP_INFO + 2] = 0; }
+struct OxLayout {
+  const Ctx& c;
+  const OxPtrs o;
+  const GP g_;
+  static constexpr bool in_place = true;       // x / y are the output slots du / lhat
+  __device__ static GP grad(const OxPtrs& o) { if constexpr (std::is_same<GP, cgptr>::value) return o.gdG; else return o.gdL; }
+  __device__ explicit OxLayout(const Ctx& c_) : c(c_), o(ox_ptrs(c_)), g_(grad(o)) {}
+  __device__ static void sync() { XSYNC(); }   // after writes to the row vectors: E and delta y live in the scratch
+  __device__ GP gd() const { return g_; }
+  template <bool ABSMAX>
+  __device__ void m_pass(clptr v, lptr out) const { ox_m_pass<ABSMAX>(o.M, dg_prob.n, v, o.part, out); }
+  __device__ void gt_absmax(lptr out) const { osqp_gt_absmax(dg_prob, g_, (cgptr)o.E, o.yd2, out); }
+  __device__ void gs_mul(clptr v, lptr out) const { ox_gs_mul<GP>(o, g_, v, out); }
+  __device__ void gst_mul(clptr w, lptr sc, lptr out) const { ox_gst_mul<GP>(c, o, g_, w, sc, out); }
+  __device__ lptr ey_slot() const { return o.dpart; }     // E y of the check: the slot behind w -- at least n_c doubles (dgsqp_layout.h), the dense-dot partials, rebuilt by every product; delta y survives the check
+  __device__ void build_tables_and_w() const {
+    ox_build_tables<GP>(c, o, g_);
+    PROF_BEGIN(po2);
+    ox_build_w<GP>(c, o, g_);
+    PROF_END(PH_O_W, po2);
+  }
+  __device__ bool build_k(double rho, double cc) const {
+    if (!ox_build_k(c, rho, cc)) return false;
+    // (the elimination's multipliers lie over w)
+    for (int r = TID; r < dg_prob.nc; r += NT) o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]);
     __syncthreads();
-    return 1;
+    return true;
   }
-  const double cinv = 1.0 / cc;
-  double rho = D.par.osqp_rho_carry ? o.scal[DG_OSQP_RHO] : 0.1;      // (carried from the scenario's previous call: include/dgsqp.h)
-  int rho_updates = 0;
-  for (int j = TID; j < n; j += NT) { o.x[j] = 0.0; o.dx[j] = 0.0; }
-  for (int r = TID; r < nc; r += NT) { o.z[r] = 0.0; o.y[r] = 0.0; o.dy[r] = 0.0; o.w[r] = 0.0; }
-  XSYNC();
-  int status = OSQP_MAX_ITER, iters = 0, approx_flags = 0;
-  double pri_res = INFINITY, dua_res = INFINITY, eps_p = 0, eps_d = 0;
-  bool need_k = true;
-  PROF_BEGIN(po4);
-  for (int it = check_every; it <= max_iter; it += check_every) {       // one block of iterations, then a termination check
-    if (need_k) {
-      need_k = false;
-      if (!ox_build_k(c, rho, cc)) { status = OSQP_NAN_DATA; break; }
-      // (the elimination's multipliers lie over w)
-      for (int r = TID; r < nc; r += NT) o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]);
-      __syncthreads();
-    }
-    if (n <= 176) ox_iterate_block<GP, false>(c, gd, rho, cc, check_every); else ox_iterate_block<GP, true>(c, gd, rho, cc, check_every);
-    iters = it;
-    ox_check<GP>(c, gd, cc, it == max_iter);
-    pri_res = o.scal[DG_OSQP_CHK]; dua_res = o.scal[DG_OSQP_CHK + 1]; eps_p = o.scal[DG_OSQP_CHK + 2]; eps_d = o.scal[DG_OSQP_CHK + 3];
-    const double ad_pr = o.scal[DG_OSQP_CHK + 4], ad_dr = o.scal[DG_OSQP_CHK + 5];
-    const int flags = (int)o.scal[DG_OSQP_CHK + 6];
-    if (pri_res <= eps_p && dua_res <= eps_d) { status = OSQP_SOLVED; break; }
-    if (flags & 1) { status = OSQP_PRIMAL_INFEASIBLE; break; }
-    if (flags & 2) { status = OSQP_DUAL_INFEASIBLE; break; }
-    approx_flags = flags;
-    {
-      const double rho_new = fmin(fmax(rho * sqrt(ad_pr / (ad_dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-      if (rho_new > rho * 5.0 || rho_new < rho / 5.0) { rho = rho_new; rho_updates++; need_k = true; }
-    }
-    for (int r = TID; r < nc; r += NT) o.w[r] = o.E[r] * (rho * o.z[r] - o.y[r]);
-    __syncthreads();
+  __device__ void iterate(double rho, double cc, int count) const {
+    if (dg_prob.n <= 176) ox_iterate_block<GP, false>(c, g_, rho, cc, count); else ox_iterate_block<GP, true>(c, g_, rho, cc, count);
   }
-  PROF_END(PH_O_ADMM, po4);
-  PROF_COUNT(PH_O_ITERS, iters);
-  if (status == OSQP_MAX_ITER && iters == max_iter) {
-    if (pri_res <= 10.0 * eps_p && dua_res <= 10.0 * eps_d) status = OSQP_SOLVED_INACCURATE;
-    else if (approx_flags & 4) status = OSQP_PRIMAL_INFEASIBLE_INACCURATE;
-    else if (approx_flags & 8) status = OSQP_DUAL_INFEASIBLE_INACCURATE;
+  __device__ int polish(double cc, double pri_res, double dua_res, int* na) const { return ox_polish<GP>(c, g_, cc, pri_res, dua_res, na); }
+  __device__ void write_iterate(double cinv) const {      // in place, after a polish that did not replace the point
+    for (int j = TID; j < dg_prob.n; j += NT) o.x[j] = o.Dv[j] * o.x[j];
+    for (int r = TID; r < dg_prob.nc; r += NT) o.y[r] = cinv * o.E[r] * o.y[r];
   }
-  __syncthreads();
-  int polished = 0, na = 0;
-  if (status == OSQP_SOLVED) polished = ox_polish<GP>(c, gd, cc, pri_res, dua_res, &na);
-  __syncthreads();
-  if (polished != 1) {      // the ADMM iterate, unscaled, in place (x is du's slot, y is lhat's)
-    for (int j = TID; j < n; j += NT) o.x[j] = o.Dv[j] * o.x[j];
-    for (int r = TID; r < nc; r += NT) o.y[r] = cinv * o.E[r] * o.y[r];
-  }
-  __syncthreads();
-  if (TID == 0) {
-    o.scal[DG_OSQP_INFO] = (double)status; o.scal[DG_OSQP_INFO + 1] = (double)iters; o.scal[DG_OSQP_INFO + 2] = (double)polished; o.scal[DG_OSQP_INFO + 3] = rho;
-    atomicAdd(&dg_osqp_count[0], 1ULL); atomicAdd(&dg_osqp_count[1], (unsigned long long)iters);
-    if (D.par.osqp_rho_carry) o.scal[DG_OSQP_RHO] = rho;
-    o.scal[DG_OSQP_INFO + 4] = (double)rho_updates; o.scal[DG_OSQP_INFO + 5] = (double)na; o.scal[DG_OSQP_INFO + 6] = pri_res; o.scal[DG_OSQP_INFO + 7] = dua_res;
-  }
-  int nonfinite = 0;
-  for (int j = TID; j < n; j += NT) nonfinite |= !(__builtin_fabs(o.x[j]) < INFINITY);
-  for (int r = TID; r < nc; r += NT) nonfinite |= !(__builtin_fabs(o.y[r]) < INFINITY);
-  nonfinite = __syncthreads_or(nonfinite);
-  PROF_END(PH_QP, pt_qp);
-  return (nonfinite || status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE ||
-          status == OSQP_DUAL_INFEASIBLE_INACCURATE || status == OSQP_NAN_DATA) ? 1 : 0;
-}
+};
 __device__ int dev_qp_osqp_xl(const Ctx& c) {
-  if (dg_prob.gd_global) return dev_qp_osqp_xl_t<cgptr>(c, c.ws + dg_prob.ws_gd);
-  return dev_qp_osqp_xl_t<clptr>(c, LP(dg_prob.L.gd));
+  if (dg_prob.gd_global) return dev_qp_osqp_t<OxLayout<cgptr>>(c);
+  return dev_qp_osqp_t<OxLayout<clptr>>(c);
 }

@@ -1,12 +1,16 @@
 """The dynamic-bicycle rollout split into a velocity chain and a pose chain on two wavefronts (csrc/dgsqp_eval.h:
-dev_rollout_dyn_split), on a real MI355X.
+dev_rollout_dyn), on a real MI355X.
 
 (a) parity of ``evaluate_batch`` with the oracle at the 1e-12 bar of tests/test_gpu.py::test_evaluate_parity, at points where
     the chains leave their fast paths: slip angles beyond atan(7/16), heading errors beyond 0.78 rad, a step across a track-segment
     boundary, a step across the lap seam (the test asserts that the inputs do that), for rk4, rk3 and rk2;
 (b) the hand-off between the two wavefronts is deterministic: repeated evaluations and repeated solves are bit-identical;
 (c) the fused pass, the multi-trajectory line-search rollouts and the plain rollout agree: the trajectory a solve returns is
-    ``evaluate_batch``'s at the returned inputs, to the bit."""
+    ``evaluate_batch``'s at the returned inputs, to the bit;
+(d) the same three at a short horizon (N = 4), where the hand-off ring is deeper than the whole rollout of a stage.
+
+Not covered here: the single-wavefront mode of dev_rollout_dyn (DYN_BOTH), taken when dyn_ring_setup finds no room for one evaluation
+of every lane pair.  No game this package builds reaches it -- see the docstring of test_short_horizon_dynamic_game."""
 import numpy as np
 import pytest
 
@@ -118,4 +122,50 @@ def test_solve_trajectory_is_the_evaluated_one():
     assert ok.sum() >= 32
     ev = s.evaluate_batch(x0[ok], res['u'][ok])
     xs = np.ascontiguousarray(res['x'][ok]).reshape(ev['x'].shape)
+    assert np.array_equal(xs.view(np.int64), ev['x'].view(np.int64)), np.abs(xs - ev['x']).max()
+
+
+@pytest.mark.parametrize('method', ['rk4', 'rk3'])
+def test_short_horizon_dynamic_game(oracle, method):
+    """dynamic_racing_game at N = 4, rk4 and rk3: (a) evaluate_batch against the oracle at 1e-12, repeated solves bit-identical, (c) the
+    trajectory a solve returns is evaluate_batch's at the returned inputs, to the bit.
+
+    This game was meant to drive the line search's blocks of K concurrent trial trajectories into the single-wavefront mode of
+    dev_rollout_dyn (DYN_BOTH: dyn_ring_setup's depth (N + 1) nq / (3 K M) < 1 needs K >= 14 at N = 4, M = 2).  It does NOT: the
+    layout (dgsqp_layout.h, ls_spec) only grants K > 0 where the QP scratch reaches beyond the evaluation arrays by whole trajectories,
+    and a host-side print of ls_spec gives 0 for every two-car dynamic game at N = 1 .. 5 (rk4, rk3, v2 parameters, the 'curve'
+    definition; active-set and OSQP QP) -- 15 at N = 25, 16 at N = 15.  With K = 0 every trial is a single-trajectory rollout
+    (depth 13): the split modes, as are the fused passes of the solve and of evaluate_batch.  So every part of this test runs the
+    split modes at a short horizon, (c) compares split with split, and DYN_BOTH has no coverage in the suite."""
+    from dgsqp_amd.montecarlo import sample_scenarios
+    from dgsqp_amd.solver import DGSQP, build_problem
+    g = _dyn_game(method, 4, 4)
+    P = build_problem(*g.solver_args())
+    x0, u_tm = sample_scenarios(g, 64, seed=34)
+    u = agent_major(u_tm)
+    # (a) evaluate_batch against the oracle
+    s = DGSQP(*g.solver_args(), print_method=None, lsqr_tol=1e-13)
+    rng = np.random.default_rng(2)
+    l = np.maximum(0, rng.standard_normal((4, s.n_c_total)))
+    ev = s.evaluate_batch(x0[:4], u[:4], l)
+    for b in range(4):
+        ref = oracle.evaluate(P, x0[b], u[b], l[b], 1)
+        for key in ('x', 'q', 'g', 'G', 'Q'):
+            err = rel(ev[key][b], ref[key])
+            print(method, 'scenario', b, key, f'{err:.2e}')
+            assert err < 1e-12, (key, b, err)
+    # repeated solves are bit-identical
+    s = DGSQP(*g.solver_args(), print_method=None)
+    r1, r2 = s.solve_batch(x0, u_tm), s.solve_batch(x0, u_tm)
+    for key in ('status', 'num_iters', 'qp_solves'):
+        assert np.array_equal(r1[key], r2[key]), key
+    for key in ('u', 'l', 'x'):
+        assert np.array_equal(r1[key].view(np.int64), r2[key].view(np.int64)), key
+    # (c) the returned trajectory is evaluate_batch's at the returned inputs
+    ok = (r1['status'] <= 1) & np.isfinite(r1['u']).all(axis=1)
+    print(method, 'converged', int(ok.sum()), 'of', len(ok), 'iterations', r1['num_iters'][ok].min(), '..', r1['num_iters'][ok].max())
+    assert ok.sum() >= 32
+    assert r1['num_iters'][ok].max() >= 1
+    ev = s.evaluate_batch(x0[ok], r1['u'][ok])
+    xs = np.ascontiguousarray(r1['x'][ok]).reshape(ev['x'].shape)
     assert np.array_equal(xs.view(np.int64), ev['x'].view(np.int64)), np.abs(xs - ev['x']).max()
