@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import agent_major, assert_control_flow_parity, stable_mask, tight_lsqr
+import multistage_kat
 
 pytestmark = pytest.mark.gpu
 GOLD = pathlib.Path(__file__).parent / 'golden'
@@ -859,6 +860,27 @@ def test_one_stage_game_hessian_from_sympy_tensors(kind, method):
         assert np.abs(ev['Q'][b] - want).max() < 1e-11 * np.abs(want).max(), (kind, method, b)
         x1 = np.concatenate([kat[f'{method}_fd'][k1], kat[f'{method}_fd'][k2]])
         np.testing.assert_allclose(ev['x'][b].reshape(2, -1)[1], x1, rtol=1e-13, atol=1e-14)
+
+
+@pytest.mark.parametrize('case', multistage_kat.CASES)
+def test_multistage_game_against_high_precision_derivatives(case):
+    """x, g, q, G, Q of dgsqp_evaluate_batch on MULTI-STAGE games against an exact answer that shares nothing with oracle/ or csrc/: the
+    rollout, the costs and the rows as plain 60-digit functions of the input sequence, differenced (tools/make_multistage_kats.py ->
+    tests/golden/multistage_<case>.npz; Q is row block a of d2/du2 [J^a + l . C], DGSQP.py:937-941).  1e-11 relative to the largest
+    entry of each array or 64 x the fixture's own sensitivity, x at rtol 1e-13; the n = 120 / 150 cases (big and XL layout) through
+    G v and Q v.  No oracle in this test; one solver and one evaluate_batch per case.  Measured maxima: DESIGN.md section 2 item 1."""
+    from dgsqp_amd.solver import DGSQP
+    kat, g, P = multistage_kat.load(case)
+    if case in multistage_kat.DIRECTIONAL_CASES:
+        multistage_kat.assert_layout(case, g, P)
+    s = DGSQP(*g.solver_args(), print_method=None)
+    assert (s.n, s.n_c_total) == (kat['u'].shape[1], kat['l'].shape[1])
+    ev = s.evaluate_batch(kat['x0'], kat['u'], kat['l'])
+    worst = {}
+    for b in range(len(kat['x0'])):
+        for k, e in multistage_kat.compare(kat, b, {key: ev[key][b] for key in ('x', 'g', 'q', 'G', 'Q')}, multistage_kat.DEVICE_BAR, f'{case} device').items():
+            worst[k] = max(worst.get(k, 0.0), e)
+    print(f'{case}: device vs fixture, maxima ' + ', '.join(f'{k} {e:.2e}' for k, e in worst.items()))
 
 
 def _plant_rk4(model, q, u, substeps=10):

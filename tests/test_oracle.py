@@ -9,6 +9,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
 from conftest import agent_major, tight_lsqr
+import multistage_kat
 
 GOLD = pathlib.Path(__file__).parent / 'golden'
 
@@ -567,6 +568,50 @@ def test_one_stage_game_hessian_from_sympy_tensors(oracle, kind, method):
         want = sympy_one_stage_Q(kat, method, k1, k2, 0.7, nqa, s_idx)
         assert np.abs(ev['Q'] - want).max() < 1e-12 * np.abs(want).max(), (kind, method, k1, k2)
         np.testing.assert_allclose(ev['x'].reshape(2, -1)[1], np.concatenate([kat[f'{method}_fd'][k1], kat[f'{method}_fd'][k2]]), rtol=1e-13, atol=1e-14)
+
+
+@pytest.mark.parametrize('case', multistage_kat.CASES)
+def test_multistage_game_against_high_precision_derivatives(oracle, case):
+    """x, g, q, G, Q of a MULTI-STAGE game against an exact answer that shares nothing with oracle/ or csrc/: the rollout, the costs and
+    the rows as plain 60-digit functions of the input sequence, differenced (tools/make_multistage_kats.py -> tests/golden/
+    multistage_<case>.npz; Q is row block a of d2/du2 [J^a + l . C], DGSQP.py:937-941).  The oracle's DP (hessian=1) and the literal
+    per-row DP of DGSQP.py:829-877 (hessian=2), 1e-12 relative to the largest entry of each array or 64 x the fixture's own
+    sensitivity; the two n = 120 / 150 cases through G v and Q v.  Measured maxima: DESIGN.md section 2 item 1."""
+    kat, g, P = multistage_kat.load(case)
+    if case in multistage_kat.DIRECTIONAL_CASES:
+        multistage_kat.assert_layout(case, g, P)
+    worst = {}
+    for b in range(len(kat['x0'])):
+        for hessian in (1, 2):
+            ev = oracle.evaluate(P, kat['x0'][b], kat['u'][b], kat['l'][b], hessian)
+            for k, e in multistage_kat.compare(kat, b, ev, multistage_kat.ORACLE_BAR, f'{case} oracle hessian={hessian}').items():
+                worst[k] = max(worst.get(k, 0.0), e)
+    print(f'{case}: oracle vs fixture, maxima ' + ', '.join(f'{k} {e:.2e}' for k, e in worst.items()))
+    if 'Q' in kat.files and not case.startswith(('uni', 'dyn', 'kin2_rk4')):      # (atan competition term: no potential game)
+        assert np.abs(kat['Q'] - kat['Q'].transpose(0, 2, 1)).max() > 1e-3
+
+
+@pytest.mark.parametrize('kind,method', [('kin', 'euler'), ('kin', 'rk4'), ('dyn', 'euler'), ('dyn', 'rk4')])
+def test_multistage_generator_reproduces_the_sympy_pin(kind, method):
+    """The generator of the multi-stage known answers (tools/make_multistage_kats.py), run with N = 1 on the games of
+    conftest.sympy_one_stage_game: its differenced Q against the closed formula in sympy's exact tensors to 1e-13, its rollout against
+    sympy's f_d to 1e-14 -- the tie of the new generator to the one independent pin there was."""
+    import importlib.util
+    from conftest import sympy_one_stage_Q
+    spec = importlib.util.spec_from_file_location('make_multistage_kats', pathlib.Path(__file__).resolve().parent.parent / 'tools' / 'make_multistage_kats.py')
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    kat = np.load(GOLD / f'sympy_fd_{kind}.npz')
+    nqa = gen.NQ[kind]
+    for k1, k2 in ((0, 1), (2, 3), (3, 0)):
+        out = gen.one_stage_answers(kind, method, kat, k1, k2, 0.7)
+        want = sympy_one_stage_Q(kat, method, k1, k2, 0.7, nqa, gen.S_IDX[kind])
+        err = np.abs(out['Q'] - want).max() / np.abs(want).max()
+        x1 = np.concatenate([kat[f'{method}_fd'][k1], kat[f'{method}_fd'][k2]])
+        errx = np.abs(out['x'][1] - x1).max() / np.abs(x1).max()
+        print(kind, method, k1, k2, f'Q {err:.2e} x_1 {errx:.2e}')
+        assert err < 1e-13, (kind, method, k1, k2, err)
+        assert errx < 1e-14, (kind, method, k1, k2, errx)
 
 
 @pytest.mark.parametrize('name', ['kb_barc3_N25', 'kb_f1_N50'])
