@@ -233,6 +233,8 @@ __device__ inline double wave_sum(double v) {
   v += dpp_f64<0x140>(v);  // row_mirror: every lane now holds the sum of its 16-lane row
   return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
 }
+// NaN contract (pinned in tests/test_device_math.py): fmax returns its other operand when one is NaN, so wave_max / block_max IGNORE a
+// NaN lane (all lanes NaN: NaN), while wave_sum / block_sum propagate it.  The convergence norms use both.
 __device__ inline double wave_max(double v) {
   v = fmax(v, dpp_f64<0xB1>(v));
   v = fmax(v, dpp_f64<0x4E>(v));
@@ -289,7 +291,10 @@ __device__ inline void block_argmin(double v, int idx, lptr red, double& vout, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// Lean fp64 elementary functions (<= 1 ulp on the arguments that occur here: angles and slip ratios, |x| < 2^20).
+// Lean fp64 elementary functions for the arguments that occur here: angles and slip ratios, |x| < 2^20.  Accuracy against 60-digit
+// references (tests/test_device_math.py), in ulp of the exact value: caps fast_rcp 1, atan 1, sin / cos 2,
+// atan2 2.5 (roll_atan2 2), tan 4 (the maxima of the algorithms as written, evaluated with exact fma, rounded up).
+// Within ~|k| 1e-33 of x = k pi / 2 the two-term reduction's error is absolute (<= 2^-52 up to |k| = 2e6), not a number of ulp of the tiny result.
 // The OCML versions carry large-argument reduction and full IEEE division (sincos ~200, atan2 ~125, tan ~220 ISA
 // instructions); f_c is evaluated ~10^3 times per rollout on a handful of lanes, so the instruction count of these
 // is the latency of the whole rollout.  Kernels are the classical fdlibm minimax polynomials.
@@ -368,8 +373,12 @@ __device__ inline double dev_atan2(double y, double x) {
   const double kk = 0.5 * (double)(big ? 0 : rid);
   const double num = big ? -ax : __builtin_fma(-kk, ax, ay);
   double den = big ? ay : __builtin_fma(kk, ay, ax);
-  den = den == 0.0 ? 1.0 : den;                 // atan2(0, 0) = 0
+  const bool origin = den == 0.0;               // only at ax == ay == 0 (there every threshold test holds: rid == 4, hi = pi/2)
+  den = origin ? 1.0 : den;
   double r = atan_poly_tail(num * fast_rcp(den), hi, lo);
+  r = origin ? 0.0 : r;                         // atan2(+-0, +-0) = 0 for x >= 0, as std::atan2 and CasADi (x = -0.0 included)
+  // atan2(-0.0, x < 0) returns +pi where IEEE 754 gives -pi (y < 0.0 is false for -0.0): pinned in tests/test_device_math.py, no game
+  // can tell (the slip angles and tangent angles built on this never sit on the negative x axis)
   r = x < 0.0 ? (3.141592653589793 - r) + 1.2246467991473532e-16 : r;
   return y < 0.0 ? -r : r;
 }

@@ -139,8 +139,10 @@ __device__ inline double roll_atan2(double y, double x) {
   const double kk = 0.5 * (double)(big ? 0 : rid);
   const double num = big ? -ax : __builtin_fma(-kk, ax, ay);
   double den = big ? ay : __builtin_fma(kk, ay, ax);
-  den = den == 0.0 ? 1.0 : den;
+  const bool origin = den == 0.0;               // ax == ay == 0, as in dev_atan2 (never on the fast path above: x > 0 fails)
+  den = origin ? 1.0 : den;
   double r = roll_atan_core(num, fast_rcp(den), hi, lo);
+  r = origin ? 0.0 : r;
   r = x < 0.0 ? (3.141592653589793 - r) + 1.2246467991473532e-16 : r;
   return y < 0.0 ? -r : r;
 }

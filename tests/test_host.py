@@ -199,6 +199,27 @@ def test_product_never_imports_the_oracle():
                 assert pat not in txt, (f, pat)
 
 
+def test_product_never_loads_the_math_probe():
+    """tests/csrc/device_math_probe.hip and its library are test infrastructure: nothing under dgsqp_amd/ names them; and the helper's
+    table of ops is the probe's (op order, planes in, planes out)."""
+    import re
+    for f in (ROOT / 'dgsqp_amd').rglob('*'):
+        if f.suffix in ('.py', '.h', '.hip'):
+            txt = f.read_text()
+            for pat in ('math_probe', 'dgsqp_probe', 'tests/csrc'):
+                assert pat not in txt, (f, pat)
+    import device_math_probe as dmp
+    src = (ROOT / 'tests' / 'csrc' / 'device_math_probe.hip').read_text()
+    names = [n.strip().split('=')[0].strip() for n in re.search(r'enum \{(.*?)PR_COUNT', src, re.S).group(1).split(',') if n.strip()]
+    nin = [int(v) for v in re.search(r'pr_nin\[PR_COUNT\] = \{(.*?)\}', src).group(1).split(',')]
+    nout = [int(v) for v in re.search(r'pr_nout\[PR_COUNT\] = \{(.*?)\}', src).group(1).split(',')]
+    assert len(names) == len(nin) == len(nout) == len(dmp.OPS)
+    alias = {'sincos': 'PR_SINCOS', 'tan': 'PR_TAN', 'atan': 'PR_ATAN', 'atan2': 'PR_ATAN2', 'rcp': 'PR_RCP'}
+    for op, (code, a, b) in dmp.OPS.items():
+        assert names[code] == alias.get(op, 'PR_' + op.upper()), (op, names[code])
+        assert (nin[code], nout[code]) == (a, b), op
+
+
 def test_shard_ranges_partition_the_batch():
     from dgsqp_amd.sharding import shard_range
     for B in (0, 1, 7, 1024, 1025):

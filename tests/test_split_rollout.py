@@ -9,8 +9,11 @@ dev_rollout_dyn), on a real MI355X.
     ``evaluate_batch``'s at the returned inputs, to the bit;
 (d) the same three at a short horizon (N = 4), where the hand-off ring is deeper than the whole rollout of a stage.
 
-Not covered here: the single-wavefront mode of dev_rollout_dyn (DYN_BOTH), taken when dyn_ring_setup finds no room for one evaluation
-of every lane pair.  No game this package builds reaches it -- see the docstring of test_short_horizon_dynamic_game."""
+(e) slip angles that are exactly zero: atan2(0, vx) in the rollout's and the Taylor pass's tyre chains.
+
+The single-wavefront mode of dev_rollout_dyn (DYN_BOTH), taken when dyn_ring_setup finds no room for one evaluation of every lane
+pair, is reached by no game this package builds (see the docstring of test_short_horizon_dynamic_game); it is run directly and
+compared bit for bit with the split modes in tests/test_device_math.py::test_single_wavefront_rollout_is_the_split_one."""
 import numpy as np
 import pytest
 
@@ -136,7 +139,8 @@ def test_short_horizon_dynamic_game(oracle, method):
     and a host-side print of ls_spec gives 0 for every two-car dynamic game at N = 1 .. 5 (rk4, rk3, v2 parameters, the 'curve'
     definition; active-set and OSQP QP) -- 15 at N = 25, 16 at N = 15.  With K = 0 every trial is a single-trajectory rollout
     (depth 13): the split modes, as are the fused passes of the solve and of evaluate_batch.  So every part of this test runs the
-    split modes at a short horizon, (c) compares split with split, and DYN_BOTH has no coverage in the suite."""
+    split modes at a short horizon and (c) compares split with split; DYN_BOTH is covered by
+    tests/test_device_math.py::test_single_wavefront_rollout_is_the_split_one, which calls it through the probe library."""
     from dgsqp_amd.montecarlo import sample_scenarios
     from dgsqp_amd.solver import DGSQP, build_problem
     g = _dyn_game(method, 4, 4)
@@ -169,3 +173,36 @@ def test_short_horizon_dynamic_game(oracle, method):
     ev = s.evaluate_batch(x0[ok], r1['u'][ok])
     xs = np.ascontiguousarray(r1['x'][ok]).reshape(ev['x'].shape)
     assert np.array_equal(xs.view(np.int64), ev['x'].view(np.int64)), np.abs(xs - ev['x']).max()
+
+
+def test_zero_slip_angles(oracle):
+    """atan2(0, vx): dynamic_racing_game at N = 4, rk4 with 4 substeps, evaluate_batch against the oracle at 1e-12.
+    Scenario 0: car 1 is exactly at rest laterally (vy = w = 0, vx > 0) and never steers, so both of its slip angles are atan2(0, vx)
+    at every f_c evaluation of the horizon (vx = 0 itself is not admissible: the Taylor pass divides by vx).  Scenario 1: car 1 starts with
+    vy + w L_f = 0 exactly (front slip angle atan2(0, vx) at the first evaluation) at vx = 2, the sampler's lowest speed."""
+    from dgsqp_amd.montecarlo import sample_scenarios
+    from dgsqp_amd.solver import DGSQP, build_problem
+    N = 4
+    g = _dyn_game('rk4', N, 4)
+    P = build_problem(*g.solver_args())
+    s = DGSQP(*g.solver_args(), print_method=None, lsqr_tol=1e-13)
+    x0, u_tm = sample_scenarios(g, 2, seed=35)
+    u = agent_major(u_tm)
+    x0 = x0.copy()
+    assert x0[0, 2] > 0 and x0[0, 3] == 0 and x0[0, 4] == 0
+    u[0, 1:2 * N:2] = 0.0                          # steering of car 1, every stage
+    L_f = P.agents[0].L_f
+    x0[1, 2], x0[1, 3], x0[1, 4] = 2.0, -0.5 * L_f, 0.5
+    assert x0[1, 3] + x0[1, 4] * L_f == 0.0 and 0.5 * L_f == float(np.float64(0.5) * np.float64(L_f))
+    u[1, 1] = 0.0                                  # no steering in the first stage: the front wheel frame is the body frame there
+    rng = np.random.default_rng(3)
+    l = np.maximum(0, rng.standard_normal((2, s.n_c_total)))
+    ev = s.evaluate_batch(x0, u, l)
+    ref = [oracle.evaluate(P, x0[b], u[b], l[b], 1) for b in range(2)]
+    xr = np.asarray(ref[0]['x']).reshape(N + 1, 2, 8)
+    assert (xr[:, 0, 3] == 0).all() and (xr[:, 0, 4] == 0).all() and (xr[:, 0, 2] > 0).all()
+    for b in range(2):
+        for key in ('x', 'q', 'g', 'G', 'Q'):
+            err = rel(ev[key][b], ref[b][key])
+            print('zero slip angle, scenario', b, key, f'{err:.2e}')
+            assert err < 1e-12, (key, b, err)
