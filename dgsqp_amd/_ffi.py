@@ -16,6 +16,7 @@ MAX_LANES = 2
 NUA = 2
 
 STATUS_MSG = ['conv_abs_tol', 'conv_rel_tol', 'max_it', 'diverged', 'qp_fail', 'time_limit']
+NOT_RUN = -1         # DGSQP_NOT_RUN: a closed-loop step that never ran (step_batch reports it as 'not_run')
 
 dbl2 = C.c_double * NUA
 
@@ -164,6 +165,8 @@ def load_library(workgroups_per_cu: int = 1) -> C.CDLL:
     lib.dgsqp_set_iterate_log.restype = C.c_int
     lib.dgsqp_fetch_iterate_log.argtypes = [H, _PD, C.c_int64]
     lib.dgsqp_fetch_iterate_log.restype = C.c_int
+    lib.dgsqp_closed_loop_batch.argtypes = [H, C.c_int64, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, C.POINTER(TimingT)]
+    lib.dgsqp_closed_loop_batch.restype = C.c_int
     _PF = C.POINTER(C.c_float)
     lib.dgsqp_solve_batch_f32.argtypes = [H, C.c_int64, _PF, _PF, _PF, _PF, _PF, _PI, _PI, _PI, _PF, _PF, C.POINTER(TimingT)]
     lib.dgsqp_solve_batch_f32.restype = C.c_int
@@ -213,7 +216,8 @@ EXPORTED_SYMBOLS = ['dgsqp_create', 'dgsqp_destroy', 'dgsqp_dims', 'dgsqp_plan',
                     'dgsqp_pid_warm_start_batch', 'dgsqp_launch_staged', 'dgsqp_wait', 'dgsqp_draining',
                     'dgsqp_set_iterate_log', 'dgsqp_fetch_iterate_log', 'dgsqp_synchronize', 'dgsqp_finished', 'dgsqp_launch_staged_group', 'dgsqp_solve_batch_f32', 'dgsqp_comm_unique_id', 'dgsqp_comm_init',
                     'dgsqp_comm_destroy', 'dgsqp_gather_stats', 'dgsqp_comm_barrier', 'dgsqp_comm_allreduce_max',
-                    'dgsqp_set_cooperative', 'dgsqp_coop_stats', 'dgsqp_osqp_counters', 'dgsqp_sample_batch', 'dgsqp_set_deferral', 'dgsqp_reserve_deferral', 'dgsqp_deferral_stats', 'dgsqp_deferral_log']
+                    'dgsqp_set_cooperative', 'dgsqp_coop_stats', 'dgsqp_osqp_counters', 'dgsqp_sample_batch', 'dgsqp_set_deferral', 'dgsqp_reserve_deferral', 'dgsqp_deferral_stats', 'dgsqp_deferral_log',
+                    'dgsqp_closed_loop_batch']
 
 
 def dptr(a):

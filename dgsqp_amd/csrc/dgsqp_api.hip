@@ -119,6 +119,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 #endif
 }
 
+#include "dgsqp_closed_loop.h"
 #include "dgsqp_pid.h"
 #include "dgsqp_sampler.h"
 
@@ -241,6 +242,10 @@ struct dgsqp_solver {
   double defer_factor = 2.0;
   bool defer_requested = false;       // dgsqp_set_deferral was called (DG-SQP v2 is only deferred on request)
   dgsqp_comm_state* comm = nullptr;   // RCCL communicator + record buffers (dgsqp_comm.h), owned by the handle
+  // closed-loop launches (dgsqp_closed_loop_batch): step-major device arrays, grown on demand, freed in dgsqp_destroy
+  enum { CL_Q, CL_UWS, CL_W, CL_U, CL_L, CL_X, CL_COND, CL_COST, CL_STATUS, CL_ITERS, CL_QPS, CL_DONE, CL_COUNT };
+  void* cl_buf[CL_COUNT] = {};
+  size_t cl_bytes[CL_COUNT] = {};
   std::string err;
 };
 static thread_local std::string g_create_err;
@@ -502,7 +507,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   h->coop_bytes = sizeof(DgCoop) + sizeof(DgCoopJob) * 2 * (size_t)(h->num_cu * 2 + 2);
   if (hipMalloc((void**)&h->d_coop, h->coop_bytes) != hipSuccess) return fail("hipMalloc(coop) failed");
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
-  const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel};
+  const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -527,6 +532,7 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->comm) (void)dgsqp_comm_destroy(h);
   { std::lock_guard<std::mutex> lk(g_reg_mutex); g_handles.erase(std::remove(g_handles.begin(), g_handles.end(), h), g_handles.end()); }
   free_batch(h);
+  for (void* p : h->cl_buf) if (p) (void)hipFree(p);
   if (h->ws) (void)hipFree(h->ws);
   if (h->dp) (void)hipFree(h->dp);
   if (h->ticket) (void)hipFree(h->ticket);
@@ -854,6 +860,104 @@ int dgsqp_solve_batch(dgsqp_handle_t h, int64_t B, const double* x0, const doubl
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
     *tm = t2;
     tm->total_ms = ms;
+  }
+  return DGSQP_OK;
+}
+
+// Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h).
+static int cl_reserve(dgsqp_solver* h, int which, size_t bytes) {
+  if (bytes <= h->cl_bytes[which]) return DGSQP_OK;
+  if (h->cl_buf[which]) (void)hipFree(h->cl_buf[which]);
+  h->cl_buf[which] = nullptr; h->cl_bytes[which] = 0;
+  HIPCHK(h, hipMalloc(&h->cl_buf[which], bytes));
+  h->cl_bytes[which] = bytes;
+  return DGSQP_OK;
+}
+
+int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
+                            double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
+                            int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
+  if (!h) return DGSQP_E_ARG;
+  if (T < 1) { h->err = "closed loop: T must be at least 1"; return DGSQP_E_ARG; }
+  if (B < 0) { h->err = "closed loop: B must not be negative"; return DGSQP_E_ARG; }
+  if (tm) memset(tm, 0, sizeof(*tm));
+  if (B == 0) return DGSQP_OK;
+  if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
+    h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  const DgProb& D = h->hp;
+  const size_t TB = (size_t)T * (size_t)B, dbl = sizeof(double), i32 = sizeof(int32_t);
+  const size_t nx = (size_t)(D.N + 1) * D.nq;
+  const size_t by_q = (TB + B) * D.nq * dbl, by_uws = (TB + B) * D.n * dbl, by_w = TB * D.nq * dbl, by_u = TB * D.n * dbl, by_l = TB * D.nc * dbl;
+  const size_t by_x = (x_out ? TB : (size_t)B) * nx * dbl, by_cond = TB * 3 * dbl, by_cost = TB * D.M * dbl;
+  const size_t want[dgsqp_solver::CL_COUNT] = {by_q, by_uws, w ? by_w : 0, by_u, l_out ? by_l : 0, by_x, by_cond, by_cost, TB * i32, TB * i32, TB * i32, (size_t)B * i32};
+  for (int i = 0; i < dgsqp_solver::CL_COUNT; i++) { const int rc = cl_reserve(h, i, want[i]); if (rc) return rc; }
+  const int grid = grid_for(h, B);
+  { const int rc = ensure_ws(h, (size_t)grid); if (rc) return rc; }
+  double* d_q = (double*)h->cl_buf[dgsqp_solver::CL_Q]; double* d_uws = (double*)h->cl_buf[dgsqp_solver::CL_UWS];
+  double* d_w = w ? (double*)h->cl_buf[dgsqp_solver::CL_W] : nullptr;
+  double* d_u = (double*)h->cl_buf[dgsqp_solver::CL_U]; double* d_l = l_out ? (double*)h->cl_buf[dgsqp_solver::CL_L] : nullptr;
+  double* d_x = (double*)h->cl_buf[dgsqp_solver::CL_X]; double* d_cond = (double*)h->cl_buf[dgsqp_solver::CL_COND]; double* d_cost = (double*)h->cl_buf[dgsqp_solver::CL_COST];
+  int32_t* d_status = (int32_t*)h->cl_buf[dgsqp_solver::CL_STATUS]; int32_t* d_iters = (int32_t*)h->cl_buf[dgsqp_solver::CL_ITERS];
+  int32_t* d_qps = (int32_t*)h->cl_buf[dgsqp_solver::CL_QPS]; int32_t* d_done = (int32_t*)h->cl_buf[dgsqp_solver::CL_DONE];
+  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+  // What a step that never runs leaves behind: every byte 0xff is NaN in a double and DGSQP_NOT_RUN (-1) in a status; zero counts.
+  // The kernel writes each slice it reaches once, on top of this.
+  HIPCHK(h, hipMemsetAsync(d_q + (size_t)B * D.nq, 0xff, by_q - (size_t)B * D.nq * dbl, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_uws + (size_t)B * D.n, 0xff, by_uws - (size_t)B * D.n * dbl, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_u, 0xff, by_u, h->stream));
+  if (d_l) HIPCHK(h, hipMemsetAsync(d_l, 0xff, by_l, h->stream));
+  if (x_out) HIPCHK(h, hipMemsetAsync(d_x, 0xff, by_x, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_cond, 0xff, by_cond, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_cost, 0xff, by_cost, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_status, 0xff, TB * i32, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_iters, 0, TB * i32, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_qps, 0, TB * i32, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_done, 0, (size_t)B * i32, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_q, x0, (size_t)B * D.nq * dbl, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_uws, u_ws, (size_t)B * D.n * dbl, hipMemcpyHostToDevice, h->stream));
+  if (d_w) HIPCHK(h, hipMemcpyAsync(d_w, w, by_w, hipMemcpyHostToDevice, h->stream));
+  DgClosedLoop cl;
+  cl.T = T; cl.q = d_q; cl.uws = d_uws; cl.w = d_w;
+  cl.O = SolveOutPtrs{d_u, d_l, d_x, d_cond, d_cost, d_status, d_iters, d_qps};
+  cl.x_step = x_out ? (int64_t)B * (int64_t)nx : 0;
+  cl.steps_done = d_done;
+  {
+    std::unique_lock<std::mutex> game_lock(g_reg_mutex);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
+    release_members(h);        // (as in dgsqp_launch_staged: ev[0] / ev[1] are about to be reused)
+    { const int rcu = upload_problem(h); if (rcu) return rcu; }
+    HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    hipLaunchKernelGGL(dg_closed_loop_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
+    HIPCHK(h, hipGetLastError());
+    h->in_flight = true;       // (a launch of another game waits for this kernel before it replaces the constants)
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->in_flight = false;
+  HIPCHK(h, hipMemcpyAsync(q_out, d_q, by_q, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(u_ws_out, d_uws, by_uws, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(u_out, d_u, by_u, hipMemcpyDeviceToHost, h->stream));
+  if (l_out) HIPCHK(h, hipMemcpyAsync(l_out, d_l, by_l, hipMemcpyDeviceToHost, h->stream));
+  if (x_out) HIPCHK(h, hipMemcpyAsync(x_out, d_x, by_x, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(status, d_status, TB * i32, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(iters, d_iters, TB * i32, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(qp_solves, d_qps, TB * i32, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(cond, d_cond, by_cond, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(cost, d_cost, by_cost, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(steps_done, d_done, (size_t)B * i32, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (tm) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    tm->kernel_ms = ms;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    tm->total_ms = ms;
+    tm->grid = grid; tm->block = DG_BLOCK;
   }
   return DGSQP_OK;
 }

@@ -479,6 +479,63 @@ class DGSQP(AbstractSolver):
         out['u_pred'] = self._to_time_major(out['u'])
         return out
 
+    def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
+                   keep_predictions: bool = False) -> dict:
+        """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
+        one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
+        ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
+        plus this.  The feedback rule is ``dgsqp_amd.closed_loop.feedback``; every step is, bit for bit, the solve ``solve_batch``
+        performs from the same (state, warm start).  A chain whose next state is not finite ends there (``steps_done``; ``q`` keeps that
+        state); the steps it never ran report status -1 / 'not_run', zero counts and NaN, their ``q`` / ``u_ws`` slices included.  Event log, iterate log, cooperative line search and deferral do
+        not apply to closed-loop launches.
+
+        Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
+        the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
+        steps_done [B], time, kernel_ms; with ``keep_predictions`` also x [B, T, N+1, n_q] and l [B, T, n_c]."""
+        T = int(steps)
+        if T < 1:
+            raise ValueError(f'steps must be at least 1, got {steps}')
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B = x0.shape[0]
+        u_ws = np.asarray(u_ws, dtype=np.float64)
+        if u_ws.ndim == 3:
+            if u_ws.shape[1:] != (self.N, self.n_u):
+                raise RuntimeError('Warm start state sequence of shape (%i,%i) is incompatible with required shape (%i,%i)'
+                                   % (u_ws.shape[1], u_ws.shape[2], self.N, self.n_u))
+            u_ws = self._to_agent_major(u_ws)
+        u_ws = np.ascontiguousarray(u_ws)
+        if x0.shape != (B, self.n_q) or u_ws.shape != (B, self.n):
+            raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
+        w = None
+        if disturbance is not None:
+            w = np.asarray(disturbance, dtype=np.float64)
+            if w.shape != (B, T, self.n_q):
+                raise ValueError(f'disturbance must be [B, steps, n_q] = {(B, T, self.n_q)}, got {w.shape}')
+            w = np.ascontiguousarray(w.transpose(1, 0, 2))          # the library's arrays are step-major
+        nc = self.n_c_total
+        sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), u=np.empty((T, B, self.n)),
+                  l=np.empty((T, B, nc)) if keep_predictions else None, x=np.empty((T, B, self.N + 1, self.n_q)) if keep_predictions else None,
+                  status=np.empty((T, B), np.int32), num_iters=np.empty((T, B), np.int32), qp_solves=np.empty((T, B), np.int32),
+                  cond=np.empty((T, B, 3)), cost=np.empty((T, B, self.M)))
+        steps_done = np.empty(B, np.int32)
+        tm = _ffi.TimingT()
+        t0 = time.time()
+        rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
+                                               _ffi.dptr(sm['u']), _ffi.dptr(sm['l']), _ffi.dptr(sm['x']), _ffi.iptr(sm['status']),
+                                               _ffi.iptr(sm['num_iters']), _ffi.iptr(sm['qp_solves']), _ffi.dptr(sm['cond']), _ffi.dptr(sm['cost']),
+                                               _ffi.iptr(steps_done), C.byref(tm))
+        if rc != 0:
+            raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
+        out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
+        out['steps_done'] = steps_done
+        out['time'] = time.time() - t0
+        out['kernel_ms'] = tm.kernel_ms
+        out['msg'] = [['not_run' if s == _ffi.NOT_RUN else _ffi.STATUS_MSG[s] for s in row] for row in out['status']]
+        out['converged'] = (out['status'] >= 0) & (out['status'] <= 1)
+        out['u_pred'] = self._to_time_major(out['u'])
+        out['u_applied'] = np.ascontiguousarray(out['u_pred'][:, :, 0])
+        return out
+
     def _solve_batch_f32(self, x0, u_ws) -> dict:
         x0 = np.ascontiguousarray(x0, dtype=np.float32)
         B = x0.shape[0]

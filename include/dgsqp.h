@@ -299,6 +299,36 @@ int dgsqp_solve_batch_f32(dgsqp_handle_t h, int64_t B, const float* x0, const fl
                           dgsqp_timing_t* timing);
 
 /*
+ * Closed-loop (receding-horizon) batch: B independent chains of T calls of DGSQP.step() (DGSQP.py:283-297) in ONE launch.  One
+ * workgroup carries one scenario through all T steps, so the launch ends with its longest chain, not T times with its slowest
+ * scenario, and no intermediate state crosses the host.  Step t of scenario b is the very solve dgsqp_solve_batch performs from
+ * (q[t][b], u_ws[t][b]) -- bit for bit --; between steps
+ *   q[t+1][b]    = x_t[b][1] (+ w[t][b])          the plant is the game's own discrete model plus the optional disturbance w
+ *   u_ws[t+1][b] = u_t[b] shifted by one stage per agent, last row repeated; after DGSQP_DIVERGED / DGSQP_QP_FAIL: u_ws[t][b] again
+ * A non-finite q[t+1][b] ends chain b: steps_done[b] = t + 1 (otherwise T) and no solve starts from such a state.  Records of steps
+ * that never ran hold status DGSQP_NOT_RUN, iters = qp_solves = 0 and NaN in every double, their q / u_ws slices included
+ * (q[steps_done[b]][b] keeps the non-finite state that ended the chain; no warm start is written for it).
+ * Arrays are step-major, caller-owned host memory; w, l_out, x_out and timing may be NULL.  The call is synchronous.  Event log,
+ * iterate log, cooperative line search and deferral do not apply to closed-loop launches (a chain's next solve depends on its last
+ * one); their settings are left as they are for the next dgsqp_solve_batch.  T < 1, B < 0 or a NULL required pointer: DGSQP_E_ARG.
+ */
+#define DGSQP_NOT_RUN (-1)
+int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T,
+    const double* x0,      /* [B][n_q] */
+    const double* u_ws,    /* [B][n], agent-major */
+    const double* w,       /* [T][B][n_q] or NULL */
+    double* q_out,         /* [T+1][B][n_q]; slice 0 = x0 */
+    double* u_ws_out,      /* [T+1][B][n]; slice t = the warm start step t started from */
+    double* u_out,         /* [T][B][n] */
+    double* l_out,         /* [T][B][n_c] or NULL */
+    double* x_out,         /* [T][B][N+1][n_q] or NULL */
+    int32_t* status, int32_t* iters, int32_t* qp_solves,   /* [T][B] */
+    double* cond,          /* [T][B][3] */
+    double* cost,          /* [T][B][M] */
+    int32_t* steps_done,   /* [B] */
+    dgsqp_timing_t* timing);
+
+/*
  * Device-resident variant used by bench.py: inputs are staged once with
  * dgsqp_stage_inputs(); dgsqp_solve_staged() runs only the solve kernel on
  * the handle's stream; dgsqp_fetch_results() copies results back.
