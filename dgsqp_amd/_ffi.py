@@ -97,6 +97,56 @@ class TimingT(C.Structure):
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
+_PF = C.POINTER(C.c_float)
+_PU64 = C.POINTER(C.c_uint64)
+_H = C.c_void_p
+_TM = C.POINTER(TimingT)
+
+# The C-ABI of include/dgsqp.h, stated once: name -> (restype, argtypes).  load_library applies it; EXPORTED_SYMBOLS is its key list.
+SIGNATURES = {
+    'dgsqp_create': (C.c_int, [C.POINTER(ProblemT), C.POINTER(ParamsT), C.c_int, C.POINTER(_H)]),
+    'dgsqp_destroy': (None, [_H]),
+    'dgsqp_dims': (C.c_int, [_H, C.POINTER(DimsT)]),
+    'dgsqp_plan': (C.c_int, [C.POINTER(ProblemT), C.POINTER(ParamsT), C.POINTER(DimsT), C.c_char_p, C.c_int]),
+    'dgsqp_last_error': (C.c_char_p, [_H]),
+    'dgsqp_backend_info': (C.c_int, [C.c_char_p, C.c_int]),
+    'dgsqp_solve_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _TM]),
+    'dgsqp_solve_batch_f32': (C.c_int, [_H, C.c_int64, _PF, _PF, _PF, _PF, _PF, _PI, _PI, _PI, _PF, _PF, _TM]),
+    'dgsqp_closed_loop_batch': (C.c_int, [_H, C.c_int64, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, _TM]),
+    'dgsqp_stage_inputs': (C.c_int, [_H, C.c_int64, _PD, _PD]),
+    'dgsqp_solve_staged': (C.c_int, [_H, _TM]),
+    'dgsqp_launch_staged': (C.c_int, [_H]),
+    'dgsqp_launch_staged_group': (C.c_int, [C.POINTER(_H), C.c_int]),
+    'dgsqp_draining': (C.c_int, [_H]),
+    'dgsqp_finished': (C.c_int, [_H]),
+    'dgsqp_wait': (C.c_int, [_H, _TM]),
+    'dgsqp_synchronize': (C.c_int, [_H]),
+    'dgsqp_fetch_results': (C.c_int, [_H, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD]),
+    'dgsqp_evaluate_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD]),
+    'dgsqp_qp_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PI]),
+    'dgsqp_qp_batch_info': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PD]),
+    'dgsqp_pid_warm_start_batch': (C.c_int, [_H, C.c_int64, _PD, C.POINTER(PidT), _PD, _PD, _PI]),
+    'dgsqp_sample_batch': (C.c_int, [_H, C.c_int64, C.c_void_p, C.POINTER(PidT), _PD, _PD, C.POINTER(C.c_int64), C.c_int]),
+    'dgsqp_set_trace': (C.c_int, [_H, C.c_int]),
+    'dgsqp_fetch_trace': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_iterate_log': (C.c_int, [_H, C.c_int]),
+    'dgsqp_fetch_iterate_log': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_cooperative': (C.c_int, [_H, C.c_int]),
+    'dgsqp_coop_stats': (C.c_int, [_H, _PU64]),
+    'dgsqp_osqp_counters': (C.c_int, [_H, _PU64, C.c_int]),
+    'dgsqp_set_deferral': (C.c_int, [_H, C.c_int32, C.c_double]),
+    'dgsqp_reserve_deferral': (C.c_int, [_H, C.c_int64]),
+    'dgsqp_deferral_stats': (C.c_int, [_H, _PU64]),
+    'dgsqp_deferral_log': (C.c_int, [_H, _PU64, C.c_int64]),
+    'dgsqp_comm_unique_id': (C.c_int, [C.c_char_p]),
+    'dgsqp_comm_init': (C.c_int, [_H, C.c_char_p, C.c_int, C.c_int]),
+    'dgsqp_comm_destroy': (C.c_int, [_H]),
+    'dgsqp_gather_stats': (C.c_int, [_H, C.c_int64, C.c_void_p]),
+    'dgsqp_comm_barrier': (C.c_int, [_H]),
+    'dgsqp_comm_allreduce_max': (C.c_int, [_H, _PD, C.c_int]),
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
 _LIB = None
 _LIBS = {}          # workgroups per CU -> CDLL (1: the product build; 2: libdgsqp_hip_b256.so, 256-thread workgroups and half the LDS arena)
 
@@ -122,102 +172,13 @@ def load_library(workgroups_per_cu: int = 1) -> C.CDLL:
         raise RuntimeError(f'HIP solver library {path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            f'(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     lib = C.CDLL(str(path))
-    H = C.c_void_p
-    lib.dgsqp_create.argtypes = [C.POINTER(ProblemT), C.POINTER(ParamsT), C.c_int, C.POINTER(H)]
-    lib.dgsqp_create.restype = C.c_int
-    lib.dgsqp_destroy.argtypes = [H]
-    lib.dgsqp_destroy.restype = None
-    lib.dgsqp_dims.argtypes = [H, C.POINTER(DimsT)]
-    lib.dgsqp_dims.restype = C.c_int
-    lib.dgsqp_plan.argtypes = [C.POINTER(ProblemT), C.POINTER(ParamsT), C.POINTER(DimsT), C.c_char_p, C.c_int]
-    lib.dgsqp_plan.restype = C.c_int
-    lib.dgsqp_last_error.argtypes = [H]
-    lib.dgsqp_last_error.restype = C.c_char_p
-    lib.dgsqp_backend_info.argtypes = [C.c_char_p, C.c_int]
-    lib.dgsqp_backend_info.restype = C.c_int
-    lib.dgsqp_solve_batch.argtypes = [H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, C.POINTER(TimingT)]
-    lib.dgsqp_solve_batch.restype = C.c_int
-    lib.dgsqp_stage_inputs.argtypes = [H, C.c_int64, _PD, _PD]
-    lib.dgsqp_stage_inputs.restype = C.c_int
-    lib.dgsqp_solve_staged.argtypes = [H, C.POINTER(TimingT)]
-    lib.dgsqp_solve_staged.restype = C.c_int
-    lib.dgsqp_launch_staged.argtypes = [H]
-    lib.dgsqp_launch_staged.restype = C.c_int
-    lib.dgsqp_draining.argtypes = [H]
-    lib.dgsqp_draining.restype = C.c_int
-    lib.dgsqp_wait.argtypes = [H, C.POINTER(TimingT)]
-    lib.dgsqp_wait.restype = C.c_int
-    lib.dgsqp_fetch_results.argtypes = [H, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD]
-    lib.dgsqp_fetch_results.restype = C.c_int
-    lib.dgsqp_evaluate_batch.argtypes = [H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD]
-    lib.dgsqp_evaluate_batch.restype = C.c_int
-    lib.dgsqp_qp_batch.argtypes = [H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PI]
-    lib.dgsqp_qp_batch.restype = C.c_int
-    lib.dgsqp_qp_batch_info.argtypes = [H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PD]
-    lib.dgsqp_qp_batch_info.restype = C.c_int
-    lib.dgsqp_pid_warm_start_batch.argtypes = [H, C.c_int64, _PD, C.POINTER(PidT), _PD, _PD, _PI]
-    lib.dgsqp_pid_warm_start_batch.restype = C.c_int
-    lib.dgsqp_set_trace.argtypes = [H, C.c_int]
-    lib.dgsqp_set_trace.restype = C.c_int
-    lib.dgsqp_fetch_trace.argtypes = [H, _PD, C.c_int64]
-    lib.dgsqp_fetch_trace.restype = C.c_int
-    lib.dgsqp_set_iterate_log.argtypes = [H, C.c_int]
-    lib.dgsqp_set_iterate_log.restype = C.c_int
-    lib.dgsqp_fetch_iterate_log.argtypes = [H, _PD, C.c_int64]
-    lib.dgsqp_fetch_iterate_log.restype = C.c_int
-    lib.dgsqp_closed_loop_batch.argtypes = [H, C.c_int64, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, C.POINTER(TimingT)]
-    lib.dgsqp_closed_loop_batch.restype = C.c_int
-    _PF = C.POINTER(C.c_float)
-    lib.dgsqp_solve_batch_f32.argtypes = [H, C.c_int64, _PF, _PF, _PF, _PF, _PF, _PI, _PI, _PI, _PF, _PF, C.POINTER(TimingT)]
-    lib.dgsqp_solve_batch_f32.restype = C.c_int
-    lib.dgsqp_launch_staged_group.argtypes = [C.POINTER(H), C.c_int]
-    lib.dgsqp_launch_staged_group.restype = C.c_int
-    lib.dgsqp_finished.argtypes = [H]
-    lib.dgsqp_finished.restype = C.c_int
-    lib.dgsqp_set_cooperative.argtypes = [H, C.c_int]
-    lib.dgsqp_set_cooperative.restype = C.c_int
-    lib.dgsqp_coop_stats.argtypes = [H, C.POINTER(C.c_uint64)]
-    lib.dgsqp_coop_stats.restype = C.c_int
-    lib.dgsqp_osqp_counters.argtypes = [H, C.POINTER(C.c_uint64), C.c_int]
-    lib.dgsqp_osqp_counters.restype = C.c_int
-    lib.dgsqp_set_deferral.argtypes = [H, C.c_int32, C.c_double]
-    lib.dgsqp_set_deferral.restype = C.c_int
-    lib.dgsqp_reserve_deferral.argtypes = [H, C.c_int64]
-    lib.dgsqp_reserve_deferral.restype = C.c_int
-    lib.dgsqp_deferral_stats.argtypes = [H, C.POINTER(C.c_uint64)]
-    lib.dgsqp_deferral_stats.restype = C.c_int
-    lib.dgsqp_deferral_log.argtypes = [H, C.POINTER(C.c_uint64), C.c_int64]
-    lib.dgsqp_deferral_log.restype = C.c_int
-    lib.dgsqp_sample_batch.argtypes = [H, C.c_int64, C.c_void_p, C.POINTER(PidT), _PD, _PD, C.POINTER(C.c_int64), C.c_int]
-    lib.dgsqp_sample_batch.restype = C.c_int
-    lib.dgsqp_synchronize.argtypes = [H]
-    lib.dgsqp_synchronize.restype = C.c_int
-    lib.dgsqp_comm_unique_id.argtypes = [C.c_char_p]
-    lib.dgsqp_comm_unique_id.restype = C.c_int
-    lib.dgsqp_comm_init.argtypes = [H, C.c_char_p, C.c_int, C.c_int]
-    lib.dgsqp_comm_init.restype = C.c_int
-    lib.dgsqp_comm_destroy.argtypes = [H]
-    lib.dgsqp_comm_destroy.restype = C.c_int
-    lib.dgsqp_gather_stats.argtypes = [H, C.c_int64, C.c_void_p]
-    lib.dgsqp_gather_stats.restype = C.c_int
-    lib.dgsqp_comm_barrier.argtypes = [H]
-    lib.dgsqp_comm_barrier.restype = C.c_int
-    lib.dgsqp_comm_allreduce_max.argtypes = [H, _PD, C.c_int]
-    lib.dgsqp_comm_allreduce_max.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIBS[int(workgroups_per_cu)] = lib
     if int(workgroups_per_cu) == 1:
         _LIB = lib
     return lib
-
-
-EXPORTED_SYMBOLS = ['dgsqp_create', 'dgsqp_destroy', 'dgsqp_dims', 'dgsqp_plan', 'dgsqp_last_error', 'dgsqp_backend_info',
-                    'dgsqp_solve_batch', 'dgsqp_stage_inputs', 'dgsqp_solve_staged', 'dgsqp_fetch_results',
-                    'dgsqp_evaluate_batch', 'dgsqp_qp_batch', 'dgsqp_qp_batch_info', 'dgsqp_set_trace', 'dgsqp_fetch_trace',
-                    'dgsqp_pid_warm_start_batch', 'dgsqp_launch_staged', 'dgsqp_wait', 'dgsqp_draining',
-                    'dgsqp_set_iterate_log', 'dgsqp_fetch_iterate_log', 'dgsqp_synchronize', 'dgsqp_finished', 'dgsqp_launch_staged_group', 'dgsqp_solve_batch_f32', 'dgsqp_comm_unique_id', 'dgsqp_comm_init',
-                    'dgsqp_comm_destroy', 'dgsqp_gather_stats', 'dgsqp_comm_barrier', 'dgsqp_comm_allreduce_max',
-                    'dgsqp_set_cooperative', 'dgsqp_coop_stats', 'dgsqp_osqp_counters', 'dgsqp_sample_batch', 'dgsqp_set_deferral', 'dgsqp_reserve_deferral', 'dgsqp_deferral_stats', 'dgsqp_deferral_log',
-                    'dgsqp_closed_loop_batch']
 
 
 def dptr(a):

@@ -204,6 +204,70 @@ struct DgEnvInit {
 } dg_env_init;
 }  // namespace
 
+// The per-scenario arrays of a solve, stated once: every host function that allocates, fills, hands out or copies them walks this
+// table.  The eight records from DG_U on are in the order of the C-ABI's result parameters (include/dgsqp.h).
+enum DgRec { DG_Q, DG_UWS, DG_W, DG_U, DG_L, DG_X, DG_STATUS, DG_ITERS, DG_QPS, DG_COND, DG_COST, DG_DONE, DG_REC_COUNT };
+// `fill` is the byte a closed-loop launch leaves where a step never ran: every byte 0xff is NaN in a double and DGSQP_NOT_RUN (-1) in a
+// status; counts are zero.  The kernel writes each slice it reaches once, on top of this.
+struct DgRecDesc { size_t elem, per; int fill; };      // bytes of an element, elements per scenario, fill byte
+struct DgRecTable {
+  DgRecDesc d[DG_REC_COUNT];
+  const DgRecDesc& operator[](int r) const { return d[r]; }
+  size_t bytes(int r) const { return d[r].elem * d[r].per; }      // of one scenario
+};
+// built once per handle, in dgsqp_create
+static DgRecTable rec_table(const DgProb& D) {
+  const size_t dbl = sizeof(double), i32 = sizeof(int32_t);
+  return DgRecTable{{
+      /* DG_Q      initial state (closed loop: the chain of states)   */ {dbl, (size_t)D.nq, 0xff},
+      /* DG_UWS    warm start, agent-major (closed loop: per step)    */ {dbl, (size_t)D.n, 0xff},
+      /* DG_W      closed loop only: disturbance of the plant         */ {dbl, (size_t)D.nq, 0xff},
+      /* DG_U      */ {dbl, (size_t)D.n, 0xff},
+      /* DG_L      */ {dbl, (size_t)D.nc, 0xff},
+      /* DG_X      */ {dbl, (size_t)(D.N + 1) * D.nq, 0xff},
+      /* DG_STATUS */ {i32, 1, 0xff},
+      /* DG_ITERS  */ {i32, 1, 0},
+      /* DG_QPS    */ {i32, 1, 0},
+      /* DG_COND   p_feas, comp, stat                                 */ {dbl, 3, 0xff},
+      /* DG_COST   */ {dbl, (size_t)D.M, 0xff},
+      /* DG_DONE   closed loop only: steps a chain ran                */ {i32, 1, 0}}};
+}
+// scenarios of each record that one use of a buffer set holds (0: that record is not part of it)
+struct DgRecCount { int64_t n[DG_REC_COUNT]; };
+// a staged batch: B of everything a plain solve reads and writes
+static DgRecCount rec_count_batch(int64_t B) {
+  DgRecCount c;
+  for (int r = 0; r < DG_REC_COUNT; r++) c.n[r] = (r == DG_W || r == DG_DONE) ? 0 : B;
+  return c;
+}
+// Device buffers over the table.  Every buffer grows exactly to what is asked of it and never shrinks.
+struct DgRecords {
+  void* p[DG_REC_COUNT] = {};
+  size_t bytes[DG_REC_COUNT] = {};
+  double* dbl(int r) const { return (double*)p[r]; }
+  // a record that is not part of this use is a null pointer to the kernels, whatever an earlier use left allocated
+  SolveOutPtrs out(const DgRecCount& c) const {
+    auto at = [&](int r) { return c.n[r] ? p[r] : nullptr; };
+    return SolveOutPtrs{(double*)at(DG_U), (double*)at(DG_L), (double*)at(DG_X), (double*)at(DG_COND), (double*)at(DG_COST),
+                        (int32_t*)at(DG_STATUS), (int32_t*)at(DG_ITERS), (int32_t*)at(DG_QPS)};
+  }
+};
+// the eight result parameters of the C-ABI, in its order, as a table of host pointers (null: not wanted)
+static void rec_host_table(void* dst[DG_REC_COUNT], void* u, void* l, void* x, void* status, void* iters, void* qp_solves, void* cond, void* cost) {
+  for (int r = 0; r < DG_REC_COUNT; r++) dst[r] = nullptr;
+  dst[DG_U] = u; dst[DG_L] = l; dst[DG_X] = x; dst[DG_STATUS] = status; dst[DG_ITERS] = iters; dst[DG_QPS] = qp_solves; dst[DG_COND] = cond; dst[DG_COST] = cost;
+}
+
+// Event trace and iterate log of a single launch: one scenario's slice is a count followed by `cap` entries.
+struct DgLog {
+  bool iterates;              // entries are iterates (u, l) -- n + n_c doubles -- and not (code, value) pairs
+  double* buf = nullptr;
+  int cap = 0;                // entries per scenario (0: off)
+  int64_t held = 0;           // scenarios the buffer holds
+  int64_t launch_B = 0;       // scenarios of the launch that filled it
+  int64_t doubles(const DgProb& D) const { return 1 + (int64_t)cap * (iterates ? D.n + D.nc : 2); }
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -218,13 +282,11 @@ struct dgsqp_solver {
   unsigned long long* ticket = nullptr;
   unsigned int* drained_host = nullptr;   // mapped host memory: 1 once the last launch has handed out its last scenario
   unsigned int* drained_dev = nullptr;
-  // staged batch
-  int64_t cap = 0, B = 0;
-  double *d_x0 = nullptr, *d_uws = nullptr, *d_u = nullptr, *d_l = nullptr, *d_x = nullptr, *d_cond = nullptr, *d_cost = nullptr;
-  int32_t *d_status = nullptr, *d_iters = nullptr, *d_qps = nullptr;
-  double* d_trace = nullptr; int trace_cap = 0; int64_t trace_B = 0;    // trace_B: scenarios the buffer holds
-  int64_t trace_launch_B = 0;                                             // scenarios of the launch that filled it
-  double* d_itlog = nullptr; int itlog_cap = 0; int64_t itlog_B = 0, itlog_launch_B = 0;
+  DgRecTable rec;                         // the record table of this handle's game
+  int64_t B = 0;                          // staged batch: its size ...
+  DgRecords staged;                       // ... and its arrays
+  DgRecords closed;                       // closed-loop launches (dgsqp_closed_loop_batch): step-major arrays
+  DgLog trace{false}, itlog{true};
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -242,10 +304,6 @@ struct dgsqp_solver {
   double defer_factor = 2.0;
   bool defer_requested = false;       // dgsqp_set_deferral was called (DG-SQP v2 is only deferred on request)
   dgsqp_comm_state* comm = nullptr;   // RCCL communicator + record buffers (dgsqp_comm.h), owned by the handle
-  // closed-loop launches (dgsqp_closed_loop_batch): step-major device arrays, grown on demand, freed in dgsqp_destroy
-  enum { CL_Q, CL_UWS, CL_W, CL_U, CL_L, CL_X, CL_COND, CL_COST, CL_STATUS, CL_ITERS, CL_QPS, CL_DONE, CL_COUNT };
-  void* cl_buf[CL_COUNT] = {};
-  size_t cl_bytes[CL_COUNT] = {};
   std::string err;
 };
 static thread_local std::string g_create_err;
@@ -261,28 +319,36 @@ static thread_local std::string g_create_err;
 
 #include "dgsqp_comm.h"
 
-static void free_batch(dgsqp_solver* h) {
-  void* ptrs[] = {h->d_x0, h->d_uws, h->d_u, h->d_l, h->d_x, h->d_cond, h->d_cost, h->d_status, h->d_iters, h->d_qps};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  h->d_x0 = h->d_uws = h->d_u = h->d_l = h->d_x = h->d_cond = h->d_cost = nullptr;
-  h->d_status = h->d_iters = h->d_qps = nullptr;
-  h->cap = 0;
+static void rec_free(DgRecords& S) {
+  for (int r = 0; r < DG_REC_COUNT; r++) { if (S.p[r]) (void)hipFree(S.p[r]); S.p[r] = nullptr; S.bytes[r] = 0; }
 }
-static int ensure_batch(dgsqp_solver* h, int64_t B) {
-  if (B <= h->cap) return DGSQP_OK;
-  free_batch(h);
-  const DgProb& D = h->hp;
-  HIPCHK(h, hipMalloc(&h->d_x0, sizeof(double) * B * D.nq));
-  HIPCHK(h, hipMalloc(&h->d_uws, sizeof(double) * B * D.n));
-  HIPCHK(h, hipMalloc(&h->d_u, sizeof(double) * B * D.n));
-  HIPCHK(h, hipMalloc(&h->d_l, sizeof(double) * B * D.nc));
-  HIPCHK(h, hipMalloc(&h->d_x, sizeof(double) * B * (D.N + 1) * D.nq));
-  HIPCHK(h, hipMalloc(&h->d_cond, sizeof(double) * B * 3));
-  HIPCHK(h, hipMalloc(&h->d_cost, sizeof(double) * B * D.M));
-  HIPCHK(h, hipMalloc(&h->d_status, sizeof(int32_t) * B));
-  HIPCHK(h, hipMalloc(&h->d_iters, sizeof(int32_t) * B));
-  HIPCHK(h, hipMalloc(&h->d_qps, sizeof(int32_t) * B));
-  h->cap = B;
+static int rec_reserve(dgsqp_solver* h, DgRecords& S, const DgRecCount& c) {
+  for (int r = 0; r < DG_REC_COUNT; r++) {
+    const size_t want = (size_t)c.n[r] * h->rec.bytes(r);
+    if (want <= S.bytes[r]) continue;
+    if (S.p[r]) (void)hipFree(S.p[r]);
+    S.p[r] = nullptr; S.bytes[r] = 0;
+    HIPCHK(h, hipMalloc(&S.p[r], want));
+    S.bytes[r] = want;
+  }
+  return DGSQP_OK;
+}
+// each record's fill byte over its scenarios from keep.n[r] on, in table order on h's stream
+static int rec_fill(dgsqp_solver* h, const DgRecords& S, const DgRecCount& c, const DgRecCount& keep) {
+  for (int r = 0; r < DG_REC_COUNT; r++) {
+    const size_t one = h->rec.bytes(r);
+    if (c.n[r] > keep.n[r]) HIPCHK(h, hipMemsetAsync((char*)S.p[r] + (size_t)keep.n[r] * one, h->rec[r].fill, (size_t)(c.n[r] - keep.n[r]) * one, h->stream));
+  }
+  return DGSQP_OK;
+}
+// c.n[r] scenarios of every record with a pointer in `host`, to the device or back, in table order on h's stream (no synchronise)
+static int rec_copy(dgsqp_solver* h, const DgRecords& S, const DgRecCount& c, void* const host[DG_REC_COUNT], hipMemcpyKind kind) {
+  for (int r = 0; r < DG_REC_COUNT; r++) {
+    if (!host[r] || c.n[r] == 0) continue;
+    const size_t bytes = (size_t)c.n[r] * h->rec.bytes(r);
+    if (kind == hipMemcpyHostToDevice) HIPCHK(h, hipMemcpyAsync(S.p[r], host[r], bytes, kind, h->stream));
+    else HIPCHK(h, hipMemcpyAsync(host[r], S.p[r], bytes, kind, h->stream));
+  }
   return DGSQP_OK;
 }
 static int ensure_ws(dgsqp_solver* h, size_t groups) {
@@ -358,21 +424,23 @@ static int upload_problem(dgsqp_solver* h) {
 // Cooperative line search for the launch about to be enqueued?  Helpers keep their compute units until the launch's last
 // scenario is done: right when nothing else waits for them (synchronous calls), wrong in a pipeline of launches -- the caller
 // says so (dgsqp_set_cooperative).  Needs the whole grid resident (it is: at most one workgroup per compute unit).
-// (development knobs: DGSQP_COOP_START = rejected trials after which a line search is offered to helpers, default 4;
+// (development knobs: DGSQP_COOP_START = rejected trials after which a line search is offered to helpers, default 2;
 //  DGSQP_COOP_VERIFY = 1: owners re-evaluate every helper value and count differing bits -- dgsqp_coop_stats)
-static int coop_start_trials() { const char* e = getenv("DGSQP_COOP_START"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v; }
-static int coop_window_trials() { const char* e = getenv("DGSQP_COOP_WINDOW"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v; }
-static int coop_max_helpers() { const char* e = getenv("DGSQP_COOP_HELPERS"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v; }
-static int coop_verify_mode() { const char* e = getenv("DGSQP_COOP_VERIFY"); return e && atoi(e) != 0; }
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+static int coop_start_trials() { return std::max(1, env_int("DGSQP_COOP_START", 2)); }
+static int coop_window_trials() { return std::max(1, env_int("DGSQP_COOP_WINDOW", 64)); }
+static int coop_max_helpers() { return std::max(1, env_int("DGSQP_COOP_HELPERS", 64)); }
+static int coop_verify_mode() { return env_int("DGSQP_COOP_VERIFY", 0) != 0; }
 static bool coop_for_launch(dgsqp_solver* h, int grid) {
-  if (!h->d_coop || grid > h->num_cu * 2 + 2 || h->trace_cap > 0) return false;
+  if (!h->d_coop || grid > h->num_cu * 2 + 2 || h->trace.cap > 0) return false;
   // (development knob DGSQP_COOP_MIN_CHAIN: only for games whose rollout is a dependent chain of at least that many evaluations of f_c,
   // N x substeps x stages.  With all idle workgroups helping, the euler games lost -- 409 -> 450 ms --; with the helpers capped at 64
   // they gain as well -- 362 -> 345 ms --, so the default is 0.)
   const dgsqp_problem_t& P = h->hp.P;
   const int stages = P.integrator == DGSQP_INT_RK4 ? 4 : (P.integrator == DGSQP_INT_RK3 ? 3 : (P.integrator == DGSQP_INT_RK2 ? 2 : 1));
   const int chain = P.N * (P.integrator == DGSQP_INT_EULER ? 1 : P.substeps * stages);
-  { const char* e = getenv("DGSQP_COOP_MIN_CHAIN"); if (chain < (e ? atoi(e) : 0)) return false; }
+  if (chain < env_int("DGSQP_COOP_MIN_CHAIN", 0)) return false;
   return h->coop_mode == 2 || (h->coop_mode == 1 && h->coop_next_sync);
 }
 // Deferral of long scenarios for the cooperative launch about to be enqueued on h's stream (DgPark, dgsqp_device.h): a quarter of
@@ -389,19 +457,17 @@ static int park_for_launch(dgsqp_solver* h, bool coop, int grid, int64_t total, 
   // save (20 batches of configs[1] in one launch, profiles/r06_osqp_deferral_sweep.txt: 4,410 scen/s at factor 2, 4,914 without deferral,
   // 5,337 at factor 4, 5,108 at 6; the exact QP has its optimum at 2: 11,739 against 11,105 at 3 and 10,129 without)
   if (h->hp.osqp && h->hp.big != 2 && !h->defer_requested) factor = 4.0;
-  int time_mode = 0;
-  { const char* e = getenv("DGSQP_DEFER_TIME"); if (e) time_mode = atoi(e) != 0; }
-  { const char* e = getenv("DGSQP_DEFER"); if (e && atoi(e) == 0) min_it = 0; }
-  { const char* e = getenv("DGSQP_DEFER_MIN_IT"); if (e) min_it = atoi(e); }
-  { const char* e = getenv("DGSQP_DEFER_FACTOR"); if (e) factor = atof(e); }
-  if (!coop || min_it <= 0 || total <= (int64_t)grid || h->trace_cap > 0 || h->itlog_cap > 0) return DGSQP_OK;
+  const int time_mode = env_int("DGSQP_DEFER_TIME", 0) != 0;
+  if (env_int("DGSQP_DEFER", 1) == 0) min_it = 0;
+  min_it = env_int("DGSQP_DEFER_MIN_IT", min_it);
+  factor = env_double("DGSQP_DEFER_FACTOR", factor);
+  if (!coop || min_it <= 0 || total <= (int64_t)grid || h->trace.cap > 0 || h->itlog.cap > 0) return DGSQP_OK;
   // DG-SQP v2: only when the caller asked for it (dgsqp_set_deferral).  Nearly every v2 scenario runs ~375 iterations and a few run
   // thousands: setting those aside delays exactly the solves that decide the launch's length (48 batches of 512 as 8 x 3 launches:
   // 409 scen/s without, 367 with; as one launch 404 / 411).
   if (h->hp.par.variant == DGSQP_VARIANT_V2 && !h->defer_requested) return DGSQP_OK;
   const size_t slot = (size_t)h->hp.L.total + (size_t)h->hp.ws_doubles;
-  double frac = 0.25;
-  { const char* e = getenv("DGSQP_DEFER_CAP_FRAC"); if (e) frac = atof(e); }
+  const double frac = env_double("DGSQP_DEFER_CAP_FRAC", 0.25);
   size_t cap = (size_t)((double)total * (frac > 0.0 && frac <= 1.0 ? frac : 0.25) + 1.0);
   DgParkPool& pool = g_park[h->device & 63];      // (g_reg_mutex is held by the launch functions)
   if (pool.owner && pool.owner != h && pool.owner->in_flight && pool.owner->launch_gen == pool.owner_gen) return DGSQP_OK;   // busy: no deferral
@@ -457,6 +523,107 @@ static int build_error_code(const std::string& msg) {
   return too_large ? DGSQP_E_TOO_LARGE : DGSQP_E_ARG;
 }
 
+// what dgsqp_dims and dgsqp_plan report about a built game
+static void fill_dims(const DgProb& D, dgsqp_dims_t* out) {
+  memset(out, 0, sizeof(*out));
+  out->M = D.M; out->N = D.N; out->n_q = D.nq; out->n_u = D.nu; out->n = D.n; out->n_c = D.nc;
+  out->n_dense = D.ndense; out->lds_bytes = D.L.total * 8; out->workspace_bytes = D.ws_doubles * (int64_t)sizeof(double);
+  out->layout = D.big;
+}
+
+// every entry point that is about to use the handle's buffers for B scenarios: no launch in flight, scratch for the grid of B
+static int idle_with_ws(dgsqp_solver* h, int64_t B) {
+  const int rc = wait_idle(h);
+  return rc ? rc : ensure_ws(h, (size_t)grid_for(h, B));
+}
+
+// What every launch that re-records ev[0] / ev[1] on h's stream begins with.  Takes g_reg_mutex: the caller keeps `lock` until its
+// kernel is enqueued and the handle marked in flight (upload_problem's contract).
+static int begin_launch(dgsqp_solver* h, std::unique_lock<std::mutex>& lock) {
+  lock = std::unique_lock<std::mutex>(g_reg_mutex);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
+  release_members(h);        // (members of an earlier grouped launch led by h: that kernel is done, its events are about to be reused)
+  return upload_problem(h);
+}
+
+// The synchronous test hooks, between "inputs are on the device" and "kernels finished": `enqueue` puts the hook's kernels on h's stream
+// while the registry is locked; the lock goes once the handle is marked in flight (a launch of another game then waits for them).
+template <class F>
+static int run_sync(dgsqp_solver* h, F enqueue) {
+  {
+    std::unique_lock<std::mutex> game_lock(g_reg_mutex);
+    { const int rc = upload_problem(h); if (rc) return rc; }
+    { const int rc = enqueue(); if (rc) return rc; }
+    h->in_flight = true;       // (the sampler's enqueue waits for every round itself: for that hook this mark and the wait below do nothing)
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->in_flight = false;
+  return DGSQP_OK;
+}
+
+// ---- the two logs (DgLog) ----
+// the buffer for a launch of B scenarios, or null while the log is off
+static int log_for_launch(dgsqp_solver* h, DgLog& g, int64_t B, double** out) {
+  *out = nullptr;
+  if (g.cap <= 0) return DGSQP_OK;
+  if (g.held < B) {
+    if (g.buf) (void)hipFree(g.buf);
+    g.buf = nullptr; g.held = 0;
+    HIPCHK(h, hipMalloc(&g.buf, sizeof(double) * B * (size_t)g.doubles(h->hp)));
+    g.held = B;
+  }
+  g.launch_B = B;
+  *out = g.buf;
+  return DGSQP_OK;
+}
+static int log_set(dgsqp_solver* h, DgLog& g, int cap) {
+  if (cap < 0) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  g.cap = cap;
+  g.held = g.launch_B = 0;
+  if (g.buf) { (void)hipFree(g.buf); g.buf = nullptr; }
+  return DGSQP_OK;
+}
+static int log_fetch(dgsqp_solver* h, DgLog& g, double* out, int64_t capacity_doubles, const char* none, const char* too_small) {
+  if (!out || g.cap <= 0 || !g.buf || g.launch_B <= 0) { h->err = none; return DGSQP_E_ARG; }
+  const int64_t need = g.launch_B * g.doubles(h->hp);
+  if (capacity_doubles < need) { h->err = std::string(too_small) + std::to_string(need) + " doubles"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(out, g.buf, sizeof(double) * need, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
+// The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
+// L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.
+static int launch_solve(dgsqp_solver* L, int64_t total, const DgBatch* group, int count) {
+  const int grid = grid_for(L, total);
+  std::unique_lock<std::mutex> game_lock;
+  { const int rc = begin_launch(L, game_lock); if (rc) return rc; }
+  double *trace = nullptr, *itlog = nullptr;      // (a grouped launch has neither: its caller refuses handles that record logs)
+  { const int rc = log_for_launch(L, L->trace, total, &trace); if (rc) return rc; }
+  { const int rc = log_for_launch(L, L->itlog, total, &itlog); if (rc) return rc; }
+  if (group) HIPCHK(L, hipMemcpyAsync(L->d_group, group, sizeof(DgBatch) * count, hipMemcpyHostToDevice, L->stream));
+  HIPCHK(L, hipMemsetAsync(L->ticket, 0, sizeof(unsigned long long), L->stream));
+  const bool coop = coop_for_launch(L, grid);
+  if (coop) HIPCHK(L, hipMemsetAsync(L->d_coop, 0, L->coop_bytes, L->stream));
+  DgPark park;
+  { const int rc = park_for_launch(L, coop, grid, total, &park); if (rc) return rc; }
+  HIPCHK(L, hipEventRecord(L->ev[0], L->stream));
+  *L->drained_host = 0u;
+  hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), L->lds_bytes, L->stream, L->dp, L->B, L->staged.dbl(DG_Q), L->staged.dbl(DG_UWS),
+                     L->staged.out(rec_count_batch(L->B)), L->ws, L->ticket, trace, L->trace.cap, L->drained_dev, itlog, L->itlog.cap,
+                     group ? (const DgBatch*)L->d_group : (const DgBatch*)nullptr, group ? count : 0,
+                     coop ? L->d_coop : (DgCoop*)nullptr, L->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park);
+  HIPCHK(L, hipGetLastError());
+  L->launch_gen++;
+  L->launched_grid = grid;
+  L->in_flight = true;       // (only now: an error return above leaves the handle idle)
+  HIPCHK(L, hipEventRecord(L->ev[1], L->stream));
+  return DGSQP_OK;
+}
+
 extern "C" {
 
 int dgsqp_backend_info(char* buf, int buflen) {
@@ -480,6 +647,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
     delete h;
     return build_error_code(msg);
   }
+  h->rec = rec_table(h->hp);
   if (DG_BLOCK != 512 && (h->hp.big == 2 || h->hp.classic_qp || h->hp.osqp)) {
     // the -DDG_BLOCK=256 build (two workgroups per CU, row N1): explicit-inverse layouts (n <= 128) with the active-set QP only
     g_create_err = "too large: this build (DG_BLOCK = 256, two workgroups per CU) holds the LDS-resident and big explicit-inverse layouts with the active-set QP only";
@@ -531,8 +699,8 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->group_host) (void)hipHostFree(h->group_host);
   if (h->comm) (void)dgsqp_comm_destroy(h);
   { std::lock_guard<std::mutex> lk(g_reg_mutex); g_handles.erase(std::remove(g_handles.begin(), g_handles.end(), h), g_handles.end()); }
-  free_batch(h);
-  for (void* p : h->cl_buf) if (p) (void)hipFree(p);
+  rec_free(h->staged);
+  rec_free(h->closed);
   if (h->ws) (void)hipFree(h->ws);
   if (h->dp) (void)hipFree(h->dp);
   if (h->ticket) (void)hipFree(h->ticket);
@@ -554,8 +722,8 @@ void dgsqp_destroy(dgsqp_handle_t h) {
     }
   }
   if (h->drained_host) (void)hipHostFree(h->drained_host);
-  if (h->d_trace) (void)hipFree(h->d_trace);
-  if (h->d_itlog) (void)hipFree(h->d_itlog);
+  if (h->trace.buf) (void)hipFree(h->trace.buf);
+  if (h->itlog.buf) (void)hipFree(h->itlog.buf);
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -563,10 +731,7 @@ void dgsqp_destroy(dgsqp_handle_t h) {
 
 int dgsqp_dims(dgsqp_handle_t h, dgsqp_dims_t* out) {
   if (!h || !out) return DGSQP_E_ARG;
-  const DgProb& D = h->hp;
-  out->M = D.M; out->N = D.N; out->n_q = D.nq; out->n_u = D.nu; out->n = D.n; out->n_c = D.nc;
-  out->n_dense = D.ndense; out->lds_bytes = (int32_t)h->lds_bytes; out->workspace_bytes = D.ws_doubles * (int64_t)sizeof(double);
-  out->layout = D.big; out->reserved_ = 0;
+  fill_dims(h->hp, out);
   return DGSQP_OK;
 }
 
@@ -575,29 +740,33 @@ int dgsqp_plan(const dgsqp_problem_t* prob, const dgsqp_params_t* par, dgsqp_dim
   static DgProb D;     // ~100 KB: not on the stack (single-threaded helper, like dgsqp_create)
   const std::string err = dg_build(*prob, *par, D);
   if (msg && msglen > 0) snprintf(msg, msglen, "%s", err.c_str());
-  memset(out, 0, sizeof(*out));
-  out->M = D.M; out->N = D.N; out->n_q = D.nq; out->n_u = D.nu; out->n = D.n; out->n_c = D.nc;
-  out->n_dense = D.ndense; out->lds_bytes = D.L.total * 8; out->workspace_bytes = D.ws_doubles * (int64_t)sizeof(double);
-  out->layout = D.big;
+  fill_dims(D, out);
   if (!err.empty()) return build_error_code(err);
   return DGSQP_OK;
 }
 
 const char* dgsqp_last_error(dgsqp_handle_t h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+// what dgsqp_stage_inputs, the fp32 boundary and the sampler begin with: the handle idle, then staged arrays and scratch for B scenarios
+static int stage_begin(dgsqp_solver* h, int64_t B) {
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }            // the buffers below belong to the launch in flight, if any
+  if (B == 0) return DGSQP_OK;
+  int rc = rec_reserve(h, h->staged, rec_count_batch(B));
+  if (!rc) rc = ensure_ws(h, (size_t)grid_for(h, B));
+  if (rc) h->B = 0;        // (some staged buffers may be gone: nothing is staged any more)
+  return rc;
+}
+
 int dgsqp_stage_inputs(dgsqp_handle_t h, int64_t B, const double* x0, const double* u_ws) {
   if (!h || B < 0 || (B > 0 && (!x0 || !u_ws))) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = wait_idle(h);            // the buffers below belong to the launch in flight, if any
+  int rc = stage_begin(h, B);
   if (rc) return rc;
   h->B = B;
   if (B == 0) return DGSQP_OK;
-  rc = ensure_batch(h, B);
-  if (rc) return rc;
-  rc = ensure_ws(h, (size_t)grid_for(h, B));
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->d_x0, x0, sizeof(double) * B * h->hp.nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_uws, u_ws, sizeof(double) * B * h->hp.n, hipMemcpyHostToDevice, h->stream));
+  void* in[DG_REC_COUNT] = {};
+  in[DG_Q] = (void*)x0; in[DG_UWS] = (void*)u_ws;
+  if ((rc = rec_copy(h, h->staged, rec_count_batch(B), in, hipMemcpyHostToDevice))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DGSQP_OK;
 }
@@ -608,50 +777,7 @@ int dgsqp_launch_staged(dgsqp_handle_t h) {
   { int rcw = wait_idle(h); if (rcw) return rcw; }     // one launch in flight per handle
   h->launched_grid = 0;
   if (h->B == 0) return DGSQP_OK;
-  const int grid = grid_for(h, h->B);
-  SolveOutPtrs O{h->d_u, h->d_l, h->d_x, h->d_cond, h->d_cost, h->d_status, h->d_iters, h->d_qps};
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
-  release_members(h);        // (members of an earlier grouped launch led by h: that kernel is done, its events are about to be reused)
-  { int rcu = upload_problem(h); if (rcu) return rcu; }
-  double* trace = nullptr;
-  if (h->trace_cap > 0) {
-    if (h->trace_B < h->B) {
-      if (h->d_trace) (void)hipFree(h->d_trace);
-      h->d_trace = nullptr; h->trace_B = 0;
-      HIPCHK(h, hipMalloc(&h->d_trace, sizeof(double) * h->B * (1 + 2 * (size_t)h->trace_cap)));
-      h->trace_B = h->B;
-    }
-    trace = h->d_trace;
-    h->trace_launch_B = h->B;
-  }
-  double* itlog = nullptr;
-  if (h->itlog_cap > 0) {
-    const size_t per = 1 + (size_t)h->itlog_cap * (h->hp.n + h->hp.nc);
-    if (h->itlog_B < h->B) {
-      if (h->d_itlog) (void)hipFree(h->d_itlog);
-      h->d_itlog = nullptr; h->itlog_B = 0;
-      HIPCHK(h, hipMalloc(&h->d_itlog, sizeof(double) * h->B * per));
-      h->itlog_B = h->B;
-    }
-    itlog = h->d_itlog;
-    h->itlog_launch_B = h->B;
-  }
-  HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
-  const bool coop = coop_for_launch(h, grid);
-  if (coop) HIPCHK(h, hipMemsetAsync(h->d_coop, 0, h->coop_bytes, h->stream));
-  DgPark park;
-  { const int rcp = park_for_launch(h, coop, grid, h->B, &park); if (rcp) return rcp; }
-  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  *h->drained_host = 0u;
-  hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, h->B, h->d_x0, h->d_uws, O, h->ws, h->ticket, trace, h->trace_cap, h->drained_dev, itlog, h->itlog_cap, (const DgBatch*)nullptr, 0,
-                     coop ? h->d_coop : (DgCoop*)nullptr, h->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park);
-  HIPCHK(h, hipGetLastError());
-  h->launch_gen++;
-  h->launched_grid = grid;
-  h->in_flight = true;       // (only now: an error return above leaves the handle idle)
-  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  return DGSQP_OK;
+  return launch_solve(h, h->B, nullptr, 0);
 }
 
 int dgsqp_launch_staged_group(const dgsqp_handle_t* hs, int count) {
@@ -666,39 +792,19 @@ int dgsqp_launch_staged_group(const dgsqp_handle_t* hs, int count) {
     if (h->device != L->device || h->B != L->B || L->B <= 0 || memcmp(&h->hp, &L->hp, sizeof(DgProb)) != 0) {
       L->err = "grouped launch: every handle must hold a staged batch of the same size, of the same game, on the same device"; return DGSQP_E_ARG;
     }
-    if (h->trace_cap > 0 || h->itlog_cap > 0) { L->err = "grouped launch: event / iterate logs are per single launch"; return DGSQP_E_ARG; }
+    if (h->trace.cap > 0 || h->itlog.cap > 0) { L->err = "grouped launch: event / iterate logs are per single launch"; return DGSQP_E_ARG; }
     const int rcw = wait_idle(h);
     if (rcw) return rcw;
   }
-  const int grid = grid_for(L, L->B * count);
-  { const int rce = ensure_ws(L, (size_t)grid); if (rce) return rce; }
+  { const int rce = ensure_ws(L, (size_t)grid_for(L, L->B * count)); if (rce) return rce; }
   if (!L->d_group) HIPCHK(L, hipMalloc(&L->d_group, sizeof(DgBatch) * DG_GROUP_MAX));
   if (!L->group_host) HIPCHK(L, hipHostMalloc((void**)&L->group_host, sizeof(DgBatch) * DG_GROUP_MAX, hipHostMallocDefault));
-  for (int i = 0; i < count; i++) {
-    dgsqp_solver* h = hs[i];
-    L->group_host[i] = DgBatch{h->d_x0, h->d_uws, SolveOutPtrs{h->d_u, h->d_l, h->d_x, h->d_cond, h->d_cost, h->d_status, h->d_iters, h->d_qps}};
-  }
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  if (hipStreamSynchronize(L->stream) != hipSuccess) { L->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
-  release_members(L);
-  { int rcu = upload_problem(L); if (rcu) return rcu; }
-  HIPCHK(L, hipMemcpyAsync(L->d_group, L->group_host, sizeof(DgBatch) * count, hipMemcpyHostToDevice, L->stream));
-  HIPCHK(L, hipMemsetAsync(L->ticket, 0, sizeof(unsigned long long), L->stream));
-  const bool coop = coop_for_launch(L, grid);
-  if (coop) HIPCHK(L, hipMemsetAsync(L->d_coop, 0, L->coop_bytes, L->stream));
-  DgPark park;
-  { const int rcp = park_for_launch(L, coop, grid, L->B * count, &park); if (rcp) return rcp; }
-  HIPCHK(L, hipEventRecord(L->ev[0], L->stream));
-  *L->drained_host = 0u;
-  SolveOutPtrs O0 = L->group_host[0].O;
-  hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), L->lds_bytes, L->stream, L->dp, L->B, L->d_x0, L->d_uws, O0, L->ws, L->ticket,
-                     (double*)nullptr, 0, L->drained_dev, (double*)nullptr, 0, (const DgBatch*)L->d_group, count,
-                     coop ? L->d_coop : (DgCoop*)nullptr, L->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park);
-  HIPCHK(L, hipGetLastError());
-  L->launch_gen++;
-  for (int i = 0; i < count; i++) { hs[i]->launched_grid = grid; hs[i]->in_flight = true; hs[i]->group_leader = i == 0 ? nullptr : L; hs[i]->group_gen = L->launch_gen; }
-  HIPCHK(L, hipEventRecord(L->ev[1], L->stream));
-  return DGSQP_OK;
+  for (int i = 0; i < count; i++) L->group_host[i] = DgBatch{hs[i]->staged.dbl(DG_Q), hs[i]->staged.dbl(DG_UWS), hs[i]->staged.out(rec_count_batch(L->B))};
+  const int rc = launch_solve(L, L->B * count, L->group_host, count);
+  // (every handle was idle above: the leader is in flight exactly when the kernel was enqueued, and then so are the members' batches)
+  if (L->in_flight)
+    for (int i = 0; i < count; i++) { hs[i]->launched_grid = L->launched_grid; hs[i]->in_flight = true; hs[i]->group_leader = i == 0 ? nullptr : L; hs[i]->group_gen = L->launch_gen; }
+  return rc;
 }
 
 int dgsqp_draining(dgsqp_handle_t h) {
@@ -824,18 +930,11 @@ int dgsqp_fetch_results(dgsqp_handle_t h, double* u_out, double* l_out, double* 
                         int32_t* qp_solves, double* cond, double* cost) {
   if (!h) return DGSQP_E_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  const DgProb& D = h->hp;
-  const int64_t B = h->B;
-  if (B == 0) return DGSQP_OK;
+  if (h->B == 0) return DGSQP_OK;
   { const int rcw = wait_idle(h); if (rcw) return rcw; }      // (a member of a grouped launch was solved on its leader's stream)
-  if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, h->d_u, sizeof(double) * B * D.n, hipMemcpyDeviceToHost, h->stream));
-  if (l_out) HIPCHK(h, hipMemcpyAsync(l_out, h->d_l, sizeof(double) * B * D.nc, hipMemcpyDeviceToHost, h->stream));
-  if (x_out) HIPCHK(h, hipMemcpyAsync(x_out, h->d_x, sizeof(double) * B * (D.N + 1) * D.nq, hipMemcpyDeviceToHost, h->stream));
-  if (status) HIPCHK(h, hipMemcpyAsync(status, h->d_status, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIPCHK(h, hipMemcpyAsync(iters, h->d_iters, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream));
-  if (qp_solves) HIPCHK(h, hipMemcpyAsync(qp_solves, h->d_qps, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream));
-  if (cond) HIPCHK(h, hipMemcpyAsync(cond, h->d_cond, sizeof(double) * B * 3, hipMemcpyDeviceToHost, h->stream));
-  if (cost) HIPCHK(h, hipMemcpyAsync(cost, h->d_cost, sizeof(double) * B * D.M, hipMemcpyDeviceToHost, h->stream));
+  void* dst[DG_REC_COUNT];
+  rec_host_table(dst, u_out, l_out, x_out, status, iters, qp_solves, cond, cost);
+  { const int rc = rec_copy(h, h->staged, rec_count_batch(h->B), dst, hipMemcpyDeviceToHost); if (rc) return rc; }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DGSQP_OK;
 }
@@ -865,15 +964,6 @@ int dgsqp_solve_batch(dgsqp_handle_t h, int64_t B, const double* x0, const doubl
 }
 
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h).
-static int cl_reserve(dgsqp_solver* h, int which, size_t bytes) {
-  if (bytes <= h->cl_bytes[which]) return DGSQP_OK;
-  if (h->cl_buf[which]) (void)hipFree(h->cl_buf[which]);
-  h->cl_buf[which] = nullptr; h->cl_bytes[which] = 0;
-  HIPCHK(h, hipMalloc(&h->cl_buf[which], bytes));
-  h->cl_bytes[which] = bytes;
-  return DGSQP_OK;
-}
-
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -886,49 +976,33 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
-  const DgProb& D = h->hp;
-  const size_t TB = (size_t)T * (size_t)B, dbl = sizeof(double), i32 = sizeof(int32_t);
-  const size_t nx = (size_t)(D.N + 1) * D.nq;
-  const size_t by_q = (TB + B) * D.nq * dbl, by_uws = (TB + B) * D.n * dbl, by_w = TB * D.nq * dbl, by_u = TB * D.n * dbl, by_l = TB * D.nc * dbl;
-  const size_t by_x = (x_out ? TB : (size_t)B) * nx * dbl, by_cond = TB * 3 * dbl, by_cost = TB * D.M * dbl;
-  const size_t want[dgsqp_solver::CL_COUNT] = {by_q, by_uws, w ? by_w : 0, by_u, l_out ? by_l : 0, by_x, by_cond, by_cost, TB * i32, TB * i32, TB * i32, (size_t)B * i32};
-  for (int i = 0; i < dgsqp_solver::CL_COUNT; i++) { const int rc = cl_reserve(h, i, want[i]); if (rc) return rc; }
+  // Step-major arrays: T x B of every record, one more slice of the state and warm-start chains; c = scenarios per record, keep = the
+  // leading ones that are copied in and not filled.  Without x_out one [B][N+1][nq] slice serves every step, without l_out there is no l.
+  const int64_t TB = (int64_t)T * B;
+  DgRecCount c, keep;
+  for (int r = 0; r < DG_REC_COUNT; r++) { c.n[r] = TB; keep.n[r] = 0; }
+  c.n[DG_Q] = c.n[DG_UWS] = TB + B; keep.n[DG_Q] = keep.n[DG_UWS] = B;
+  c.n[DG_W] = keep.n[DG_W] = w ? TB : 0;
+  c.n[DG_L] = l_out ? TB : 0;
+  if (!x_out) c.n[DG_X] = keep.n[DG_X] = B;
+  c.n[DG_DONE] = B;
+  DgRecords& S = h->closed;
+  { const int rc = idle_with_ws(h, B); if (rc) return rc; }
+  { const int rc = rec_reserve(h, S, c); if (rc) return rc; }
   const int grid = grid_for(h, B);
-  { const int rc = ensure_ws(h, (size_t)grid); if (rc) return rc; }
-  double* d_q = (double*)h->cl_buf[dgsqp_solver::CL_Q]; double* d_uws = (double*)h->cl_buf[dgsqp_solver::CL_UWS];
-  double* d_w = w ? (double*)h->cl_buf[dgsqp_solver::CL_W] : nullptr;
-  double* d_u = (double*)h->cl_buf[dgsqp_solver::CL_U]; double* d_l = l_out ? (double*)h->cl_buf[dgsqp_solver::CL_L] : nullptr;
-  double* d_x = (double*)h->cl_buf[dgsqp_solver::CL_X]; double* d_cond = (double*)h->cl_buf[dgsqp_solver::CL_COND]; double* d_cost = (double*)h->cl_buf[dgsqp_solver::CL_COST];
-  int32_t* d_status = (int32_t*)h->cl_buf[dgsqp_solver::CL_STATUS]; int32_t* d_iters = (int32_t*)h->cl_buf[dgsqp_solver::CL_ITERS];
-  int32_t* d_qps = (int32_t*)h->cl_buf[dgsqp_solver::CL_QPS]; int32_t* d_done = (int32_t*)h->cl_buf[dgsqp_solver::CL_DONE];
   HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  // What a step that never runs leaves behind: every byte 0xff is NaN in a double and DGSQP_NOT_RUN (-1) in a status; zero counts.
-  // The kernel writes each slice it reaches once, on top of this.
-  HIPCHK(h, hipMemsetAsync(d_q + (size_t)B * D.nq, 0xff, by_q - (size_t)B * D.nq * dbl, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_uws + (size_t)B * D.n, 0xff, by_uws - (size_t)B * D.n * dbl, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_u, 0xff, by_u, h->stream));
-  if (d_l) HIPCHK(h, hipMemsetAsync(d_l, 0xff, by_l, h->stream));
-  if (x_out) HIPCHK(h, hipMemsetAsync(d_x, 0xff, by_x, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_cond, 0xff, by_cond, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_cost, 0xff, by_cost, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_status, 0xff, TB * i32, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_iters, 0, TB * i32, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_qps, 0, TB * i32, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_done, 0, (size_t)B * i32, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_q, x0, (size_t)B * D.nq * dbl, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_uws, u_ws, (size_t)B * D.n * dbl, hipMemcpyHostToDevice, h->stream));
-  if (d_w) HIPCHK(h, hipMemcpyAsync(d_w, w, by_w, hipMemcpyHostToDevice, h->stream));
+  { const int rc = rec_fill(h, S, c, keep); if (rc) return rc; }
+  void* host[DG_REC_COUNT] = {};
+  host[DG_Q] = (void*)x0; host[DG_UWS] = (void*)u_ws; host[DG_W] = (void*)w;
+  { const int rc = rec_copy(h, S, keep, host, hipMemcpyHostToDevice); if (rc) return rc; }
   DgClosedLoop cl;
-  cl.T = T; cl.q = d_q; cl.uws = d_uws; cl.w = d_w;
-  cl.O = SolveOutPtrs{d_u, d_l, d_x, d_cond, d_cost, d_status, d_iters, d_qps};
-  cl.x_step = x_out ? (int64_t)B * (int64_t)nx : 0;
-  cl.steps_done = d_done;
+  cl.T = T; cl.q = S.dbl(DG_Q); cl.uws = S.dbl(DG_UWS); cl.w = w ? S.dbl(DG_W) : nullptr;
+  cl.O = S.out(c);
+  cl.x_step = x_out ? B * (int64_t)h->rec[DG_X].per : 0;
+  cl.steps_done = (int32_t*)S.p[DG_DONE];
   {
-    std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
-    release_members(h);        // (as in dgsqp_launch_staged: ev[0] / ev[1] are about to be reused)
-    { const int rcu = upload_problem(h); if (rcu) return rcu; }
+    std::unique_lock<std::mutex> game_lock;
+    { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     hipLaunchKernelGGL(dg_closed_loop_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
@@ -938,17 +1012,9 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->in_flight = false;
-  HIPCHK(h, hipMemcpyAsync(q_out, d_q, by_q, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(u_ws_out, d_uws, by_uws, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(u_out, d_u, by_u, hipMemcpyDeviceToHost, h->stream));
-  if (l_out) HIPCHK(h, hipMemcpyAsync(l_out, d_l, by_l, hipMemcpyDeviceToHost, h->stream));
-  if (x_out) HIPCHK(h, hipMemcpyAsync(x_out, d_x, by_x, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(status, d_status, TB * i32, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(iters, d_iters, TB * i32, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(qp_solves, d_qps, TB * i32, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(cond, d_cond, by_cond, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(cost, d_cost, by_cost, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(steps_done, d_done, (size_t)B * i32, hipMemcpyDeviceToHost, h->stream));
+  rec_host_table(host, u_out, l_out, x_out, status, iters, qp_solves, cond, cost);
+  host[DG_Q] = q_out; host[DG_UWS] = u_ws_out; host[DG_DONE] = steps_done;
+  { const int rc = rec_copy(h, S, c, host, hipMemcpyDeviceToHost); if (rc) return rc; }
   HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (tm) {
@@ -974,49 +1040,43 @@ int dgsqp_solve_batch_f32(dgsqp_handle_t h, int64_t B, const float* x0, const fl
                           float* x_out, int32_t* status, int32_t* iters, int32_t* qp_solves, float* cond, float* cost,
                           dgsqp_timing_t* tm) {
   if (!h || B < 0 || (B > 0 && (!x0 || !u_ws))) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = wait_idle(h);
+  int rc = stage_begin(h, B);
   if (rc) return rc;
   h->B = B;
   if (B == 0) return DGSQP_OK;
-  rc = ensure_batch(h, B);
-  if (rc) return rc;
-  rc = ensure_ws(h, (size_t)grid_for(h, B));
-  if (rc) return rc;
-  const DgProb& D = h->hp;
-  const size_t nx = (size_t)(D.N + 1) * D.nq;
-  size_t big = (size_t)B * (D.nc > (int)nx ? (size_t)D.nc : nx);
-  if ((size_t)B * D.n > big) big = (size_t)B * D.n;
+  const DgRecCount c = rec_count_batch(B);
+  const DgRecords& S = h->staged;
+  size_t big = 0;
+  for (int r = 0; r < DG_REC_COUNT; r++) big = std::max(big, (size_t)c.n[r] * h->rec[r].per);
   TmpBuf tb;
   float* f = tb.alloc<float>(big);          // one single-precision staging buffer, reused for every array
   if (!f) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
   HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  auto in = [&](const float* src, double* dst, size_t cnt) -> int {
-    HIPCHK(h, hipMemcpyAsync(f, src, sizeof(float) * cnt, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(dg_widen_kernel, dim3(256), dim3(256), 0, h->stream, (int64_t)cnt, f, dst);
+  const float* in[DG_REC_COUNT] = {};
+  in[DG_Q] = x0; in[DG_UWS] = u_ws;
+  for (int r = 0; r < DG_REC_COUNT; r++) {
+    if (!in[r]) continue;
+    const size_t cnt = (size_t)c.n[r] * h->rec[r].per;
+    HIPCHK(h, hipMemcpyAsync(f, in[r], sizeof(float) * cnt, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(dg_widen_kernel, dim3(256), dim3(256), 0, h->stream, (int64_t)cnt, f, S.dbl(r));
     HIPCHK(h, hipGetLastError());
-    return DGSQP_OK;
-  };
-  if ((rc = in(x0, h->d_x0, (size_t)B * D.nq))) return rc;
-  if ((rc = in(u_ws, h->d_uws, (size_t)B * D.n))) return rc;
+  }
   dgsqp_timing_t t2;
   rc = dgsqp_solve_staged(h, &t2);
   if (rc) return rc;
-  auto out = [&](const double* src, float* dst, size_t cnt) -> int {
-    if (!dst) return DGSQP_OK;
-    hipLaunchKernelGGL(dg_narrow_kernel, dim3(256), dim3(256), 0, h->stream, (int64_t)cnt, src, f);
+  void* dst[DG_REC_COUNT];
+  rec_host_table(dst, u_out, l_out, x_out, status, iters, qp_solves, cond, cost);
+  for (int r = 0; r < DG_REC_COUNT; r++) {      // the double records are narrowed on the device; the counts are copied as they are
+    if (!dst[r] || h->rec[r].elem != sizeof(double)) continue;
+    const size_t cnt = (size_t)c.n[r] * h->rec[r].per;
+    hipLaunchKernelGGL(dg_narrow_kernel, dim3(256), dim3(256), 0, h->stream, (int64_t)cnt, (const double*)S.dbl(r), f);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(dst, f, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dst[r], f, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));       // f is reused by the next array
-    return DGSQP_OK;
-  };
-  if ((rc = out(h->d_u, u_out, (size_t)B * D.n))) return rc;
-  if ((rc = out(h->d_l, l_out, (size_t)B * D.nc))) return rc;
-  if ((rc = out(h->d_x, x_out, (size_t)B * nx))) return rc;
-  if ((rc = out(h->d_cond, cond, (size_t)B * 3))) return rc;
-  if ((rc = out(h->d_cost, cost, (size_t)B * D.M))) return rc;
-  rc = dgsqp_fetch_results(h, nullptr, nullptr, nullptr, status, iters, qp_solves, nullptr, nullptr);
-  if (rc) return rc;
+    dst[r] = nullptr;
+  }
+  if ((rc = rec_copy(h, S, c, dst, hipMemcpyDeviceToHost))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (tm) {
@@ -1054,44 +1114,13 @@ int dgsqp_prof_read(unsigned long long* out, int n) {
 #endif
 }
 
-int dgsqp_set_trace(dgsqp_handle_t h, int pairs_per_scenario) {
-  if (!h || pairs_per_scenario < 0) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rc = wait_idle(h); if (rc) return rc; }
-  h->trace_cap = pairs_per_scenario;
-  h->trace_B = h->trace_launch_B = 0;
-  if (h->d_trace) { (void)hipFree(h->d_trace); h->d_trace = nullptr; }
-  return DGSQP_OK;
-}
-
+int dgsqp_set_trace(dgsqp_handle_t h, int pairs_per_scenario) { return h ? log_set(h, h->trace, pairs_per_scenario) : DGSQP_E_ARG; }
 int dgsqp_fetch_trace(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
-  if (!h || !out || h->trace_cap <= 0 || !h->d_trace || h->trace_launch_B <= 0) { if (h) h->err = "no trace recorded"; return DGSQP_E_ARG; }
-  const int64_t need = h->trace_launch_B * (1 + 2 * (int64_t)h->trace_cap);
-  if (capacity_doubles < need) { h->err = "trace buffer too small: need " + std::to_string(need) + " doubles"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(out, h->d_trace, sizeof(double) * need, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  return h ? log_fetch(h, h->trace, out, capacity_doubles, "no trace recorded", "trace buffer too small: need ") : DGSQP_E_ARG;
 }
-
-int dgsqp_set_iterate_log(dgsqp_handle_t h, int records_per_scenario) {
-  if (!h || records_per_scenario < 0) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rc = wait_idle(h); if (rc) return rc; }
-  h->itlog_cap = records_per_scenario;
-  h->itlog_B = h->itlog_launch_B = 0;
-  if (h->d_itlog) { (void)hipFree(h->d_itlog); h->d_itlog = nullptr; }
-  return DGSQP_OK;
-}
-
+int dgsqp_set_iterate_log(dgsqp_handle_t h, int records_per_scenario) { return h ? log_set(h, h->itlog, records_per_scenario) : DGSQP_E_ARG; }
 int dgsqp_fetch_iterate_log(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
-  if (!h || !out || h->itlog_cap <= 0 || !h->d_itlog || h->itlog_launch_B <= 0) { if (h) h->err = "no iterate log recorded"; return DGSQP_E_ARG; }
-  const int64_t need = h->itlog_launch_B * (1 + (int64_t)h->itlog_cap * (h->hp.n + h->hp.nc));
-  if (capacity_doubles < need) { h->err = "iterate-log buffer too small: need " + std::to_string(need) + " doubles"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(out, h->d_itlog, sizeof(double) * need, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  return h ? log_fetch(h, h->itlog, out, capacity_doubles, "no iterate log recorded", "iterate-log buffer too small: need ") : DGSQP_E_ARG;
 }
 
 int dgsqp_synchronize(dgsqp_handle_t h) {
@@ -1111,9 +1140,7 @@ int dgsqp_evaluate_batch(dgsqp_handle_t h, int64_t B, const double* x0, const do
   HIPCHK(h, hipSetDevice(h->device));
   const DgProb& D = h->hp;
   const int grid = grid_for(h, B);
-  int rc = wait_idle(h);
-  if (rc) return rc;
-  rc = ensure_ws(h, (size_t)grid);
+  int rc = idle_with_ws(h, B);
   if (rc) return rc;
   TmpBuf tb;
   const size_t n = D.n, nc = D.nc, nx = (size_t)(D.N + 1) * D.nq;
@@ -1126,13 +1153,12 @@ int dgsqp_evaluate_batch(dgsqp_handle_t h, int64_t B, const double* x0, const do
   HIPCHK(h, hipMemcpy(dx0, x0, sizeof(double) * B * D.nq, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(du, u, sizeof(double) * B * n, hipMemcpyHostToDevice));
   if (l) HIPCHK(h, hipMemcpy(dl, l, sizeof(double) * B * nc, hipMemcpyHostToDevice));
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  { int rcu = upload_problem(h); if (rcu) return rcu; }
-  h->in_flight = true;
-  hipLaunchKernelGGL(dg_evaluate_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, dq, dg, dG, dQ, dx, dl0, h->ws);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->in_flight = false;
+  rc = run_sync(h, [&]() -> int {
+    hipLaunchKernelGGL(dg_evaluate_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, dq, dg, dG, dQ, dx, dl0, h->ws);
+    HIPCHK(h, hipGetLastError());
+    return DGSQP_OK;
+  });
+  if (rc) return rc;
   if (q) HIPCHK(h, hipMemcpy(q, dq, sizeof(double) * B * n, hipMemcpyDeviceToHost));
   if (g) HIPCHK(h, hipMemcpy(g, dg, sizeof(double) * B * nc, hipMemcpyDeviceToHost));
   if (G) HIPCHK(h, hipMemcpy(G, dG, sizeof(double) * B * nc * n, hipMemcpyDeviceToHost));
@@ -1157,20 +1183,19 @@ int dgsqp_pid_warm_start_batch(dgsqp_handle_t h, int64_t B, const double* q0, co
   int32_t* dc = collide ? tb.alloc<int32_t>(B) : nullptr;
   if (!dq0 || !du || ((q_ws || collide) && !dq) || (collide && !dc)) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
   HIPCHK(h, hipMemcpy(dq0, q0, sizeof(double) * B * D.nq, hipMemcpyHostToDevice));
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  { int rcu = upload_problem(h); if (rcu) return rcu; }
-  h->in_flight = true;
   const int64_t lanes = B * D.M;
   int grid = (int)((lanes + DG_BLOCK - 1) / DG_BLOCK);
   if (grid > 4 * h->num_cu) grid = 4 * h->num_cu;
-  hipLaunchKernelGGL(dg_pid_kernel, dim3(grid), dim3(DG_BLOCK), (size_t)D.L.scr * sizeof(double), h->stream, B, dq0, *pid, du, dq);
-  HIPCHK(h, hipGetLastError());
-  if (collide) {
-    hipLaunchKernelGGL(dg_collide_kernel, dim3((int)((B + 255) / 256)), dim3(256), 0, h->stream, B, dq, dc);
+  const int rc = run_sync(h, [&]() -> int {
+    hipLaunchKernelGGL(dg_pid_kernel, dim3(grid), dim3(DG_BLOCK), (size_t)D.L.scr * sizeof(double), h->stream, B, dq0, *pid, du, dq);
     HIPCHK(h, hipGetLastError());
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->in_flight = false;
+    if (collide) {
+      hipLaunchKernelGGL(dg_collide_kernel, dim3((int)((B + 255) / 256)), dim3(256), 0, h->stream, B, dq, dc);
+      HIPCHK(h, hipGetLastError());
+    }
+    return DGSQP_OK;
+  });
+  if (rc) return rc;
   HIPCHK(h, hipMemcpy(u_ws, du, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
   if (q_ws) HIPCHK(h, hipMemcpy(q_ws, dq, sizeof(double) * B * nx, hipMemcpyDeviceToHost));
   if (collide) HIPCHK(h, hipMemcpy(collide, dc, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
@@ -1188,50 +1213,51 @@ int dgsqp_sample_batch(dgsqp_handle_t h, int64_t B, const dgsqp_sampler_t* spec,
     if ((D.nqa[a] == 4) != merge) { h->err = "sampler and vehicle model do not fit (merge: unicycles; the others: Frenet-frame models)"; return DGSQP_E_ARG; }
   if (candidates) *candidates = 0;
   if (B == 0) return DGSQP_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rc = wait_idle(h); if (rc) return rc; }
-  { int rc = ensure_batch(h, B); if (rc) return rc; }
-  { int rc = ensure_ws(h, (size_t)grid_for(h, B)); if (rc) return rc; }
+  { const int rc = stage_begin(h, B); if (rc) return rc; }
+  double *const d_x0 = h->staged.dbl(DG_Q), *const d_uws = h->staged.dbl(DG_UWS);
   const int64_t nround = std::max<int64_t>(256, std::min<int64_t>(2 * B, 1 << 16));        // candidates per round
   const size_t nx = (size_t)(D.N + 1) * D.nq;
   TmpBuf tb;
   double* dq0 = tb.alloc<double>(nround * D.nq); double* du = tb.alloc<double>(nround * D.n); double* dq = tb.alloc<double>(nround * nx);
   int32_t* dok = tb.alloc<int32_t>(nround); int32_t* dcol = tb.alloc<int32_t>(nround); int32_t* dpos = tb.alloc<int32_t>(nround); int32_t* dcnt = tb.alloc<int32_t>(1);
   if (!dq0 || !du || !dq || !dok || !dcol || !dpos || !dcnt) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  { int rcu = upload_problem(h); if (rcu) return rcu; }
-  int64_t have = 0;
-  unsigned long long c0 = 0;
-  for (int round = 0; have < B; round++) {
-    if (round > 10000) { h->err = "sampler did not produce enough collision-free scenarios"; return DGSQP_E_ARG; }
-    hipLaunchKernelGGL(dg_sample_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, dq0, dok);
-    HIPCHK(h, hipGetLastError());
-    if (merge) {
-      hipLaunchKernelGGL(dg_sample_zero_rollout_kernel, dim3((unsigned)((nround * D.M + 255) / 256)), dim3(256), 0, h->stream, nround, dq0, dq);
-    } else {
-      int grid = (int)((nround * D.M + DG_BLOCK - 1) / DG_BLOCK);
-      if (grid > 4 * h->num_cu) grid = 4 * h->num_cu;
-      hipLaunchKernelGGL(dg_pid_kernel, dim3(grid), dim3(DG_BLOCK), (size_t)D.L.scr * sizeof(double), h->stream, nround, dq0, *pid, du, dq);
+  // (the rounds belong together: one critical section around all of them)
+  const int rcs = run_sync(h, [&]() -> int {
+    int64_t have = 0;
+    unsigned long long c0 = 0;
+    for (int round = 0; have < B; round++) {
+      if (round > 10000) { h->err = "sampler did not produce enough collision-free scenarios"; return DGSQP_E_ARG; }
+      hipLaunchKernelGGL(dg_sample_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, dq0, dok);
+      HIPCHK(h, hipGetLastError());
+      if (merge) {
+        hipLaunchKernelGGL(dg_sample_zero_rollout_kernel, dim3((unsigned)((nround * D.M + 255) / 256)), dim3(256), 0, h->stream, nround, dq0, dq);
+      } else {
+        int grid = (int)((nround * D.M + DG_BLOCK - 1) / DG_BLOCK);
+        if (grid > 4 * h->num_cu) grid = 4 * h->num_cu;
+        hipLaunchKernelGGL(dg_pid_kernel, dim3(grid), dim3(DG_BLOCK), (size_t)D.L.scr * sizeof(double), h->stream, nround, dq0, *pid, du, dq);
+      }
+      HIPCHK(h, hipGetLastError());
+      hipLaunchKernelGGL(dg_collide_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, dq, dcol);
+      hipLaunchKernelGGL(dg_sample_scan_kernel, dim3(1), dim3(1024), 0, h->stream, nround, dok, dcol, dpos, dcnt);
+      hipLaunchKernelGGL(dg_sample_gather_kernel, dim3(1024), dim3(128), 0, h->stream, nround, have, B, dpos, dq0, merge ? (const double*)nullptr : du, d_x0, d_uws);
+      HIPCHK(h, hipGetLastError());
+      int32_t cnt = 0;
+      HIPCHK(h, hipMemcpyAsync(&cnt, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if (have + cnt >= B && candidates) {
+        // index after the (B - have)-th accepted candidate of this round
+        std::vector<int32_t> pos((size_t)nround);
+        HIPCHK(h, hipMemcpy(pos.data(), dpos, sizeof(int32_t) * nround, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < nround; i++) if (pos[i] == (int32_t)(B - have - 1)) { *candidates = (int64_t)(c0 + i + 1); break; }
+      }
+      have += cnt;
+      c0 += (unsigned long long)nround;
     }
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(dg_collide_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, dq, dcol);
-    hipLaunchKernelGGL(dg_sample_scan_kernel, dim3(1), dim3(1024), 0, h->stream, nround, dok, dcol, dpos, dcnt);
-    hipLaunchKernelGGL(dg_sample_gather_kernel, dim3(1024), dim3(128), 0, h->stream, nround, have, B, dpos, dq0, merge ? (const double*)nullptr : du, h->d_x0, h->d_uws);
-    HIPCHK(h, hipGetLastError());
-    int32_t cnt = 0;
-    HIPCHK(h, hipMemcpyAsync(&cnt, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (have + cnt >= B && candidates) {
-      // index after the (B - have)-th accepted candidate of this round
-      std::vector<int32_t> pos((size_t)nround);
-      HIPCHK(h, hipMemcpy(pos.data(), dpos, sizeof(int32_t) * nround, hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < nround; i++) if (pos[i] == (int32_t)(B - have - 1)) { *candidates = (int64_t)(c0 + i + 1); break; }
-    }
-    have += cnt;
-    c0 += (unsigned long long)nround;
-  }
-  if (x0_out) HIPCHK(h, hipMemcpy(x0_out, h->d_x0, sizeof(double) * B * D.nq, hipMemcpyDeviceToHost));
-  if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, h->d_uws, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
+    return DGSQP_OK;
+  });
+  if (rcs) return rcs;
+  if (x0_out) HIPCHK(h, hipMemcpy(x0_out, d_x0, sizeof(double) * B * D.nq, hipMemcpyDeviceToHost));
+  if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, d_uws, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
   h->B = stage ? B : 0;          // (the staging buffers were used either way: without `stage` nothing is left staged)
   return DGSQP_OK;
 }
@@ -1248,9 +1274,7 @@ int dgsqp_qp_batch_info(dgsqp_handle_t h, int64_t B, const double* x0, const dou
   HIPCHK(h, hipSetDevice(h->device));
   const DgProb& D = h->hp;
   const int grid = grid_for(h, B);
-  int rc = wait_idle(h);
-  if (rc) return rc;
-  rc = ensure_ws(h, (size_t)grid);
+  int rc = idle_with_ws(h, B);
   if (rc) return rc;
   TmpBuf tb;
   const size_t n = D.n, nc = D.nc;
@@ -1262,13 +1286,12 @@ int dgsqp_qp_batch_info(dgsqp_handle_t h, int64_t B, const double* x0, const dou
   HIPCHK(h, hipMemcpy(dx0, x0, sizeof(double) * B * D.nq, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(du, u, sizeof(double) * B * n, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(dl, l, sizeof(double) * B * nc, hipMemcpyHostToDevice));
-  std::unique_lock<std::mutex> game_lock(g_reg_mutex);
-  { int rcu = upload_problem(h); if (rcu) return rcu; }
-  h->in_flight = true;
-  hipLaunchKernelGGL(dg_qp_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, ddu, dlh, dQ, df, dinfo, h->ws);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->in_flight = false;
+  rc = run_sync(h, [&]() -> int {
+    hipLaunchKernelGGL(dg_qp_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, ddu, dlh, dQ, df, dinfo, h->ws);
+    HIPCHK(h, hipGetLastError());
+    return DGSQP_OK;
+  });
+  if (rc) return rc;
   if (du_out) HIPCHK(h, hipMemcpy(du_out, ddu, sizeof(double) * B * n, hipMemcpyDeviceToHost));
   if (lhat) HIPCHK(h, hipMemcpy(lhat, dlh, sizeof(double) * B * nc, hipMemcpyDeviceToHost));
   if (Qpd) HIPCHK(h, hipMemcpy(Qpd, dQ, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
@@ -1332,8 +1355,9 @@ int dgsqp_gather_stats(dgsqp_handle_t h, int64_t B_pad, dgsqp_stat_record_t* out
     HIPCHK(h, hipMalloc(&c->d_all, sizeof(dgsqp_stat_record_t) * B_pad * c->world));
     c->rec_cap = B_pad;
   }
+  const SolveOutPtrs O = h->staged.out(rec_count_batch(h->B));      // (the kernel takes the five arrays it packs one by one)
   hipLaunchKernelGGL(dg_pack_stats_kernel, dim3((unsigned)((B_pad + 255) / 256)), dim3(256), 0, h->stream, h->B, B_pad, h->hp.M, c->rank,
-                     h->d_status, h->d_iters, h->d_qps, h->d_cond, h->d_cost, c->d_rec);
+                     O.status, O.iters, O.qp_solves, O.cond, O.cost, c->d_rec);
   HIPCHK(h, hipGetLastError());
   NCCLCHK(h, g_rccl.AllGather(c->d_rec, c->d_all, sizeof(dgsqp_stat_record_t) * B_pad, ncclChar, c->comm, h->stream));
   HIPCHK(h, hipMemcpyAsync(out, c->d_all, sizeof(dgsqp_stat_record_t) * B_pad * c->world, hipMemcpyDeviceToHost, h->stream));

@@ -254,6 +254,40 @@ def _build_params_v2(params: DGSQPV2Params, eig_floor, snap_active_bounds, lsqr_
     return p
 
 
+def agent_major(u_tm: np.ndarray, N: int, num_ua_d) -> np.ndarray:
+    """[..., N, n_u] time-major joint inputs -> [..., n] agent-major decision vector (DGSQP.py:271-281)."""
+    parts, si = [], 0
+    for nu in num_ua_d:
+        parts.append(u_tm[..., :, si:si + nu].reshape(*u_tm.shape[:-2], N * nu))
+        si += nu
+    return np.concatenate(parts, axis=-1)
+
+
+def coerce_inputs(x0, u_ws, dtype, N: int, n_q: int, num_ua_d):
+    """What every batched entry point makes of its ``(x0, u_ws)``: C-contiguous ``[B, n_q]`` and agent-major ``[B, n]`` arrays of ``dtype``.
+    ``u_ws`` is [B, N, n_u] (time-major, as ``set_warm_start``) or [B, n] already.  Needs the game's dimensions only: the horizon, the joint
+    state size and every agent's input count."""
+    n_u = sum(num_ua_d)
+    x0 = np.ascontiguousarray(x0, dtype=dtype)
+    B = x0.shape[0]
+    u_ws = np.asarray(u_ws, dtype=dtype)
+    if u_ws.ndim == 3:
+        if u_ws.shape[1:] != (N, n_u):
+            raise RuntimeError('Warm start state sequence of shape (%i,%i) is incompatible with required shape (%i,%i)'
+                               % (u_ws.shape[1], u_ws.shape[2], N, n_u))
+        u_ws = agent_major(u_ws, N, num_ua_d)
+    u_ws = np.ascontiguousarray(u_ws)
+    if x0.shape != (B, n_q) or u_ws.shape != (B, N * n_u):
+        raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
+    return x0, u_ws
+
+
+def _record_ptrs(out: dict, fptr=_ffi.dptr) -> tuple:
+    """The eight result arguments of the C-ABI, in its order, from a record dictionary (``None`` entries become NULL)."""
+    return (fptr(out['u']), fptr(out['l']), fptr(out['x']), _ffi.iptr(out['status']), _ffi.iptr(out['num_iters']),
+            _ffi.iptr(out['qp_solves']), fptr(out['cond']), fptr(out['cost']))
+
+
 def solve_batches(solvers, batches) -> list:
     """Several Monte-Carlo batches of the SAME game and size in ONE launch (``dgsqp_launch_staged_group``): ``solvers`` are DGSQP
     objects of that game (one per batch: every batch keeps its own device buffers), ``batches`` the matching ``(x0, u_ws)`` pairs as
@@ -269,15 +303,8 @@ def solve_batches(solvers, batches) -> list:
         if isinstance(bt, (int, np.integer)):          # already staged on the device (DGSQP.sample_batch(..., stage=True)): just its size
             staged.append(int(bt))
             continue
-        x0, u_ws = bt
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        u_ws = np.asarray(u_ws, dtype=np.float64)
-        if u_ws.ndim == 3:
-            u_ws = s._to_agent_major(u_ws)
-        u_ws = np.ascontiguousarray(u_ws)
+        x0, u_ws = s._inputs(*bt)
         B = x0.shape[0]
-        if x0.shape != (B, s.n_q) or u_ws.shape != (B, s.n):
-            raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
         if lib.dgsqp_stage_inputs(s._h, B, _ffi.dptr(x0), _ffi.dptr(u_ws)) != 0:
             raise RuntimeError('dgsqp_stage_inputs failed: ' + lib.dgsqp_last_error(s._h).decode())
         staged.append(B)
@@ -298,18 +325,10 @@ def solve_batches(solvers, batches) -> list:
     for s, B in zip(solvers, staged):
         if lib.dgsqp_wait(s._h, C.byref(tm)) != 0:
             raise RuntimeError('dgsqp_wait failed: ' + lib.dgsqp_last_error(s._h).decode())
-        out = dict(u=np.empty((B, s.n)), l=np.empty((B, s.n_c_total)), x=np.empty((B, s.N + 1, s.n_q)), status=np.empty(B, np.int32),
-                   num_iters=np.empty(B, np.int32), qp_solves=np.empty(B, np.int32), cond=np.empty((B, 3)), cost=np.empty((B, s.M)))
-        rc = lib.dgsqp_fetch_results(s._h, _ffi.dptr(out['u']), _ffi.dptr(out['l']), _ffi.dptr(out['x']), _ffi.iptr(out['status']),
-                                     _ffi.iptr(out['num_iters']), _ffi.iptr(out['qp_solves']), _ffi.dptr(out['cond']), _ffi.dptr(out['cost']))
-        if rc != 0:
+        out = s._records((B,))
+        if lib.dgsqp_fetch_results(s._h, *_record_ptrs(out)) != 0:
             raise RuntimeError('dgsqp_fetch_results failed: ' + lib.dgsqp_last_error(s._h).decode())
-        out['time'] = time.time() - t0
-        out['kernel_ms'] = tm.kernel_ms
-        out['msg'] = [_ffi.STATUS_MSG[v] for v in out['status']]
-        out['converged'] = out['status'] <= 1
-        out['u_pred'] = s._to_time_major(out['u'])
-        outs.append(out)
+        outs.append(s._finish(out, t0, tm))
     return outs
 
 
@@ -421,11 +440,7 @@ class DGSQP(AbstractSolver):
     # ---- layout helpers (DGSQP.py:271-281, :477-482) ------------------------------------------
     def _to_agent_major(self, u_tm: np.ndarray) -> np.ndarray:
         """[..., N, n_u] time-major joint inputs -> [..., n] agent-major decision vector."""
-        parts, si = [], 0
-        for nu in self.num_ua_d:
-            parts.append(u_tm[..., :, si:si + nu].reshape(*u_tm.shape[:-2], self.N * nu))
-            si += nu
-        return np.concatenate(parts, axis=-1)
+        return agent_major(u_tm, self.N, self.num_ua_d)
 
     def _to_time_major(self, u_am: np.ndarray) -> np.ndarray:
         parts, si = [], 0
@@ -444,40 +459,47 @@ class DGSQP(AbstractSolver):
         self.u_ws = self._to_agent_major(np.asarray(u_ws, dtype=float))
         self.l_ws = l_ws
 
+    # ---- batched entry points: shared pieces ---------------------------------------------------
+    def _inputs(self, x0, u_ws, dtype=np.float64):
+        return coerce_inputs(x0, u_ws, dtype, self.N, self.n_q, self.num_ua_d)
+
+    def _records(self, lead: tuple, ftype=np.float64, predictions: bool = True) -> dict:
+        """Uninitialised record arrays of leading shape ``lead`` ([B], or [T, B] step-major) for the library to fill."""
+        return dict(u=np.empty(lead + (self.n,), ftype),
+                    l=np.empty(lead + (self.n_c_total,), ftype) if predictions else None,
+                    x=np.empty(lead + (self.N + 1, self.n_q), ftype) if predictions else None,
+                    status=np.empty(lead, np.int32), num_iters=np.empty(lead, np.int32), qp_solves=np.empty(lead, np.int32),
+                    cond=np.empty(lead + (3,), ftype), cost=np.empty(lead + (self.M,), ftype))
+
+    def _finish(self, out: dict, t0: float, tm: _ffi.TimingT) -> dict:
+        """What every result dictionary ends with, from its ``status`` [B] or [B, T] and ``u``."""
+        name = lambda s: 'not_run' if s == _ffi.NOT_RUN else _ffi.STATUS_MSG[s]
+        st = out['status']
+        out['time'] = time.time() - t0
+        out['kernel_ms'] = tm.kernel_ms
+        out['msg'] = [name(s) for s in st] if st.ndim == 1 else [[name(s) for s in row] for row in st]
+        out['converged'] = (st >= 0) & (st <= 1)
+        out['u_pred'] = self._to_time_major(out['u'])
+        return out
+
     # ---- batched entry point -------------------------------------------------------------------
     def solve_batch(self, x0: np.ndarray, u_ws: np.ndarray, dtype=np.float64) -> dict:
         """B independent ``solve()`` calls.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] (time-major,
         as ``set_warm_start``) or [B, n] (agent-major).  ``dtype=np.float32``: single-precision arrays at the boundary
         (``dgsqp_solve_batch_f32``: widened on the device, fp64 solve, results rounded to fp32)."""
-        if np.dtype(dtype) == np.float32:
-            return self._solve_batch_f32(x0, u_ws)
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        f32 = np.dtype(dtype) == np.float32
+        ftype = np.float32 if f32 else np.float64
+        fptr = (lambda a: a.ctypes.data_as(C.POINTER(C.c_float))) if f32 else _ffi.dptr
+        what = 'dgsqp_solve_batch_f32' if f32 else 'dgsqp_solve_batch'
+        x0, u_ws = self._inputs(x0, u_ws, ftype)
         B = x0.shape[0]
-        u_ws = np.asarray(u_ws, dtype=np.float64)
-        if u_ws.ndim == 3:
-            if u_ws.shape[1:] != (self.N, self.n_u):
-                raise RuntimeError('Warm start state sequence of shape (%i,%i) is incompatible with required shape (%i,%i)'
-                                   % (u_ws.shape[1], u_ws.shape[2], self.N, self.n_u))
-            u_ws = self._to_agent_major(u_ws)
-        u_ws = np.ascontiguousarray(u_ws)
-        if x0.shape != (B, self.n_q) or u_ws.shape != (B, self.n):
-            raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
-        out = dict(u=np.empty((B, self.n)), l=np.empty((B, self.n_c_total)), x=np.empty((B, self.N + 1, self.n_q)),
-                   status=np.empty(B, np.int32), num_iters=np.empty(B, np.int32), qp_solves=np.empty(B, np.int32),
-                   cond=np.empty((B, 3)), cost=np.empty((B, self.M)))
+        out = self._records((B,), ftype)
         tm = _ffi.TimingT()
         t0 = time.time()
-        rc = self._lib.dgsqp_solve_batch(self._h, B, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(out['u']), _ffi.dptr(out['l']),
-                                         _ffi.dptr(out['x']), _ffi.iptr(out['status']), _ffi.iptr(out['num_iters']),
-                                         _ffi.iptr(out['qp_solves']), _ffi.dptr(out['cond']), _ffi.dptr(out['cost']), C.byref(tm))
+        rc = getattr(self._lib, what)(self._h, B, fptr(x0), fptr(u_ws), *_record_ptrs(out, fptr), C.byref(tm))
         if rc != 0:
-            raise RuntimeError(f'dgsqp_solve_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
-        out['time'] = time.time() - t0
-        out['kernel_ms'] = tm.kernel_ms
-        out['msg'] = [_ffi.STATUS_MSG[s] for s in out['status']]
-        out['converged'] = out['status'] <= 1
-        out['u_pred'] = self._to_time_major(out['u'])
-        return out
+            raise RuntimeError(f'{what} failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
+        return self._finish(out, t0, tm)
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
                    keep_predictions: bool = False) -> dict:
@@ -495,72 +517,26 @@ class DGSQP(AbstractSolver):
         T = int(steps)
         if T < 1:
             raise ValueError(f'steps must be at least 1, got {steps}')
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x0, u_ws = self._inputs(x0, u_ws)
         B = x0.shape[0]
-        u_ws = np.asarray(u_ws, dtype=np.float64)
-        if u_ws.ndim == 3:
-            if u_ws.shape[1:] != (self.N, self.n_u):
-                raise RuntimeError('Warm start state sequence of shape (%i,%i) is incompatible with required shape (%i,%i)'
-                                   % (u_ws.shape[1], u_ws.shape[2], self.N, self.n_u))
-            u_ws = self._to_agent_major(u_ws)
-        u_ws = np.ascontiguousarray(u_ws)
-        if x0.shape != (B, self.n_q) or u_ws.shape != (B, self.n):
-            raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
         w = None
         if disturbance is not None:
             w = np.asarray(disturbance, dtype=np.float64)
             if w.shape != (B, T, self.n_q):
                 raise ValueError(f'disturbance must be [B, steps, n_q] = {(B, T, self.n_q)}, got {w.shape}')
             w = np.ascontiguousarray(w.transpose(1, 0, 2))          # the library's arrays are step-major
-        nc = self.n_c_total
-        sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), u=np.empty((T, B, self.n)),
-                  l=np.empty((T, B, nc)) if keep_predictions else None, x=np.empty((T, B, self.N + 1, self.n_q)) if keep_predictions else None,
-                  status=np.empty((T, B), np.int32), num_iters=np.empty((T, B), np.int32), qp_solves=np.empty((T, B), np.int32),
-                  cond=np.empty((T, B, 3)), cost=np.empty((T, B, self.M)))
+        sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), **self._records((T, B), predictions=keep_predictions))
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
         t0 = time.time()
         rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
-                                               _ffi.dptr(sm['u']), _ffi.dptr(sm['l']), _ffi.dptr(sm['x']), _ffi.iptr(sm['status']),
-                                               _ffi.iptr(sm['num_iters']), _ffi.iptr(sm['qp_solves']), _ffi.dptr(sm['cond']), _ffi.dptr(sm['cost']),
-                                               _ffi.iptr(steps_done), C.byref(tm))
+                                               *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
         if rc != 0:
             raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
         out['steps_done'] = steps_done
-        out['time'] = time.time() - t0
-        out['kernel_ms'] = tm.kernel_ms
-        out['msg'] = [['not_run' if s == _ffi.NOT_RUN else _ffi.STATUS_MSG[s] for s in row] for row in out['status']]
-        out['converged'] = (out['status'] >= 0) & (out['status'] <= 1)
-        out['u_pred'] = self._to_time_major(out['u'])
+        self._finish(out, t0, tm)
         out['u_applied'] = np.ascontiguousarray(out['u_pred'][:, :, 0])
-        return out
-
-    def _solve_batch_f32(self, x0, u_ws) -> dict:
-        x0 = np.ascontiguousarray(x0, dtype=np.float32)
-        B = x0.shape[0]
-        u_ws = np.asarray(u_ws, dtype=np.float32)
-        if u_ws.ndim == 3:
-            u_ws = self._to_agent_major(u_ws)
-        u_ws = np.ascontiguousarray(u_ws, dtype=np.float32)
-        if x0.shape != (B, self.n_q) or u_ws.shape != (B, self.n):
-            raise RuntimeError(f'bad batch shapes x0 {x0.shape} u_ws {u_ws.shape}')
-        f32 = np.float32
-        out = dict(u=np.empty((B, self.n), f32), l=np.empty((B, self.n_c_total), f32), x=np.empty((B, self.N + 1, self.n_q), f32),
-                   status=np.empty(B, np.int32), num_iters=np.empty(B, np.int32), qp_solves=np.empty(B, np.int32),
-                   cond=np.empty((B, 3), f32), cost=np.empty((B, self.M), f32))
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        tm = _ffi.TimingT()
-        t0 = time.time()
-        rc = self._lib.dgsqp_solve_batch_f32(self._h, B, fp(x0), fp(u_ws), fp(out['u']), fp(out['l']), fp(out['x']), _ffi.iptr(out['status']),
-                                             _ffi.iptr(out['num_iters']), _ffi.iptr(out['qp_solves']), fp(out['cond']), fp(out['cost']), C.byref(tm))
-        if rc != 0:
-            raise RuntimeError(f'dgsqp_solve_batch_f32 failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
-        out['time'] = time.time() - t0
-        out['kernel_ms'] = tm.kernel_ms
-        out['msg'] = [_ffi.STATUS_MSG[s] for s in out['status']]
-        out['converged'] = out['status'] <= 1
-        out['u_pred'] = self._to_time_major(out['u'])
         return out
 
     def set_trace(self, pairs_per_scenario: int):

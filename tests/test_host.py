@@ -113,6 +113,49 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_ffi.EXPORTED_SYMBOLS)
     for name in declared:
         assert hasattr(lib, name), name
+    loaded = _ffi.load_library()
+    for name in _ffi.EXPORTED_SYMBOLS:                # ... and the loader gives every one of them its signature
+        assert getattr(loaded, name).argtypes is not None, name
+
+
+def test_batch_input_coercion():
+    """solver.coerce_inputs, with kb_chicane_N15's dimensions (N = 15, n_q = 12, two agents of two inputs): [B, N, n_u] and [B, n] warm starts
+    become C-contiguous agent-major [B, n] arrays of the requested dtype; a 3-D warm start of any other trailing shape is refused."""
+    from dgsqp_amd.solver import coerce_inputs
+    N, n_q, num_ua_d, B = 15, 12, [2, 2], 3
+    rng = np.random.default_rng(0)
+    x0, u_tm = rng.standard_normal((B, n_q)), rng.standard_normal((B, N, 4))
+    for bad in (np.zeros((B, N, 5)), np.zeros((B, N + 1, 4))):
+        with pytest.raises(RuntimeError, match=r'Warm start state sequence of shape \(\d+,\d+\) is incompatible with required shape \(15,4\)'):
+            coerce_inputs(x0, bad, np.float64, N, n_q, num_ua_d)
+    with pytest.raises(RuntimeError, match='bad batch shapes'):
+        coerce_inputs(x0, np.zeros((B, N * 4 + 1)), np.float64, N, n_q, num_ua_d)
+    for dtype in (np.float64, np.float32):
+        for u_in in (u_tm, agent_major(u_tm), np.asfortranarray(u_tm), u_tm.tolist()):
+            a, b = coerce_inputs(np.asfortranarray(x0), u_in, dtype, N, n_q, num_ua_d)
+            assert a.dtype == b.dtype == dtype and a.flags.c_contiguous and b.flags.c_contiguous
+            assert a.shape == (B, n_q) and b.shape == (B, N * 4)
+            assert np.array_equal(a, x0.astype(dtype)) and np.array_equal(b, agent_major(u_tm).astype(dtype))
+
+
+def test_every_batched_entry_point_coerces_its_inputs(monkeypatch):
+    """solve_batch (both dtypes), step_batch and solve_batches all pass their (x0, u_ws) through solver.coerce_inputs: with that function
+    replaced by one that raises, each of them raises before it touches the library (the objects have no handle)."""
+    from dgsqp_amd import solver
+
+    class Reached(Exception):
+        pass
+
+    def raiser(*a, **k):
+        raise Reached
+    monkeypatch.setattr(solver, 'coerce_inputs', raiser)
+    s = solver.DGSQP.__new__(solver.DGSQP)
+    s.N, s.n_q, s.num_ua_d, s._lib, s._h = 15, 12, [2, 2], None, None
+    x0, u_ws = np.zeros((2, 12)), np.zeros((2, 15, 4))
+    for call in (lambda: s.solve_batch(x0, u_ws), lambda: s.solve_batch(x0, u_ws, dtype=np.float32), lambda: s.step_batch(x0, u_ws, 2),
+                 lambda: solver.solve_batches([s], [(x0, u_ws)])):
+        with pytest.raises(Reached):
+            call()
 
 
 def test_half_arena_build_exports_and_plans():
