@@ -195,15 +195,6 @@ dg_qp_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restrict__
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// Overlapping launches on several handles (bench.py --pipeline) need one hardware queue per stream; the HIP runtime creates
-// 4 by default and reads this variable when it initialises (first HIP call), so set it when the library is loaded unless
-// the user already chose a value.
-namespace {
-struct DgEnvInit {
-  DgEnvInit() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-} dg_env_init;
-}  // namespace
-
 // The per-scenario arrays of a solve, stated once: every host function that allocates, fills, hands out or copies them walks this
 // table.  The eight records from DG_U on are in the order of the C-ABI's result parameters (include/dgsqp.h).
 enum DgRec { DG_Q, DG_UWS, DG_W, DG_U, DG_L, DG_X, DG_STATUS, DG_ITERS, DG_QPS, DG_COND, DG_COST, DG_DONE, DG_REC_COUNT };
@@ -273,7 +264,8 @@ struct dgsqp_solver {
   int device = 0;
   DgProb hp;
   DgProb* dp = nullptr;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;          // the handle's own: staging, result copies, the synchronous hooks and closed-loop launches
+  hipStream_t launch_stream = nullptr;   // what the handle's launch in flight (or its last one) runs on: a pool stream (launch_solve) or `stream`
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int num_cu = 0, wg_per_cu = 1, max_grid = 0, launched_grid = 0;
   size_t lds_bytes = 0;
@@ -380,15 +372,42 @@ struct DgParkPool {
   unsigned long long owner_gen = 0;         // ... and which of its launches
 };
 DgParkPool g_park[64];
+// Launch streams: dg_solve_kernel launches do not run on their handles' streams but on a small pool of streams per device, taken
+// round robin in launch order.  The runtime spreads streams over GPU_MAX_HW_QUEUES hardware queues (4 unless set) in creation order,
+// and a kernel waits for everything before it in its hardware queue: with one stream per handle, which launches shared a queue --
+// and then ran one after the other, tail included -- depended on which handles led them.  The pool is created before the first
+// handle's stream of the device, so its K = min(queues, 8) streams sit on different queues; launch j shares a stream with launch
+// j - K alone.  It lives while the device has a handle.
+struct DgLaunchStreams {
+  std::vector<hipStream_t> streams;
+  unsigned long long next = 0;      // launches handed a stream so far
+};
+DgLaunchStreams g_launch_streams[64];
 }  // namespace
-// the stream the handle's solve in flight runs on: its own, or the leader's for a member of a grouped launch
-static hipStream_t active_stream(const dgsqp_solver* h) { return h->group_leader ? h->group_leader->stream : h->stream; }
+static int launch_stream_count() {
+  const char* e = getenv("GPU_MAX_HW_QUEUES");
+  char* end = nullptr;
+  const long q = e ? strtol(e, &end, 10) : 0;
+  return (int)std::min<long>(e && end != e && *end == '\0' && q >= 1 ? q : 4, 8);
+}
+// Call with g_reg_mutex held and the device current.  The pool of h's device, created on demand.
+static int ensure_launch_streams(dgsqp_solver* h) {
+  DgLaunchStreams& pool = g_launch_streams[h->device & 63];
+  for (int k = (int)pool.streams.size(), K = launch_stream_count(); k < K; k++) {
+    hipStream_t s = nullptr;
+    HIPCHK(h, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    pool.streams.push_back(s);
+  }
+  return DGSQP_OK;
+}
+// the stream the handle's solve in flight runs on: its own launch's, or the leader's for a member of a grouped launch
+static hipStream_t active_stream(const dgsqp_solver* h) { return (h->group_leader ? h->group_leader : h)->launch_stream; }
 // kernel time of h's completed launch (events ev[0], ev[1] of the stream it ran on)
 static void record_last_ms(dgsqp_solver* h, dgsqp_solver* leader) {
   float ms = 0.0f;
   if (h->launched_grid > 0 && hipEventElapsedTime(&ms, leader->ev[0], leader->ev[1]) == hipSuccess) h->last_ms = ms;
 }
-// The members of a grouped launch led by L whose kernel has completed (L's stream is synchronised): they leave the group
+// The members of a grouped launch led by L whose kernel has completed (L's launch stream is synchronised): they leave the group
 // with the kernel time of THAT launch.  Called before L's events are re-recorded by its next launch, so that a member's
 // later dgsqp_wait / dgsqp_finished never looks at the events of an unrelated kernel.
 static void release_members(dgsqp_solver* L) {
@@ -398,7 +417,7 @@ static void release_members(dgsqp_solver* L) {
 static int wait_idle(dgsqp_solver* h) {
   if (h->in_flight) {
     dgsqp_solver* L = h->group_leader ? h->group_leader : h;
-    HIPCHK(h, hipStreamSynchronize(L->stream));
+    HIPCHK(h, hipStreamSynchronize(L->launch_stream));
     record_last_ms(h, L);
     h->in_flight = false;
     h->group_leader = nullptr;
@@ -443,11 +462,11 @@ static bool coop_for_launch(dgsqp_solver* h, int grid) {
   if (chain < env_int("DGSQP_COOP_MIN_CHAIN", 0)) return false;
   return h->coop_mode == 2 || (h->coop_mode == 1 && h->coop_next_sync);
 }
-// Deferral of long scenarios for the cooperative launch about to be enqueued on h's stream (DgPark, dgsqp_device.h): a quarter of
+// Deferral of long scenarios for the cooperative launch about to be enqueued on `stream` (DgPark, dgsqp_device.h): a quarter of
 // the launch's scenarios may be deferred at a time (bounded by 16 GB of slots).  Off for launches that give every scenario its own
 // workgroup and while logs are recorded; DG-SQP v2 only after an explicit dgsqp_set_deferral (round 4).  (development knobs: DGSQP_DEFER = 0 switches it off, DGSQP_DEFER_MIN_IT,
 // DGSQP_DEFER_FACTOR override dgsqp_set_deferral.)
-static int park_for_launch(dgsqp_solver* h, bool coop, int grid, int64_t total, DgPark* out) {
+static int park_for_launch(dgsqp_solver* h, hipStream_t stream, bool coop, int grid, int64_t total, DgPark* out) {
   memset(out, 0, sizeof(*out));
   h->park_last_cap = 0;
   int min_it = h->defer_min_it;
@@ -495,7 +514,7 @@ static int park_for_launch(dgsqp_solver* h, bool coop, int grid, int64_t total, 
     pool.slots = slots; pool.slot_doubles = slot;
   }
   if (cap > pool.slots) cap = pool.slots;
-  HIPCHK(h, hipMemsetAsync(pool.entries, 0, sizeof(DgParkEntry) * cap, h->stream));
+  HIPCHK(h, hipMemsetAsync(pool.entries, 0, sizeof(DgParkEntry) * cap, stream));
   pool.owner = h; pool.owner_gen = h->launch_gen + 1;      // (the launch about to be enqueued)
   h->park_last_cap = cap;
   out->entries = pool.entries; out->store = pool.store; out->cap = (unsigned int)cap;
@@ -537,8 +556,10 @@ static int idle_with_ws(dgsqp_solver* h, int64_t B) {
   return rc ? rc : ensure_ws(h, (size_t)grid_for(h, B));
 }
 
-// What every launch that re-records ev[0] / ev[1] on h's stream begins with.  Takes g_reg_mutex: the caller keeps `lock` until its
-// kernel is enqueued and the handle marked in flight (upload_problem's contract).
+// What every launch that re-records ev[0] / ev[1] begins with.  Takes g_reg_mutex: the caller keeps `lock` until its kernel is
+// enqueued and the handle marked in flight (upload_problem's contract).  The handle is idle (its callers waited for its last launch),
+// and the host waits here for what is queued on the handle's OWN stream -- staging copies, the sampler, the fp32 widening, log
+// set-up --, so the kernel may go to any stream; no launch stream is waited for: that would stall the host behind an older launch.
 static int begin_launch(dgsqp_solver* h, std::unique_lock<std::mutex>& lock) {
   lock = std::unique_lock<std::mutex>(g_reg_mutex);
   if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "hipStreamSynchronize failed"; return DGSQP_E_DEVICE; }
@@ -554,6 +575,7 @@ static int run_sync(dgsqp_solver* h, F enqueue) {
     std::unique_lock<std::mutex> game_lock(g_reg_mutex);
     { const int rc = upload_problem(h); if (rc) return rc; }
     { const int rc = enqueue(); if (rc) return rc; }
+    h->launch_stream = h->stream;
     h->in_flight = true;       // (the sampler's enqueue waits for every round itself: for that hook this mark and the wait below do nothing)
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -596,31 +618,37 @@ static int log_fetch(dgsqp_solver* h, DgLog& g, double* out, int64_t capacity_do
 }
 
 // The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
-// L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.
+// L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.  Everything it enqueues goes
+// to the next launch stream of the device's pool, which L records: waits, queries and timing follow that record.
 static int launch_solve(dgsqp_solver* L, int64_t total, const DgBatch* group, int count) {
   const int grid = grid_for(L, total);
   std::unique_lock<std::mutex> game_lock;
   { const int rc = begin_launch(L, game_lock); if (rc) return rc; }
+  { const int rc = ensure_launch_streams(L); if (rc) return rc; }
+  DgLaunchStreams& pool = g_launch_streams[L->device & 63];
+  const hipStream_t stream = pool.streams[pool.next % pool.streams.size()];
   double *trace = nullptr, *itlog = nullptr;      // (a grouped launch has neither: its caller refuses handles that record logs)
   { const int rc = log_for_launch(L, L->trace, total, &trace); if (rc) return rc; }
   { const int rc = log_for_launch(L, L->itlog, total, &itlog); if (rc) return rc; }
-  if (group) HIPCHK(L, hipMemcpyAsync(L->d_group, group, sizeof(DgBatch) * count, hipMemcpyHostToDevice, L->stream));
-  HIPCHK(L, hipMemsetAsync(L->ticket, 0, sizeof(unsigned long long), L->stream));
+  if (group) HIPCHK(L, hipMemcpyAsync(L->d_group, group, sizeof(DgBatch) * count, hipMemcpyHostToDevice, stream));
+  HIPCHK(L, hipMemsetAsync(L->ticket, 0, sizeof(unsigned long long), stream));
   const bool coop = coop_for_launch(L, grid);
-  if (coop) HIPCHK(L, hipMemsetAsync(L->d_coop, 0, L->coop_bytes, L->stream));
+  if (coop) HIPCHK(L, hipMemsetAsync(L->d_coop, 0, L->coop_bytes, stream));
   DgPark park;
-  { const int rc = park_for_launch(L, coop, grid, total, &park); if (rc) return rc; }
-  HIPCHK(L, hipEventRecord(L->ev[0], L->stream));
+  { const int rc = park_for_launch(L, stream, coop, grid, total, &park); if (rc) return rc; }
+  HIPCHK(L, hipEventRecord(L->ev[0], stream));
   *L->drained_host = 0u;
-  hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), L->lds_bytes, L->stream, L->dp, L->B, L->staged.dbl(DG_Q), L->staged.dbl(DG_UWS),
+  hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), L->lds_bytes, stream, L->dp, L->B, L->staged.dbl(DG_Q), L->staged.dbl(DG_UWS),
                      L->staged.out(rec_count_batch(L->B)), L->ws, L->ticket, trace, L->trace.cap, L->drained_dev, itlog, L->itlog.cap,
                      group ? (const DgBatch*)L->d_group : (const DgBatch*)nullptr, group ? count : 0,
                      coop ? L->d_coop : (DgCoop*)nullptr, L->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park);
   HIPCHK(L, hipGetLastError());
+  pool.next++;
+  L->launch_stream = stream;
   L->launch_gen++;
   L->launched_grid = grid;
   L->in_flight = true;       // (only now: an error return above leaves the handle idle)
-  HIPCHK(L, hipEventRecord(L->ev[1], L->stream));
+  HIPCHK(L, hipEventRecord(L->ev[1], stream));
   return DGSQP_OK;
 }
 
@@ -664,7 +692,11 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipGetDeviceProperties(&p, device) != hipSuccess) return fail("hipGetDeviceProperties failed");
   h->num_cu = p.multiProcessorCount;
   h->lds_bytes = (size_t)h->hp.L.total * sizeof(double);
+  int rc_pool;      // (the launch streams first: they get hardware queues of their own before the handles' streams share them out)
+  { std::lock_guard<std::mutex> lk(g_reg_mutex); rc_pool = ensure_launch_streams(h); }
+  if (rc_pool != DGSQP_OK) return fail("hipStreamCreate (launch streams) failed");
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
+  h->launch_stream = h->stream;
   for (auto& e : h->ev) if (hipEventCreate(&e) != hipSuccess) return fail("hipEventCreate failed");
   if (hipMalloc(&h->dp, sizeof(DgProb)) != hipSuccess) return fail("hipMalloc(problem) failed");
   if (hipMemcpy(h->dp, &h->hp, sizeof(DgProb), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy(problem) failed");
@@ -692,8 +724,8 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
 void dgsqp_destroy(dgsqp_handle_t h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->stream && h->in_flight) (void)hipStreamSynchronize(active_stream(h));
-  (void)hipStreamSynchronize(h->stream);
+  if (h->in_flight && active_stream(h)) (void)hipStreamSynchronize(active_stream(h));      // the launch in flight first: nothing it uses is freed under it
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
   { std::lock_guard<std::mutex> lk(g_reg_mutex); for (dgsqp_solver* o : g_handles) if (o->group_leader == h) { o->group_leader = nullptr; o->in_flight = false; } }
   if (h->d_group) (void)hipFree(h->d_group);
   if (h->group_host) (void)hipHostFree(h->group_host);
@@ -710,6 +742,12 @@ void dgsqp_destroy(dgsqp_handle_t h) {
     std::lock_guard<std::mutex> lk(g_reg_mutex);
     DgParkPool& pool = g_park[h->device & 63];
     if (pool.owner == h) pool.owner = nullptr;
+    // last handle of the device: its launch streams go as well (none has work left: every handle waited for its launch above)
+    if (std::none_of(g_handles.begin(), g_handles.end(), [&](const dgsqp_solver* o) { return o->device == h->device; })) {
+      DgLaunchStreams& ls = g_launch_streams[h->device & 63];
+      for (hipStream_t s : ls.streams) (void)hipStreamDestroy(s);
+      ls = DgLaunchStreams();
+    }
     if (g_handles.empty()) {          // last handle of the process: the pools go as well
       for (DgParkPool& pl : g_park) {
         if (pl.entries || pl.store) {
@@ -860,7 +898,7 @@ int dgsqp_reserve_deferral(dgsqp_handle_t h, int64_t scenarios) {
   dgsqp_solver* const owner = pool.owner;
   const unsigned long long owner_gen = pool.owner_gen;
   DgPark unused;
-  const int rc = park_for_launch(h, true, h->max_grid, scenarios, &unused);      // (sizes the device's pool exactly as that launch would)
+  const int rc = park_for_launch(h, h->stream, true, h->max_grid, scenarios, &unused);      // (sizes the device's pool exactly as that launch would)
   h->park_last_cap = 0;
   // no launch follows: the pool must not look taken by this handle's NEXT launch (a plain one would make other handles' cooperative
   // launches find it "busy" and run without deferral).  A re-allocation reset the owner anyway; otherwise put back what was there.
@@ -1007,6 +1045,7 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     hipLaunchKernelGGL(dg_closed_loop_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
     HIPCHK(h, hipGetLastError());
+    h->launch_stream = h->stream;
     h->in_flight = true;       // (a launch of another game waits for this kernel before it replaces the constants)
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   }

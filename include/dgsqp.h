@@ -335,7 +335,7 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T,
  */
 int dgsqp_stage_inputs(dgsqp_handle_t h, int64_t B, const double* x0, const double* u_ws);
 int dgsqp_solve_staged(dgsqp_handle_t h, dgsqp_timing_t* timing);
-/* Asynchronous halves of dgsqp_solve_staged(): enqueue the solve on the handle's own stream / wait for it.  Independent
+/* Asynchronous halves of dgsqp_solve_staged(): enqueue the solve on one of the device's launch streams / wait for it.  Independent
    batches held by different handles of the SAME game (same dgsqp_problem_t and dgsqp_params_t) can be in flight together:
    the workgroups of the later launch take over the compute units as the earlier launch drains its slowest scenarios.
    Handles of DIFFERENT games are safe too, but serialised: such a launch first waits for the launches in flight on the
@@ -344,9 +344,11 @@ int dgsqp_launch_staged(dgsqp_handle_t h);
 int dgsqp_wait(dgsqp_handle_t h, dgsqp_timing_t* timing);
 /* ONE launch over the staged batches of `count` handles (same game, same batch size, same device; at most 64): the scenarios of all
    of them share one ticket queue, every batch keeps its own input and output buffers, results are bit-identical to separate
-   launches.  A launch ends with its slowest scenario, so few long launches keep the compute units busier than many short ones; the
-   number of launches in flight is bounded by the hardware queues (16 here).  hs[0] leads: its stream, workspace and events are
-   used; every handle of the group is in flight until ITS dgsqp_wait / dgsqp_fetch_results (which wait for the group's kernel).
+   launches.  A launch ends with its slowest scenario, so few long launches keep the compute units busier than many short ones.
+   Launches run on K = min(GPU_MAX_HW_QUEUES, 8) launch streams per device (4 queues unless the variable is set), taken round robin
+   in launch order whichever handles lead: up to K launches in flight overlap, launch j queues behind launch j - K alone.  hs[0]
+   leads: its workspace and events are used; every handle of the group is in flight until ITS dgsqp_wait / dgsqp_fetch_results
+   (which wait for the group's kernel).
    Event and iterate logs are not available in grouped launches. */
 int dgsqp_launch_staged_group(const dgsqp_handle_t* hs, int count);
 /* Cooperative line search.  A launch ends with its slowest scenario (dozens of failing 50-trial line searches) while most
