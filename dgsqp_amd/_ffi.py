@@ -14,6 +14,7 @@ MAX_SEGS = 16
 MAX_NQA = 8
 MAX_LANES = 2
 NUA = 2
+MAX_DELAY = 16       # DGSQP_MAX_DELAY: longest input delay line of a closed-loop plant, in simulation steps
 
 STATUS_MSG = ['conv_abs_tol', 'conv_rel_tol', 'max_it', 'diverged', 'qp_fail', 'time_limit']
 NOT_RUN = -1         # DGSQP_NOT_RUN: a closed-loop step that never ran (step_batch reports it as 'not_run')
@@ -72,6 +73,12 @@ class ParamsT(C.Structure):
     ]
 
 
+class PlantT(C.Structure):
+    """dgsqp_plant_t: the plant of closed-loop launches (closed_loop.PlantModel lowers to it)."""
+    _fields_ = [('integrator', C.c_int32), ('substeps', C.c_int32), ('sim_steps', C.c_int32), ('use_game_agents', C.c_int32),
+                ('delay', (C.c_int32 * NUA) * MAX_AGENTS), ('agents', AgentT * MAX_AGENTS)]
+
+
 class PidT(C.Structure):
     _fields_ = [
         ('kp_v', C.c_double), ('kp_s', C.c_double), ('ki_s', C.c_double), ('ey_gain', C.c_double), ('ei_max', C.c_double),
@@ -113,6 +120,8 @@ SIGNATURES = {
     'dgsqp_solve_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _TM]),
     'dgsqp_solve_batch_f32': (C.c_int, [_H, C.c_int64, _PF, _PF, _PF, _PF, _PF, _PI, _PI, _PI, _PF, _PF, _TM]),
     'dgsqp_closed_loop_batch': (C.c_int, [_H, C.c_int64, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, _TM]),
+    'dgsqp_set_plant': (C.c_int, [_H, C.POINTER(PlantT)]),
+    'dgsqp_fetch_u_plant': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_stage_inputs': (C.c_int, [_H, C.c_int64, _PD, _PD]),
     'dgsqp_solve_staged': (C.c_int, [_H, _TM]),
     'dgsqp_launch_staged': (C.c_int, [_H]),

@@ -259,6 +259,18 @@ struct DgLog {
   int64_t doubles(const DgProb& D) const { return 1 + (int64_t)cap * (iterates ? D.n + D.nc : 2); }
 };
 
+// The plant of closed-loop launches (dgsqp_set_plant) and what such a launch leaves behind for dgsqp_fetch_u_plant.
+struct DgPlantState {
+  bool set = false;
+  dgsqp_plant_t host;                 // resolved: agents[] hold the game's records when the plant uses the game's parameters
+  dgsqp_plant_t* dev = nullptr;
+  double* lines = nullptr;            // delay lines, one set per workgroup
+  size_t lines_groups = 0;
+  double* u_buf = nullptr;            // u_plant [T][B][S][nu] of the last launch with a plant
+  size_t u_bytes = 0;
+  int64_t u_doubles = 0;              // what that launch wrote (0: none yet)
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -279,6 +291,7 @@ struct dgsqp_solver {
   DgRecords staged;                       // ... and its arrays
   DgRecords closed;                       // closed-loop launches (dgsqp_closed_loop_batch): step-major arrays
   DgLog trace{false}, itlog{true};
+  DgPlantState plant;
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -617,6 +630,31 @@ static int log_fetch(dgsqp_solver* h, DgLog& g, double* out, int64_t capacity_do
   return DGSQP_OK;
 }
 
+// ---- the plant of closed-loop launches (DgPlantState) ----
+// what a closed-loop launch of `grid` workgroups over TB (step, scenario) pairs hands the plant kernel: delay lines per workgroup (the
+// kernel clears them when a chain starts) and the u_plant record, filled with NaN on h's stream
+static int plant_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantDev* out) {
+  DgPlantState& S = h->plant;
+  if ((size_t)grid > S.lines_groups) {
+    if (S.lines) (void)hipFree(S.lines);
+    S.lines = nullptr; S.lines_groups = 0;
+    HIPCHK(h, hipMalloc((void**)&S.lines, sizeof(double) * (size_t)grid * DGSQP_MAX_AGENTS * DGSQP_NUA * DGSQP_MAX_DELAY));
+    S.lines_groups = (size_t)grid;
+  }
+  S.u_doubles = 0;
+  const int64_t doubles = TB * S.host.sim_steps * h->hp.nu;
+  if (sizeof(double) * (size_t)doubles > S.u_bytes) {
+    if (S.u_buf) (void)hipFree(S.u_buf);
+    S.u_buf = nullptr; S.u_bytes = 0;
+    HIPCHK(h, hipMalloc((void**)&S.u_buf, sizeof(double) * (size_t)doubles));
+    S.u_bytes = sizeof(double) * (size_t)doubles;
+  }
+  HIPCHK(h, hipMemsetAsync(S.u_buf, 0xff, sizeof(double) * (size_t)doubles, h->stream));
+  S.u_doubles = doubles;
+  *out = DgPlantDev{S.dev, S.lines, S.u_buf};
+  return DGSQP_OK;
+}
+
 // The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
 // L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.  Everything it enqueues goes
 // to the next launch stream of the device's pool, which L records: waits, queries and timing follow that record.
@@ -707,7 +745,8 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   h->coop_bytes = sizeof(DgCoop) + sizeof(DgCoopJob) * 2 * (size_t)(h->num_cu * 2 + 2);
   if (hipMalloc((void**)&h->d_coop, h->coop_bytes) != hipSuccess) return fail("hipMalloc(coop) failed");
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
-  const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel};
+  const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
+                           (const void*)dg_closed_loop_kernel<DgPlantDev>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -762,6 +801,9 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->drained_host) (void)hipHostFree(h->drained_host);
   if (h->trace.buf) (void)hipFree(h->trace.buf);
   if (h->itlog.buf) (void)hipFree(h->itlog.buf);
+  if (h->plant.dev) (void)hipFree(h->plant.dev);
+  if (h->plant.lines) (void)hipFree(h->plant.lines);
+  if (h->plant.u_buf) (void)hipFree(h->plant.u_buf);
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1001,7 +1043,45 @@ int dgsqp_solve_batch(dgsqp_handle_t h, int64_t B, const double* x0, const doubl
   return DGSQP_OK;
 }
 
-// Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h).
+int dgsqp_set_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  DgPlantState& S = h->plant;
+  if (!plant) { S.set = false; return DGSQP_OK; }
+  auto bad = [&](const std::string& m) { h->err = "plant: " + m; return DGSQP_E_ARG; };
+  const int integ = plant->integrator;
+  if (integ != DGSQP_INT_EULER && integ != DGSQP_INT_RK4 && integ != DGSQP_INT_RK3 && integ != DGSQP_INT_RK2) return bad("unknown integrator " + std::to_string(integ));
+  if (plant->substeps < 1) return bad("substeps must be at least 1, got " + std::to_string(plant->substeps));
+  if (plant->sim_steps < 1) return bad("sim_steps must be at least 1, got " + std::to_string(plant->sim_steps));
+  const dgsqp_problem_t& P = h->hp.P;
+  for (int a = 0; a < P.M; a++) {
+    for (int j = 0; j < DGSQP_NUA; j++)
+      if (plant->delay[a][j] < 0 || plant->delay[a][j] > DGSQP_MAX_DELAY)
+        return bad("delay of agent " + std::to_string(a) + ", input " + std::to_string(j) + " is " + std::to_string(plant->delay[a][j]) + " simulation steps, allowed 0 .. " + std::to_string(DGSQP_MAX_DELAY));
+    if (!plant->use_game_agents && plant->agents[a].model != P.agents[a].model)
+      return bad("agent " + std::to_string(a) + " is of model class " + std::to_string(plant->agents[a].model) + ", the game's is " + std::to_string(P.agents[a].model));
+  }
+  S.host = *plant;
+  if (plant->use_game_agents) memcpy(S.host.agents, P.agents, sizeof(P.agents));
+  if (!S.dev) HIPCHK(h, hipMalloc((void**)&S.dev, sizeof(dgsqp_plant_t)));
+  HIPCHK(h, hipMemcpy(S.dev, &S.host, sizeof(dgsqp_plant_t), hipMemcpyHostToDevice));
+  S.set = true;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  if (!h) return DGSQP_E_ARG;
+  const DgPlantState& S = h->plant;
+  if (!out || !S.u_buf || S.u_doubles <= 0) { h->err = "no closed-loop launch with a plant has run"; return DGSQP_E_ARG; }
+  if (capacity_doubles < S.u_doubles) { h->err = "u_plant buffer too small: need " + std::to_string(S.u_doubles) + " doubles"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(out, S.u_buf, sizeof(double) * (size_t)S.u_doubles, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
+// Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
+// DgPlantDev argument when the handle has a plant.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1038,12 +1118,15 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   cl.O = S.out(c);
   cl.x_step = x_out ? B * (int64_t)h->rec[DG_X].per : 0;
   cl.steps_done = (int32_t*)S.p[DG_DONE];
+  DgPlantDev pd{};
+  if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(dg_closed_loop_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
+    if (h->plant.set) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd);
+    else hipLaunchKernelGGL(dg_closed_loop_kernel<>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
     HIPCHK(h, hipGetLastError());
     h->launch_stream = h->stream;
     h->in_flight = true;       // (a launch of another game waits for this kernel before it replaces the constants)

@@ -16,16 +16,135 @@ struct DgClosedLoop {
   int32_t* steps_done;   // [B]
 };
 
+// A plant of its own (dgsqp_set_plant; reference DGSQP/dynamics/dynamics_simulator.py:11-40): after every solve the state is advanced by
+// S simulation steps of length dt / S of a model with the plant's vehicle parameters and integrator, every input channel behind a delay
+// line.  `lines` is written and read back by the same lane of the same workgroup: a plain pointer like q and uws.
+struct DgPlantDev {
+  const dgsqp_plant_t* P;   // resolved by the host: agents[] hold the game's records when the plant uses the game's parameters
+  double* lines;            // [grid][DGSQP_MAX_AGENTS][DGSQP_NUA][DGSQP_MAX_DELAY]  one set per workgroup, cleared when a chain starts
+  double* u_plant;          // [T][B][S][nu]  the inputs the plant integrated under
+};
+
+// S simulation steps of agent a's plant from q (in place).  Simulation step `count` (counted from the chain's start) of a channel with
+// delay d > 0 integrates under entry count % d of its line -- the oldest of the last d -- and then stores u_new there (a deque of
+// length d: read [0], append); d = 0 integrates under u_new.  One plant step is dev_fd_t's arithmetic on f_c with the plant's agent
+// record, step length and sub-step count (euler: one step per simulation step, as the game's model).
+template <int NQA, bool SPL>
+__device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_plant_t& pl, int a, int64_t count, const double* u_new,
+                                       double* line, double* u_rec, int nu, double* qa) {
+  typedef Ty<0> T;
+  const dgsqp_agent_t& ag = pl.agents[a];
+  const int S = pl.sim_steps, integ = pl.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : pl.substeps;
+  const double hs = P.dt / S, h = hs / nsub;
+  T x[NQA], k1[NQA], k2[NQA], t[NQA], u[DGSQP_NUA];
+#pragma unroll
+  for (int i = 0; i < NQA; i++) x[i].c[0] = qa[i];
+  for (int j = 0; j < S; j++, count++) {
+    for (int ch = 0; ch < DGSQP_NUA; ch++) {
+      const int d = pl.delay[a][ch];
+      double v = u_new[ch];
+      if (d > 0) {
+        double* slot = line + ch * DGSQP_MAX_DELAY + (int)(count % d);
+        v = *slot;
+        *slot = u_new[ch];
+      }
+      u[ch].c[0] = v;
+      u_rec[(int64_t)j * nu + ch] = v;
+    }
+    FcPre<0> pre;
+    if constexpr (NQA == 8) dev_fc_pre_dyn<0>(ag, u, pre);
+    else if constexpr (NQA == 4) { pre.im = 1.0 / ag.mass; pre.iz = 0.0; pre.ilr = 0.0; }
+    else dev_fc_pre_kin<0>(ag, u, pre);
+    for (int m = 0; m < nsub; m++) {
+      dev_fc<0, NQA, SPL>(P, ag, x, u, pre, k1);
+      if (integ == DGSQP_INT_RK4) {
+#pragma unroll
+        for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * (h / 2);
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * (h / 2); k1[i] = k1[i] + k2[i] * 2.0; }
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * h; k1[i] = k1[i] + k2[i] * 2.0; }
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 6.0);
+      } else if (integ == DGSQP_INT_RK3) {
+#pragma unroll
+        for (int i = 0; i < NQA; i++) { k1[i] = k1[i] * h; t[i] = x[i] + k1[i] * 0.5; }
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) { k2[i] = k2[i] * h; t[i] = x[i] - k1[i] + k2[i] * 2.0; }
+        T k3[NQA];
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k3);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
+      } else if (integ == DGSQP_INT_RK2) {
+#pragma unroll
+        for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * h;
+        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+#pragma unroll
+        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 2);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NQA; i++) x[i] = x[i] + k1[i] * hs;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NQA; i++) qa[i] = x[i].c[0];
+}
+
+// The plant's feedback of step t of chain b, one lane per agent: q_next = plant(q_t, stage 0 of u_t) (+ w_t).  Returns non-zero on the
+// lanes whose part of q_next is not finite.  Out of line: the solve that is inlined next to the call keeps its register allocation.
+// The caller has fenced the solve's records (u_t); q_t was written by this very lane one step ago, or by the host.
+__device__ __noinline__ int dev_plant_feedback(DgPlantDev pd, int t, int64_t tb_b, const double* q_t, const double* u_t, const double* w_t,
+                                               double* q_next) {
+  const DgProb& D = dg_prob;
+  const int a = TID;
+  if (a >= D.M) return 0;
+  const dgsqp_plant_t& pl = *pd.P;
+  const int S = pl.sim_steps, nqa = D.nqa[a], qo = D.qoff[a];
+  double* line = pd.lines + ((int64_t)blockIdx.x * DGSQP_MAX_AGENTS + a) * (DGSQP_NUA * DGSQP_MAX_DELAY);
+  if (t == 0)
+    for (int i = 0; i < DGSQP_NUA * DGSQP_MAX_DELAY; i++) line[i] = 0.0;      // every chain starts with empty (zero) lines
+  double u_new[DGSQP_NUA], qa[DGSQP_MAX_NQA];
+  for (int j = 0; j < DGSQP_NUA; j++) u_new[j] = u_t[am_col(D, a, 0, j)];
+  for (int i = 0; i < DGSQP_MAX_NQA; i++) qa[i] = i < nqa ? q_t[qo + i] : 0.0;
+  double* u_rec = pd.u_plant + tb_b * S * D.nu + a * DGSQP_NUA;
+  const int64_t count = (int64_t)t * S;
+  if (nqa == 4) dev_plant_agent<4, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  else if (D.P.track_kind == DGSQP_TRACK_SPLINE) {
+    if (nqa == 8) dev_plant_agent<8, true>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+    else dev_plant_agent<6, true>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  }
+  else if (nqa == 8) dev_plant_agent<8, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  else dev_plant_agent<6, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  int bad = 0;
+  for (int i = 0; i < DGSQP_MAX_NQA; i++)
+    if (i < nqa) {
+      double v = qa[i];
+      if (w_t) v = v + w_t[qo + i];
+      q_next[qo + i] = v;
+      bad |= !isfinite(v);
+    }
+  return bad;
+}
+
 // Per ticket b, for t = 0 .. T-1: solve from (q[t][b], uws[t][b]) exactly as dg_solve_kernel would, then
 //   q[t+1][b]   = x_t[b][1] (+ w[t][b])                          the game's own discrete model is the plant
+//            or = plant(q[t][b], stage 0 of u_t[b]) (+ w[t][b])  with a PLANT: dev_plant_feedback
 //   uws[t+1][b] = shift(u_t[b]), or uws[t][b] after 'diverged' / 'qp_fail'   (DGSQP.py:293-295)
 // shift, per agent: row k takes row k + 1, the last row is repeated (np.vstack((u_pred[1:], u_pred[-1]))).
 // A non-finite q[t+1][b] ends the chain: steps_done[b] = t + 1, and no solve starts from such a state (q[t+1][b] keeps that state,
 // uws[t+1][b] is not written).  The records of steps that never ran keep what the host filled them with before the launch
 // (status DGSQP_NOT_RUN, zero counts, NaN).
 // No cooperative line search, no deferral, no event or iterate log: a chain's next solve depends on its last one.
+// PLANT is empty, or one DgPlantDev: the instantiation without a plant has the argument list it always had and holds nothing of the plant.
+template <class... PLANT>
 __global__ void __launch_bounds__(DG_BLOCK, 2)
-dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket) {
+dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket, PLANT... pd) {
+  static_assert(sizeof...(PLANT) <= 1, "at most one plant");
   Ctx c;
   c.coop = nullptr; c.coop_payload = nullptr; c.coop_total = 0; c.coop_start = 0; c.coop_verify = 0; c.coop_window = 0; c.coop_helpers = 0;
   c.park = DgPark{};
@@ -63,12 +182,14 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
       double* q_next = cl.q + (tb + B + b) * nq;
       double* uws_next = cl.uws + (tb + B + b) * n;
       int bad = 0;
-      for (int i = TID; i < nq; i += NT) {
-        double v = x1[i];
-        if (w_t) v = v + w_t[i];
-        q_next[i] = v;
-        bad |= !isfinite(v);
-      }
+      if constexpr (sizeof...(PLANT) != 0) bad = dev_plant_feedback(pd..., t, tb + b, cl.q + (tb + b) * nq, u_t, w_t, q_next);
+      else
+        for (int i = TID; i < nq; i += NT) {
+          double v = x1[i];
+          if (w_t) v = v + w_t[i];
+          q_next[i] = v;
+          bad |= !isfinite(v);
+        }
       t++;
       if (__syncthreads_or(bad)) break;                     // the chain ends: q[t] shows why, its warm start is never written
       for (int i = TID; i < n; i += NT) {

@@ -44,6 +44,31 @@ class AbstractSolver:
 # ---------------------------------------------------------------------------------------------
 # lowering of the game to the C PODs (pure host logic, no GPU needed)
 # ---------------------------------------------------------------------------------------------
+def fill_vehicle(A: _ffi.AgentT, model_id: int, c) -> None:
+    """The vehicle fields of one ``dgsqp_agent_t`` (model .. lin_Br) from a model class and its config: what ``build_problem`` writes for
+    every agent of the game and ``closed_loop.PlantModel`` for every agent of a plant."""
+    A.model = model_id
+    if model_id != 2:
+        A.L_f, A.L_r, A.mass = c.wheel_dist_front, c.wheel_dist_rear, c.mass
+        A.c_dr, A.c_da = c.drag_coefficient, c.damping_coefficient
+        A.c_r, A.p_r = c.rolling_resistance, c.rolling_resistance_exponent
+    if model_id == 2:
+        A.L_f = A.L_r = 0.13
+        A.mass, A.I_z, A.gravity = float(getattr(c, 'mass', 2.366)), 1.0, 9.81      # (CasadiKinematicUnicycle.m)
+        A.c_dr = A.c_da = A.c_r = 0.0
+        A.p_r = 0.5
+    elif model_id == 0:
+        A.c_s = c.slip_coefficient
+        A.I_z, A.gravity = 1.0, 9.81
+    else:
+        A.I_z, A.gravity = c.yaw_inertia, c.gravity
+        A.tire_model = 0 if c.tire_model == 'pacejka' else 1
+        A.drive_wheels = 0 if c.drive_wheels == 'all' else 1
+        A.simple_slip = int(bool(c.simple_slip))
+        A.pac_Bf, A.pac_Br, A.pac_Cf, A.pac_Cr = c.pacejka_b_front, c.pacejka_b_rear, c.pacejka_c_front, c.pacejka_c_rear
+        A.pac_Df, A.pac_Dr, A.lin_Bf, A.lin_Br = c.pacejka_d_front, c.pacejka_d_rear, c.linear_bf, c.linear_br
+
+
 def build_problem(joint_dynamics: CasadiDecoupledMultiAgentDynamicsModel,
                   costs: List[RacingCost],
                   agent_constraints: List[Optional[InputRateLimits]],
@@ -88,27 +113,7 @@ def build_problem(joint_dynamics: CasadiDecoupledMultiAgentDynamicsModel,
         raise ValueError('CollisionAvoidance.radii must have one entry per agent')
     for a, mdl in enumerate(joint_dynamics.dynamics_models):
         A = P.agents[a]
-        c = mdl.model_config
-        A.model = mdl.model_id
-        if mdl.model_id != 2:
-            A.L_f, A.L_r, A.mass = c.wheel_dist_front, c.wheel_dist_rear, c.mass
-            A.c_dr, A.c_da = c.drag_coefficient, c.damping_coefficient
-            A.c_r, A.p_r = c.rolling_resistance, c.rolling_resistance_exponent
-        if mdl.model_id == 2:
-            A.L_f = A.L_r = 0.13
-            A.mass, A.I_z, A.gravity = float(mdl.m), 1.0, 9.81
-            A.c_dr = A.c_da = A.c_r = 0.0
-            A.p_r = 0.5
-        elif mdl.model_id == 0:
-            A.c_s = c.slip_coefficient
-            A.I_z, A.gravity = 1.0, 9.81
-        else:
-            A.I_z, A.gravity = c.yaw_inertia, c.gravity
-            A.tire_model = 0 if c.tire_model == 'pacejka' else 1
-            A.drive_wheels = 0 if c.drive_wheels == 'all' else 1
-            A.simple_slip = int(bool(c.simple_slip))
-            A.pac_Bf, A.pac_Br, A.pac_Cf, A.pac_Cr = c.pacejka_b_front, c.pacejka_b_rear, c.pacejka_c_front, c.pacejka_c_rear
-            A.pac_Df, A.pac_Dr, A.lin_Bf, A.lin_Br = c.pacejka_d_front, c.pacejka_d_rear, c.linear_bf, c.linear_br
+        fill_vehicle(A, mdl.model_id, mdl.model_config)
         cost = costs[a]
         for j in range(2):
             A.w_in[j] = float(cost.input_weight[j])
@@ -502,7 +507,7 @@ class DGSQP(AbstractSolver):
         return self._finish(out, t0, tm)
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
-                   keep_predictions: bool = False) -> dict:
+                   keep_predictions: bool = False, plant=None) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -510,6 +515,11 @@ class DGSQP(AbstractSolver):
         performs from the same (state, warm start).  A chain whose next state is not finite ends there (``steps_done``; ``q`` keeps that
         state); the steps it never ran report status -1 / 'not_run', zero counts and NaN, their ``q`` / ``u_ws`` slices included.  Event log, iterate log, cooperative line search and deferral do
         not apply to closed-loop launches.
+
+        ``plant`` (``closed_loop.PlantModel``): the state is fed back through a plant of its own instead of stage 1 of the prediction --
+        other vehicle parameters, a finer integration, delayed inputs (``dgsqp_set_plant``; host mirror ``closed_loop.plant_feedback``) --
+        for this call only; the solves themselves do not change.  The result then also holds u_plant [B, T, S, n_u], the inputs the plant
+        integrated under in each of its S simulation steps (NaN where a step never ran).
 
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
@@ -528,11 +538,25 @@ class DGSQP(AbstractSolver):
         sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), **self._records((T, B), predictions=keep_predictions))
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
+        u_plant = None
+        if plant is not None:
+            pt = plant.lower(self._problem)
+            if self._lib.dgsqp_set_plant(self._h, C.byref(pt)) != 0:
+                raise ValueError('dgsqp_set_plant failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+            u_plant = np.empty((T, B, pt.sim_steps, self.n_u))
         t0 = time.time()
-        rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
-                                               *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
-        if rc != 0:
-            raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
+        try:
+            rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
+                                                   *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
+            if rc != 0:
+                raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
+            if u_plant is not None and B > 0 and self._lib.dgsqp_fetch_u_plant(self._h, _ffi.dptr(u_plant), u_plant.size) != 0:
+                raise RuntimeError('dgsqp_fetch_u_plant failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+        finally:
+            if plant is not None:
+                self._lib.dgsqp_set_plant(self._h, None)
+        if u_plant is not None:
+            sm['u_plant'] = u_plant
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
         out['steps_done'] = steps_done
         self._finish(out, t0, tm)

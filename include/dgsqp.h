@@ -304,6 +304,7 @@ int dgsqp_solve_batch_f32(dgsqp_handle_t h, int64_t B, const float* x0, const fl
  * scenario, and no intermediate state crosses the host.  Step t of scenario b is the very solve dgsqp_solve_batch performs from
  * (q[t][b], u_ws[t][b]) -- bit for bit --; between steps
  *   q[t+1][b]    = x_t[b][1] (+ w[t][b])          the plant is the game's own discrete model plus the optional disturbance w
+ *                                                 (or the plant of dgsqp_set_plant, below)
  *   u_ws[t+1][b] = u_t[b] shifted by one stage per agent, last row repeated; after DGSQP_DIVERGED / DGSQP_QP_FAIL: u_ws[t][b] again
  * A non-finite q[t+1][b] ends chain b: steps_done[b] = t + 1 (otherwise T) and no solve starts from such a state.  Records of steps
  * that never ran hold status DGSQP_NOT_RUN, iters = qp_solves = 0 and NaN in every double, their q / u_ws slices included
@@ -327,6 +328,36 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T,
     double* cost,          /* [T][B][M] */
     int32_t* steps_done,   /* [B] */
     dgsqp_timing_t* timing);
+
+/*
+ * A plant of its own for closed-loop launches (reference DGSQP/dynamics/dynamics_simulator.py:11-40: the simulator steps a model
+ * built from its own dynamics_config, several simulation steps per control step, every input channel behind a delay line).  With a
+ * plant set, q[t+1][b] is no longer stage 1 of the prediction: the state q[t][b] is advanced by sim_steps simulation steps of
+ * length dt / sim_steps of the plant's model -- the game's model class, state layout and track; vehicle parameters, tyre model,
+ * driven wheels and slip formula of its own -- under u_new = stage 0 of u_t[b].  Simulation step j of a channel with delay d > 0
+ * integrates under the oldest entry of that channel's line (d entries, zeros when the chain starts, kept from control step to control
+ * step) and then appends u_new; d = 0 integrates under u_new.  One simulation step is `substeps` steps of `integrator` on the
+ * continuous model (DGSQP_INT_EULER takes one step, as the game's model does).  After the sim_steps steps w[t][b] is added as
+ * before; the end-of-chain rule, steps_done, the warm-start shift and every solve are unchanged (step t still is, bit for bit, the
+ * solve dgsqp_solve_batch performs from (q[t][b], u_ws[t][b])).
+ */
+#define DGSQP_MAX_DELAY 16
+typedef struct {
+  int32_t integrator;      /* DGSQP_INT_* */
+  int32_t substeps;        /* >= 1 */
+  int32_t sim_steps;       /* >= 1 */
+  int32_t use_game_agents; /* 1: the game's vehicle parameters (agents[] is not read) */
+  int32_t delay[DGSQP_MAX_AGENTS][DGSQP_NUA]; /* simulation steps, 0 .. DGSQP_MAX_DELAY; entries beyond M are not read */
+  dgsqp_agent_t agents[DGSQP_MAX_AGENTS];     /* only the vehicle fields (model .. lin_Br) are read; model must equal the game's */
+} dgsqp_plant_t;
+/* The plant of the handle's SUBSEQUENT closed-loop launches (copied); NULL: the game's own discrete model again.  Nothing else is
+   affected.  DGSQP_E_ARG with the reason in dgsqp_last_error: unknown integrator, substeps < 1, sim_steps < 1, a delay outside
+   0 .. DGSQP_MAX_DELAY, an agent of another model class than the game's. */
+int dgsqp_set_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant);
+/* The inputs the plant integrated under in the handle's last closed-loop launch with a plant: out [T][B][sim_steps][n_u] (n_u joint
+   inputs, agent after agent); NaN where a step never ran.  capacity_doubles = what out can hold (DGSQP_E_ARG when it is too small or
+   when no such launch has run). */
+int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles);
 
 /*
  * Device-resident variant used by bench.py: inputs are staged once with

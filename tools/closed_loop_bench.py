@@ -3,13 +3,17 @@
 
 (a) host loop: T rounds of ``solve_batch`` (default cooperative mode), numpy ``closed_loop.feedback``, re-upload -- T launches, each
     ending with its slowest scenario, and 2 T copies;
-(b) ``step_batch``: one launch that ends with its longest chain, no intermediate copies (and no line-search helpers, no deferral).
+(b) ``step_batch``: one launch that ends with its longest chain, no intermediate copies (and no line-search helpers, no deferral);
+(c) with ``--plant``: ``step_batch`` with a plant of its own (``closed_loop.PlantModel``: the game's vehicle, rk4 with 10 sub-steps, 2
+    simulation steps per control step, car 1's steering delayed by one simulation step), timed next to (a) and (b).  Its chains differ
+    from (b)'s -- another state is fed back --, so its time is reported, not compared.
 
 Game and size: BASELINE configs[1] (dyn_curve_N25), B = 1,024, T = 10, no disturbance, inputs from the device sampler.  The two are
 alternated ``--repeats`` times in one process after one warm-up each; times are host clocks around synchronous calls.  The script also
 asserts that both produce identical status, num_iters and q.
 
     python tools/closed_loop_bench.py [--out profiles/closed_loop_dyn_curve_N25.txt]
+    python tools/closed_loop_bench.py --plant --out profiles/closed_loop_plant_dyn_curve_N25.txt
 """
 import argparse
 import pathlib
@@ -53,6 +57,7 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--plant', action='store_true', help='also time step_batch with a plant of its own (c)')
     ap.add_argument('--out', default=str(ROOT / 'profiles' / 'closed_loop_dyn_curve_N25.txt'))
     args = ap.parse_args()
     from dgsqp_amd.montecarlo import dynamic_racing_game
@@ -70,14 +75,22 @@ def main():
 
     run_a = lambda: host_loop(s, x0, u_am, T)
     run_b = lambda: s.step_batch(x0, u_am, T)
+    if args.plant:
+        from dgsqp_amd.closed_loop import PlantModel
+        plant = PlantModel(method='rk4', M=10, sim_steps=2, delay_steps=[[0, 1], [0, 0]])
+        run_c = lambda: s.step_batch(x0, u_am, T, plant=plant)
     _, a = timed(run_a)                                          # warm-up of each (code objects, buffers)
     _, b = timed(run_b)
+    if args.plant:
+        timed(run_c)
     for key in ('status', 'num_iters', 'q'):
         assert np.array_equal(a[key], b[key], equal_nan=(key == 'q')), f'{key}: host loop and step_batch differ'
-    ta, tb, ka, kb = [], [], [], []
+    ta, tb, tc, ka, kb, kc = [], [], [], [], [], []
     for _ in range(args.repeats):
         dt, a = timed(run_a); ta.append(dt); ka.append(a['kernel_ms'] / 1e3)
         dt, b = timed(run_b); tb.append(dt); kb.append(b['kernel_ms'] / 1e3)
+        if args.plant:
+            dt, c = timed(run_c); tc.append(dt); kc.append(c['kernel_ms'] / 1e3)
     st = b['status']
     fmt = lambda v: f'median {np.median(v) * 1e3:.1f} ms (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f})'
     lines = [f'closed loop, dyn_curve_N25 (BASELINE configs[1]), B = {B} chains x T = {T} steps, no disturbance, device-sampled inputs (seed {args.seed}); {args.repeats} alternated repeats after one warm-up each',
@@ -86,6 +99,11 @@ def main():
              f'(b) / (a), medians of the wall times: {np.median(tb) / np.median(ta):.3f}   ((a) / (b) = {np.median(ta) / np.median(tb):.3f})',
              f'identical status, num_iters and q in (a) and (b): yes (asserted); steps run {int((st >= 0).sum())} of {B * T}, converged {np.mean((st >= 0) & (st <= 1)):.3f}, '
              f'iterations per step: mean {b["num_iters"].mean():.2f}, max {int(b["num_iters"].max())}; per chain: mean {b["num_iters"].sum(axis=1).mean():.1f}, max {int(b["num_iters"].sum(axis=1).max())}']
+    if args.plant:
+        sc = c['status']
+        lines.append(f'(c) step_batch with a plant (rk4, 10 sub-steps, 2 simulation steps per control step, one delayed channel):  wall {fmt(tc)}; kernel alone {fmt(kc)}; '
+                     f'steps run {int((sc >= 0).sum())} of {B * T}, converged {np.mean((sc >= 0) & (sc <= 1)):.3f}, iterations per chain: mean {c["num_iters"].sum(axis=1).mean():.1f}, '
+                     f'max {int(c["num_iters"].sum(axis=1).max())}; every wall time of (b): {", ".join(f"{v * 1e3:.1f}" for v in tb)} ms')
     text = '\n'.join(lines)
     print(text)
     pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
