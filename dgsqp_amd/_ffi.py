@@ -79,6 +79,11 @@ class PlantT(C.Structure):
                 ('delay', (C.c_int32 * NUA) * MAX_AGENTS), ('agents', AgentT * MAX_AGENTS)]
 
 
+class VehicleT(C.Structure):
+    """dgsqp_vehicle_t: the vehicle fields of dgsqp_agent_t (model .. lin_Br), one per chain and agent of a plant ensemble."""
+    _fields_ = AgentT._fields_[:22]
+
+
 class PidT(C.Structure):
     _fields_ = [
         ('kp_v', C.c_double), ('kp_s', C.c_double), ('ki_s', C.c_double), ('ey_gain', C.c_double), ('ei_max', C.c_double),
@@ -122,6 +127,11 @@ SIGNATURES = {
     'dgsqp_closed_loop_batch': (C.c_int, [_H, C.c_int64, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, _TM]),
     'dgsqp_set_plant': (C.c_int, [_H, C.POINTER(PlantT)]),
     'dgsqp_fetch_u_plant': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_plant_ensemble': (C.c_int, [_H, C.c_int64, C.POINTER(VehicleT), _PI]),
+    'dgsqp_set_estimate_noise': (C.c_int, [_H, C.c_int32, C.c_int64, _PD]),
+    'dgsqp_fetch_q_est': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_monitor': (C.c_int, [_H, C.c_int]),
+    'dgsqp_fetch_monitor': (C.c_int, [_H, _PD, _PD, _PI]),
     'dgsqp_stage_inputs': (C.c_int, [_H, C.c_int64, _PD, _PD]),
     'dgsqp_solve_staged': (C.c_int, [_H, _TM]),
     'dgsqp_launch_staged': (C.c_int, [_H]),

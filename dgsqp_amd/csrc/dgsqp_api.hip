@@ -271,6 +271,27 @@ struct DgPlantState {
   int64_t u_doubles = 0;              // what that launch wrote (0: none yet)
 };
 
+// The further settings of closed-loop launches with a plant (dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise, dgsqp_set_monitor) and
+// what such a launch leaves behind for dgsqp_fetch_q_est / dgsqp_fetch_monitor.  A device buffer that only grows: DgBuf.
+struct DgBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+struct DgEnsembleState {
+  int64_t B = 0;                      // chains of the plant ensemble (0: off)
+  bool has_delay = false;
+  DgBuf vehicles, delay;              // [B][M] dgsqp_vehicle_t, [B][M][DGSQP_NUA] int32
+  DgBuf wg_plant;                     // one dgsqp_plant_t per workgroup
+  int32_t est_T = 0;                  // estimate noise: its shape (0: off) ...
+  int64_t est_B = 0;
+  DgBuf v, q_est;                     // ... v and q_est [T][B][nq]
+  int64_t q_est_doubles = 0;          // what the last launch with estimates wrote (0: none yet)
+  int monitor = 0;                    // 0 off, 1 record, 2 record and stop
+  DgBuf scratch, clearance, box_excess, hit_step;
+  int64_t mon_TB = 0, mon_B = 0;      // shape of the last launch with the monitor on (0: none yet)
+  bool any() const { return B > 0 || est_T > 0 || monitor != 0; }
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -292,6 +313,7 @@ struct dgsqp_solver {
   DgRecords closed;                       // closed-loop launches (dgsqp_closed_loop_batch): step-major arrays
   DgLog trace{false}, itlog{true};
   DgPlantState plant;
+  DgEnsembleState ens;
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -655,6 +677,53 @@ static int plant_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantDev* o
   return DGSQP_OK;
 }
 
+static int buf_reserve(dgsqp_solver* h, DgBuf& b, size_t bytes) {
+  if (bytes <= b.bytes) return DGSQP_OK;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr; b.bytes = 0;
+  HIPCHK(h, hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return DGSQP_OK;
+}
+// what a closed-loop launch of `grid` workgroups, B chains and T steps hands the kernel when one of the further settings is on: sizes the
+// per-workgroup buffers and fills the records on h's stream (NaN, hit_step -1).  The caller has checked the shapes the settings were made for.
+static int ensemble_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, const DgPlantDev& pd, DgEnsembleDev* out) {
+  DgEnsembleState& E = h->ens;
+  const int64_t TB = (int64_t)T * B;
+  DgEnsembleDev ex{};
+  ex.pd = pd; ex.B = B;
+  if (E.B > 0) {
+    if (sizeof(dgsqp_plant_t) * (size_t)grid > E.wg_plant.bytes) {
+      { const int rc = buf_reserve(h, E.wg_plant, sizeof(dgsqp_plant_t) * (size_t)grid); if (rc) return rc; }
+      HIPCHK(h, hipMemsetAsync(E.wg_plant.p, 0, E.wg_plant.bytes, h->stream));
+    }
+    ex.vehicles = (const dgsqp_vehicle_t*)E.vehicles.p; ex.delay = E.has_delay ? (const int32_t*)E.delay.p : nullptr; ex.wg_plant = (dgsqp_plant_t*)E.wg_plant.p;
+  }
+  if (E.est_T > 0) {
+    const size_t bytes = sizeof(double) * (size_t)TB * h->hp.nq;
+    E.q_est_doubles = 0;
+    { const int rc = buf_reserve(h, E.q_est, bytes); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(E.q_est.p, 0xff, bytes, h->stream));
+    E.q_est_doubles = TB * h->hp.nq;
+    ex.v = (const double*)E.v.p; ex.q_est = (double*)E.q_est.p;
+  }
+  if (E.monitor) {
+    E.mon_TB = E.mon_B = 0;
+    { const int rc = buf_reserve(h, E.scratch, sizeof(double) * (size_t)grid * h->plant.host.sim_steps * h->hp.M * 3); if (rc) return rc; }
+    { const int rc = buf_reserve(h, E.clearance, sizeof(double) * (size_t)TB); if (rc) return rc; }
+    { const int rc = buf_reserve(h, E.box_excess, sizeof(double) * (size_t)TB); if (rc) return rc; }
+    { const int rc = buf_reserve(h, E.hit_step, sizeof(int32_t) * (size_t)B); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(E.clearance.p, 0xff, sizeof(double) * (size_t)TB, h->stream));
+    HIPCHK(h, hipMemsetAsync(E.box_excess.p, 0xff, sizeof(double) * (size_t)TB, h->stream));
+    HIPCHK(h, hipMemsetAsync(E.hit_step.p, 0xff, sizeof(int32_t) * (size_t)B, h->stream));
+    E.mon_TB = TB; E.mon_B = B;
+    ex.monitor = E.monitor; ex.mon_scratch = (double*)E.scratch.p; ex.clearance = (double*)E.clearance.p; ex.box_excess = (double*)E.box_excess.p;
+    ex.hit_step = (int32_t*)E.hit_step.p;
+  }
+  *out = ex;
+  return DGSQP_OK;
+}
+
 // The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
 // L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.  Everything it enqueues goes
 // to the next launch stream of the device's pool, which L records: waits, queries and timing follow that record.
@@ -746,7 +815,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc((void**)&h->d_coop, h->coop_bytes) != hipSuccess) return fail("hipMalloc(coop) failed");
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
   const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDev>};
+                           (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -804,6 +873,8 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->plant.dev) (void)hipFree(h->plant.dev);
   if (h->plant.lines) (void)hipFree(h->plant.lines);
   if (h->plant.u_buf) (void)hipFree(h->plant.u_buf);
+  for (DgBuf* b : {&h->ens.vehicles, &h->ens.delay, &h->ens.wg_plant, &h->ens.v, &h->ens.q_est, &h->ens.scratch, &h->ens.clearance, &h->ens.box_excess, &h->ens.hit_step})
+    if (b->p) (void)hipFree(b->p);
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1080,8 +1151,88 @@ int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles)
   return DGSQP_OK;
 }
 
+int dgsqp_set_plant_ensemble(dgsqp_handle_t h, int64_t B, const dgsqp_vehicle_t* vehicles, const int32_t* delay) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  DgEnsembleState& E = h->ens;
+  if (!vehicles || B == 0) { E.B = 0; return DGSQP_OK; }
+  auto bad = [&](const std::string& m) { h->err = "plant ensemble: " + m; return DGSQP_E_ARG; };
+  if (!h->plant.set) return bad("no plant set (dgsqp_set_plant first; the identity plant will do)");
+  if (B < 0) return bad("B must not be negative");
+  const int M = h->hp.P.M;
+  for (int64_t b = 0; b < B; b++)
+    for (int a = 0; a < M; a++) {
+      if (vehicles[b * M + a].model != h->hp.P.agents[a].model)
+        return bad("vehicle of chain " + std::to_string(b) + ", agent " + std::to_string(a) + " is of model class " + std::to_string(vehicles[b * M + a].model) + ", the game's is " + std::to_string(h->hp.P.agents[a].model));
+      for (int j = 0; delay && j < DGSQP_NUA; j++) {
+        const int32_t d = delay[(b * M + a) * DGSQP_NUA + j];
+        if (d < 0 || d > DGSQP_MAX_DELAY)
+          return bad("delay of chain " + std::to_string(b) + ", agent " + std::to_string(a) + ", input " + std::to_string(j) + " is " + std::to_string(d) + " simulation steps, allowed 0 .. " + std::to_string(DGSQP_MAX_DELAY));
+      }
+    }
+  E.B = 0;
+  const size_t nv = sizeof(dgsqp_vehicle_t) * (size_t)B * M, nd = sizeof(int32_t) * (size_t)B * M * DGSQP_NUA;
+  { const int rc = buf_reserve(h, E.vehicles, nv); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(E.vehicles.p, vehicles, nv, hipMemcpyHostToDevice));
+  if (delay) {
+    { const int rc = buf_reserve(h, E.delay, nd); if (rc) return rc; }
+    HIPCHK(h, hipMemcpy(E.delay.p, delay, nd, hipMemcpyHostToDevice));
+  }
+  E.has_delay = delay != nullptr;
+  E.B = B;
+  return DGSQP_OK;
+}
+int dgsqp_set_estimate_noise(dgsqp_handle_t h, int32_t T, int64_t B, const double* v) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  DgEnsembleState& E = h->ens;
+  if (!v || T == 0 || B == 0) { E.est_T = 0; E.est_B = 0; return DGSQP_OK; }
+  if (!h->plant.set) { h->err = "estimate noise: no plant set (dgsqp_set_plant first; the identity plant will do)"; return DGSQP_E_ARG; }
+  if (T < 0 || B < 0) { h->err = "estimate noise: T and B must not be negative"; return DGSQP_E_ARG; }
+  E.est_T = 0; E.est_B = 0;
+  const size_t bytes = sizeof(double) * (size_t)T * (size_t)B * h->hp.nq;
+  { const int rc = buf_reserve(h, E.v, bytes); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(E.v.p, v, bytes, hipMemcpyHostToDevice));
+  E.est_T = T; E.est_B = B;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_q_est(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  if (!h) return DGSQP_E_ARG;
+  const DgEnsembleState& E = h->ens;
+  if (!out || !E.q_est.p || E.q_est_doubles <= 0) { h->err = "no closed-loop launch with state estimates has run"; return DGSQP_E_ARG; }
+  if (capacity_doubles < E.q_est_doubles) { h->err = "q_est buffer too small: need " + std::to_string(E.q_est_doubles) + " doubles"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(out, E.q_est.p, sizeof(double) * (size_t)E.q_est_doubles, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+int dgsqp_set_monitor(dgsqp_handle_t h, int mode) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  if (mode == 0) { h->ens.monitor = 0; return DGSQP_OK; }
+  if (mode != 1 && mode != 2) { h->err = "monitor: mode must be 0 (off), 1 (record) or 2 (record and stop), got " + std::to_string(mode); return DGSQP_E_ARG; }
+  if (!h->plant.set) { h->err = "monitor: no plant set (dgsqp_set_plant first; the identity plant will do)"; return DGSQP_E_ARG; }
+  h->ens.monitor = mode;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess, int32_t* hit_step) {
+  if (!h) return DGSQP_E_ARG;
+  const DgEnsembleState& E = h->ens;
+  if (E.mon_TB <= 0) { h->err = "no closed-loop launch with the monitor on has run"; return DGSQP_E_ARG; }
+  if (!clearance || !box_excess || !hit_step) { h->err = "monitor: null argument"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(clearance, E.clearance.p, sizeof(double) * (size_t)E.mon_TB, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(box_excess, E.box_excess.p, sizeof(double) * (size_t)E.mon_TB, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(hit_step, E.hit_step.p, sizeof(int32_t) * (size_t)E.mon_B, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
-// DgPlantDev argument when the handle has a plant.
+// DgPlantDev argument when the handle has a plant and a DgEnsembleDev when one of the further settings is on as well.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1092,6 +1243,19 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (B == 0) return DGSQP_OK;
   if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
+  }
+  const bool further = h->ens.any();
+  if (further && !h->plant.set) {
+    h->err = std::string(h->ens.B > 0 ? "plant ensemble" : h->ens.est_T > 0 ? "estimate noise" : "monitor") + ": no plant set for this launch";
+    return DGSQP_E_ARG;
+  }
+  {
+    const DgEnsembleState& E = h->ens;
+    if (E.B > 0 && E.B != B) { h->err = "plant ensemble: launch of B = " + std::to_string(B) + " chains, the ensemble holds " + std::to_string(E.B); return DGSQP_E_ARG; }
+    if (E.est_T > 0 && (E.est_T != T || E.est_B != B)) {
+      h->err = "estimate noise: launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the noise was set for T = " + std::to_string(E.est_T) + ", B = " + std::to_string(E.est_B);
+      return DGSQP_E_ARG;
+    }
   }
   HIPCHK(h, hipSetDevice(h->device));
   // Step-major arrays: T x B of every record, one more slice of the state and warm-start chains; c = scenarios per record, keep = the
@@ -1119,13 +1283,16 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   cl.x_step = x_out ? B * (int64_t)h->rec[DG_X].per : 0;
   cl.steps_done = (int32_t*)S.p[DG_DONE];
   DgPlantDev pd{};
+  DgEnsembleDev ex{};
   if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
+  if (further) { const int rc = ensemble_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->plant.set) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd);
+    if (further) hipLaunchKernelGGL(dg_closed_loop_kernel<DgEnsembleDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, ex);
+    else if (h->plant.set) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd);
     else hipLaunchKernelGGL(dg_closed_loop_kernel<>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
     HIPCHK(h, hipGetLastError());
     h->launch_stream = h->stream;

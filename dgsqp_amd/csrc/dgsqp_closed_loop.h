@@ -25,13 +25,44 @@ struct DgPlantDev {
   double* u_plant;          // [T][B][S][nu]  the inputs the plant integrated under
 };
 
+// The further settings of a launch with a plant (dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise, dgsqp_set_monitor): the pack type of
+// the third instantiation of dg_closed_loop_kernel.  A launch that uses none of them is handed a DgPlantDev and runs what it always ran.
+struct DgEnsembleDev {
+  DgPlantDev pd;
+  int64_t B;                          // chains of the launch: records are indexed by the CHAIN b, never by the workgroup
+  const dgsqp_vehicle_t* vehicles;    // [B][M] chain b's vehicle records, or null (every chain runs pd.P)
+  const int32_t* delay;               // [B][M][DGSQP_NUA] chain b's delays, or null (pd.P's)
+  dgsqp_plant_t* wg_plant;            // [grid] the plant of the chain a workgroup carries: filled when the chain starts (with vehicles only)
+  const double* v;                    // [T][B][nq] estimate noise, or null (the solves start from the true state)
+  double* q_est;                      // [T][B][nq] q + v, what solve t starts from
+  int monitor;                        // 0 off, 1 record, 2 record and stop
+  double* mon_scratch;                // [grid][S][M][3] per simulation step and agent: position (2), the agent's own box excess
+  double* clearance;                  // [T][B]
+  double* box_excess;                 // [T][B]
+  int32_t* hit_step;                  // [B], -1 until the chain's first hit
+};
+
+// Agent a's monitor record of one simulation step, from its state block z: the position and the largest excess over the GAME's bounds
+// (-inf: no finite bound; NaN: an entry of z is not finite).  One lane, no cross-lane operation.
+__device__ inline void dev_monitor_store(const dgsqp_agent_t& game, int nqa, const double* z, double* rec) {
+  double ex = -INFINITY;
+  bool fin = true;
+  for (int i = 0; i < nqa; i++) {
+    fin = fin && isfinite(z[i]);
+    if (isfinite(game.st_ub[i])) ex = fmax(ex, z[i] - game.st_ub[i]);
+    if (isfinite(game.st_lb[i])) ex = fmax(ex, game.st_lb[i] - z[i]);
+  }
+  rec[0] = z[0]; rec[1] = z[1]; rec[2] = fin ? ex : NAN;
+}
+
 // S simulation steps of agent a's plant from q (in place).  Simulation step `count` (counted from the chain's start) of a channel with
 // delay d > 0 integrates under entry count % d of its line -- the oldest of the last d -- and then stores u_new there (a deque of
 // length d: read [0], append); d = 0 integrates under u_new.  One plant step is dev_fd_t's arithmetic on f_c with the plant's agent
 // record, step length and sub-step count (euler: one step per simulation step, as the game's model).
-template <int NQA, bool SPL>
+// MON with a non-null `mon` ([S][M][3], the workgroup's): the agent's monitor record after every simulation step (dev_monitor_store).
+template <int NQA, bool SPL, bool MON = false>
 __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_plant_t& pl, int a, int64_t count, const double* u_new,
-                                       double* line, double* u_rec, int nu, double* qa) {
+                                       double* line, double* u_rec, int nu, double* qa, double* mon = nullptr) {
   typedef Ty<0> T;
   const dgsqp_agent_t& ag = pl.agents[a];
   const int S = pl.sim_steps, integ = pl.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : pl.substeps;
@@ -90,36 +121,42 @@ __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_pla
         for (int i = 0; i < NQA; i++) x[i] = x[i] + k1[i] * hs;
       }
     }
+    if constexpr (MON)
+      if (mon) {
+        double z[NQA];
+#pragma unroll
+        for (int i = 0; i < NQA; i++) z[i] = x[i].c[0];
+        dev_monitor_store(P.agents[a], NQA, z, mon + ((int64_t)j * P.M + a) * 3);
+      }
   }
 #pragma unroll
   for (int i = 0; i < NQA; i++) qa[i] = x[i].c[0];
 }
 
-// The plant's feedback of step t of chain b, one lane per agent: q_next = plant(q_t, stage 0 of u_t) (+ w_t).  Returns non-zero on the
-// lanes whose part of q_next is not finite.  Out of line: the solve that is inlined next to the call keeps its register allocation.
-// The caller has fenced the solve's records (u_t); q_t was written by this very lane one step ago, or by the host.
-__device__ __noinline__ int dev_plant_feedback(DgPlantDev pd, int t, int64_t tb_b, const double* q_t, const double* u_t, const double* w_t,
-                                               double* q_next) {
+// The plant's feedback of step t of chain b on the lane of agent a = TID < M: q_next = plant(q_t, stage 0 of u_t) (+ w_t) with the plant
+// `pl`.  Returns 1 when the lane's part of q_next is not finite, else 0.  `lines` and `u_plant` as in DgPlantDev, `mon` as in
+// dev_plant_agent; its record of the last simulation step is stored here, after w_t: that state is q_next.
+template <bool MON>
+__device__ inline int dev_plant_step(const dgsqp_plant_t& pl, double* lines, double* u_plant, int t, int64_t tb_b, const double* q_t,
+                                     const double* u_t, const double* w_t, double* q_next, double* mon) {
   const DgProb& D = dg_prob;
   const int a = TID;
-  if (a >= D.M) return 0;
-  const dgsqp_plant_t& pl = *pd.P;
   const int S = pl.sim_steps, nqa = D.nqa[a], qo = D.qoff[a];
-  double* line = pd.lines + ((int64_t)blockIdx.x * DGSQP_MAX_AGENTS + a) * (DGSQP_NUA * DGSQP_MAX_DELAY);
+  double* line = lines + ((int64_t)blockIdx.x * DGSQP_MAX_AGENTS + a) * (DGSQP_NUA * DGSQP_MAX_DELAY);
   if (t == 0)
     for (int i = 0; i < DGSQP_NUA * DGSQP_MAX_DELAY; i++) line[i] = 0.0;      // every chain starts with empty (zero) lines
   double u_new[DGSQP_NUA], qa[DGSQP_MAX_NQA];
   for (int j = 0; j < DGSQP_NUA; j++) u_new[j] = u_t[am_col(D, a, 0, j)];
   for (int i = 0; i < DGSQP_MAX_NQA; i++) qa[i] = i < nqa ? q_t[qo + i] : 0.0;
-  double* u_rec = pd.u_plant + tb_b * S * D.nu + a * DGSQP_NUA;
+  double* u_rec = u_plant + tb_b * S * D.nu + a * DGSQP_NUA;
   const int64_t count = (int64_t)t * S;
-  if (nqa == 4) dev_plant_agent<4, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  if (nqa == 4) dev_plant_agent<4, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   else if (D.P.track_kind == DGSQP_TRACK_SPLINE) {
-    if (nqa == 8) dev_plant_agent<8, true>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
-    else dev_plant_agent<6, true>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+    if (nqa == 8) dev_plant_agent<8, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+    else dev_plant_agent<6, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   }
-  else if (nqa == 8) dev_plant_agent<8, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
-  else dev_plant_agent<6, false>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa);
+  else if (nqa == 8) dev_plant_agent<8, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+  else dev_plant_agent<6, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   int bad = 0;
   for (int i = 0; i < DGSQP_MAX_NQA; i++)
     if (i < nqa) {
@@ -127,8 +164,98 @@ __device__ __noinline__ int dev_plant_feedback(DgPlantDev pd, int t, int64_t tb_
       if (w_t) v = v + w_t[qo + i];
       q_next[qo + i] = v;
       bad |= !isfinite(v);
+      if constexpr (MON) qa[i] = v;
     }
+  if constexpr (MON)
+    if (mon) dev_monitor_store(D.P.agents[a], nqa, qa, mon + ((int64_t)(S - 1) * D.M + a) * 3);
   return bad;
+}
+
+// The plant's feedback of step t of chain b, one lane per agent: q_next = plant(q_t, stage 0 of u_t) (+ w_t).  Returns non-zero on the
+// lanes whose part of q_next is not finite.  Out of line: the solve that is inlined next to the call keeps its register allocation.
+// The caller has fenced the solve's records (u_t); q_t was written by this very lane one step ago, or by the host.
+__device__ __noinline__ int dev_plant_feedback(DgPlantDev pd, int t, int64_t tb_b, const double* q_t, const double* u_t, const double* w_t,
+                                               double* q_next) {
+  if (TID >= dg_prob.M) return 0;
+  return dev_plant_step<false>(*pd.P, pd.lines, pd.u_plant, t, tb_b, q_t, u_t, w_t, q_next, nullptr);
+}
+
+// The same feedback with the further settings (DgEnsembleDev); every lane of the workgroup calls it.  Chain b's plant: the vehicle
+// records and delays of CHAIN b, copied into the workgroup's own dgsqp_plant_t when the chain starts -- lane a its agent's, lane 0 the
+// shared scalars -- exactly where the delay lines are cleared; the copy is read back after a fence and a barrier.  With the monitor on,
+// lane a leaves its records of the S simulation steps in the workgroup's scratch; after another fence and barrier lane 0 reduces the
+// pairs and writes clearance, box_excess and hit_step.  The return value also ends the chain (from lane 0, as 1: every
+// feedback returns 0 or 1) after a hit in mode 2.
+__device__ __noinline__ int dev_plant_feedback(DgEnsembleDev ex, int t, int64_t tb_b, const double* q_t, const double* u_t, const double* w_t,
+                                               double* q_next) {
+  const DgProb& D = dg_prob;
+  const int a = TID, M = D.M;
+  const int64_t b = tb_b - (int64_t)t * ex.B;
+  const dgsqp_plant_t* pl = ex.pd.P;
+  if (ex.vehicles) {
+    dgsqp_plant_t* mine = ex.wg_plant + blockIdx.x;
+    if (t == 0) {
+      if (a == 0) { mine->integrator = pl->integrator; mine->substeps = pl->substeps; mine->sim_steps = pl->sim_steps; mine->use_game_agents = 0; }
+      if (a < M) {
+        __builtin_memcpy(&mine->agents[a], &ex.vehicles[b * M + a], sizeof(dgsqp_vehicle_t));      // (the vehicle prefix of dgsqp_agent_t)
+        for (int ch = 0; ch < DGSQP_NUA; ch++) mine->delay[a][ch] = ex.delay ? ex.delay[(b * M + a) * DGSQP_NUA + ch] : pl->delay[a][ch];
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+    pl = mine;
+  }
+  const int S = pl->sim_steps;
+  double* mon = ex.monitor ? ex.mon_scratch + (int64_t)blockIdx.x * S * M * 3 : nullptr;
+  int bad = 0;
+  if (a < M) bad = dev_plant_step<true>(*pl, ex.pd.lines, ex.pd.u_plant, t, tb_b, q_t, u_t, w_t, q_next, mon);
+  if (!mon) return bad;
+  __threadfence_block();
+  __syncthreads();
+  if (a == 0) {
+    double cl = INFINITY, bx = -INFINITY;
+    bool fin = true;
+    int hit = -1;
+    for (int j = 0; j < S; j++)
+      for (int i = 0; i < M; i++) {
+        const double* ri = mon + ((int64_t)j * M + i) * 3;
+        fin = fin && ri[2] == ri[2];
+        bx = fmax(bx, ri[2]);
+        for (int k = i + 1; k < M; k++) {
+          const double* rk = ri + (k - i) * 3;
+          const double dx = ri[0] - rk[0], dy = ri[1] - rk[1];
+          const double d = sqrt(dx * dx + dy * dy) - (D.P.agents[i].radius + D.P.agents[k].radius);
+          cl = fmin(cl, d);
+          if (d < 0.0 && hit < 0) hit = j;
+        }
+      }
+    ex.clearance[tb_b] = fin ? cl : NAN;
+    ex.box_excess[tb_b] = fin ? bx : NAN;
+    if (hit >= 0) {
+      if (ex.hit_step[b] < 0) ex.hit_step[b] = t * S + hit;
+      if (ex.monitor == 2) bad = 1;
+    }
+  }
+  return bad;
+}
+
+// The state solve t of chain b starts from.  With estimates: the lanes write q_est[t][b] = q[t][b] + v[t][b], and the slice is handed to
+// the solve through memory (fence + barrier) like every other state; returns non-zero when it is not finite (the chain ends before
+// the solve).  Out of line, as the feedback.
+__device__ __noinline__ int dev_estimate(DgEnsembleDev ex, int64_t tb_b, const double* q_t, const double** x0) {
+  if (!ex.v) { *x0 = q_t; return 0; }
+  const int nq = dg_prob.nq;
+  double* qe = ex.q_est + tb_b * nq;
+  const double* v = ex.v + tb_b * nq;
+  int bad = 0;
+  for (int i = TID; i < nq; i += NT) {
+    const double e = q_t[i] + v[i];
+    qe[i] = e;
+    bad |= !isfinite(e);
+  }
+  __threadfence_block();
+  *x0 = qe;
+  return __syncthreads_or(bad);
 }
 
 // Per ticket b, for t = 0 .. T-1: solve from (q[t][b], uws[t][b]) exactly as dg_solve_kernel would, then
@@ -140,7 +267,11 @@ __device__ __noinline__ int dev_plant_feedback(DgPlantDev pd, int t, int64_t tb_
 // uws[t+1][b] is not written).  The records of steps that never ran keep what the host filled them with before the launch
 // (status DGSQP_NOT_RUN, zero counts, NaN).
 // No cooperative line search, no deferral, no event or iterate log: a chain's next solve depends on its last one.
-// PLANT is empty, or one DgPlantDev: the instantiation without a plant has the argument list it always had and holds nothing of the plant.
+// A non-finite q_est[t][b] (DgEnsembleDev with estimates) ends the chain BEFORE solve t: steps_done[b] = t.
+// PLANT is empty, one DgPlantDev, or one DgEnsembleDev: the instantiation without a plant has the argument list it always had and holds
+// nothing of the plant, the one with a DgPlantDev nothing of the further settings.
+template <class... PLANT> struct DgHasEstimates { static constexpr bool value = false; };
+template <> struct DgHasEstimates<DgEnsembleDev> { static constexpr bool value = true; };
 template <class... PLANT>
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket, PLANT... pd) {
@@ -168,7 +299,12 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
       SolveOutPtrs O = cl.O;
       O.u += tb * n; if (O.l) O.l += tb * nc; O.x += (int64_t)t * cl.x_step; O.cond += tb * 3; O.cost += tb * dg_prob.M;
       O.status += tb; O.iters += tb; O.qp_solves += tb;
-      c.x0 = (cgptr)(cl.q + (tb + b) * nq);
+      if constexpr (DgHasEstimates<PLANT...>::value) {
+        const double* x0 = nullptr;
+        if (dev_estimate(pd..., tb + b, cl.q + (tb + b) * nq, &x0)) break;
+        c.x0 = (cgptr)x0;
+      }
+      else c.x0 = (cgptr)(cl.q + (tb + b) * nq);
       if (dg_prob.par.variant == DGSQP_VARIANT_V2) dev_solve_v2(c, (cgptr)uws_t, b, O);
       else dev_solve(c, (cgptr)uws_t, b, O);
       // feedback.  The solve's records were stored by other lanes of this workgroup: fence + barrier before they are read back.

@@ -507,7 +507,7 @@ class DGSQP(AbstractSolver):
         return self._finish(out, t0, tm)
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
-                   keep_predictions: bool = False, plant=None) -> dict:
+                   keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -520,6 +520,15 @@ class DGSQP(AbstractSolver):
         other vehicle parameters, a finer integration, delayed inputs (``dgsqp_set_plant``; host mirror ``closed_loop.plant_feedback``) --
         for this call only; the solves themselves do not change.  The result then also holds u_plant [B, T, S, n_u], the inputs the plant
         integrated under in each of its S simulation steps (NaN where a step never ran).
+
+        With a plant (``PlantModel()`` is the identity plant) three more settings, each for this call only:
+
+        * ``plant.per_chain_configs`` / ``plant.per_chain_delay_steps``: a plant PER CHAIN (``dgsqp_set_plant_ensemble``;
+          ``closed_loop.perturbed_configs`` draws an ensemble);
+        * ``estimate_noise`` [B, steps, n_q]: solve t starts from the estimate ``q_est[:, t] = q[:, t] + estimate_noise[:, t]`` while the
+          plant advances the true ``q``; a chain whose estimate is not finite ends before that solve.  The result gains q_est [B, T, n_q];
+        * ``monitor`` True, or 'stop' to end a chain after the control step of its first contact: the result gains clearance [B, T],
+          box_excess [B, T] (over all simulation steps of a control step; host mirror ``closed_loop.monitor``) and hit_step [B].
 
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
@@ -538,27 +547,62 @@ class DGSQP(AbstractSolver):
         sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), **self._records((T, B), predictions=keep_predictions))
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
-        u_plant = None
+        u_plant = noise = q_est = mon = ensemble = None
+        if monitor not in (False, None, True, 'stop'):
+            raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
+        if plant is None and (estimate_noise is not None or monitor):
+            raise ValueError('estimate_noise and monitor need a plant (PlantModel() is the identity plant)')
+        if estimate_noise is not None:
+            noise = np.asarray(estimate_noise, dtype=np.float64)
+            if noise.shape != (B, T, self.n_q):
+                raise ValueError(f'estimate_noise must be [B, steps, n_q] = {(B, T, self.n_q)}, got {noise.shape}')
+            noise = np.ascontiguousarray(noise.transpose(1, 0, 2))
+            q_est = np.empty((T, B, self.n_q))
+        if monitor:
+            mon = dict(clearance=np.empty((T, B)), box_excess=np.empty((T, B)), hit_step=np.empty(B, np.int32))
         if plant is not None:
             pt = plant.lower(self._problem)
-            if self._lib.dgsqp_set_plant(self._h, C.byref(pt)) != 0:
-                raise ValueError('dgsqp_set_plant failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+            ensemble = plant.lower_ensemble(self._problem, B) if plant.per_chain else None
             u_plant = np.empty((T, B, pt.sim_steps, self.n_u))
+        err = lambda what: ValueError(f'{what} failed: ' + self._lib.dgsqp_last_error(self._h).decode())
         t0 = time.time()
         try:
+            if plant is not None:
+                if self._lib.dgsqp_set_plant(self._h, C.byref(pt)) != 0:
+                    raise err('dgsqp_set_plant')
+                if ensemble is not None and self._lib.dgsqp_set_plant_ensemble(self._h, B, ensemble[0], _ffi.iptr(ensemble[1])) != 0:
+                    raise err('dgsqp_set_plant_ensemble')
+                if noise is not None and self._lib.dgsqp_set_estimate_noise(self._h, T, B, _ffi.dptr(noise)) != 0:
+                    raise err('dgsqp_set_estimate_noise')
+                if mon is not None and self._lib.dgsqp_set_monitor(self._h, 2 if monitor == 'stop' else 1) != 0:
+                    raise err('dgsqp_set_monitor')
             rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
                                                    *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
             if rc != 0:
                 raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
             if u_plant is not None and B > 0 and self._lib.dgsqp_fetch_u_plant(self._h, _ffi.dptr(u_plant), u_plant.size) != 0:
                 raise RuntimeError('dgsqp_fetch_u_plant failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+            if q_est is not None and B > 0 and self._lib.dgsqp_fetch_q_est(self._h, _ffi.dptr(q_est), q_est.size) != 0:
+                raise RuntimeError('dgsqp_fetch_q_est failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+            if mon is not None and B > 0 and self._lib.dgsqp_fetch_monitor(self._h, _ffi.dptr(mon['clearance']), _ffi.dptr(mon['box_excess']),
+                                                                           _ffi.iptr(mon['hit_step'])) != 0:
+                raise RuntimeError('dgsqp_fetch_monitor failed: ' + self._lib.dgsqp_last_error(self._h).decode())
         finally:
             if plant is not None:
+                self._lib.dgsqp_set_monitor(self._h, 0)
+                self._lib.dgsqp_set_estimate_noise(self._h, 0, 0, None)
+                self._lib.dgsqp_set_plant_ensemble(self._h, 0, None, None)
                 self._lib.dgsqp_set_plant(self._h, None)
         if u_plant is not None:
             sm['u_plant'] = u_plant
+        if q_est is not None:
+            sm['q_est'] = q_est
+        if mon is not None:
+            sm['clearance'], sm['box_excess'] = mon['clearance'], mon['box_excess']
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
         out['steps_done'] = steps_done
+        if mon is not None:
+            out['hit_step'] = mon['hit_step']
         self._finish(out, t0, tm)
         out['u_applied'] = np.ascontiguousarray(out['u_pred'][:, :, 0])
         return out

@@ -21,6 +21,7 @@
 #ifndef DGSQP_H
 #define DGSQP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -358,6 +359,62 @@ int dgsqp_set_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant);
    inputs, agent after agent); NaN where a step never ran.  capacity_doubles = what out can hold (DGSQP_E_ARG when it is too small or
    when no such launch has run). */
 int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles);
+
+/*
+ * Three more settings of closed-loop launches WITH A PLANT SET (robustness studies over a distribution of vehicles).  Each has a setter
+ * for the handle's SUBSEQUENT closed-loop launches (NULL / 0 switches it off again) and, where it records something, a fetcher for what
+ * the last such launch left behind.  dgsqp_set_plant(h, plant) of the identity plant (use_game_agents = 1, sim_steps = 1, the game's
+ * integrator, no delay) is enough; switching any of them on, or launching with one of them on, while no plant is set is DGSQP_E_ARG.
+ * A launch that uses none of them runs the kernels it always ran; dgsqp_solve_batch is never affected.
+ */
+/* The vehicle fields model .. lin_Br of dgsqp_agent_t: its first 160 bytes, field for field. */
+typedef struct {
+  int32_t model, tire_model, drive_wheels, simple_slip;
+  double L_f, L_r, mass, I_z, gravity;
+  double c_dr, c_da, c_s, c_r, p_r;
+  double pac_Bf, pac_Br, pac_Cf, pac_Cr, pac_Df, pac_Dr;
+  double lin_Bf, lin_Br;
+} dgsqp_vehicle_t;
+#ifdef __cplusplus
+static_assert(sizeof(dgsqp_vehicle_t) == 160 && offsetof(dgsqp_agent_t, w_in) == sizeof(dgsqp_vehicle_t) &&
+              offsetof(dgsqp_vehicle_t, model) == offsetof(dgsqp_agent_t, model) && offsetof(dgsqp_vehicle_t, simple_slip) == offsetof(dgsqp_agent_t, simple_slip) &&
+              offsetof(dgsqp_vehicle_t, L_f) == offsetof(dgsqp_agent_t, L_f) && offsetof(dgsqp_vehicle_t, gravity) == offsetof(dgsqp_agent_t, gravity) &&
+              offsetof(dgsqp_vehicle_t, c_dr) == offsetof(dgsqp_agent_t, c_dr) && offsetof(dgsqp_vehicle_t, p_r) == offsetof(dgsqp_agent_t, p_r) &&
+              offsetof(dgsqp_vehicle_t, pac_Bf) == offsetof(dgsqp_agent_t, pac_Bf) && offsetof(dgsqp_vehicle_t, pac_Dr) == offsetof(dgsqp_agent_t, pac_Dr) &&
+              offsetof(dgsqp_vehicle_t, lin_Bf) == offsetof(dgsqp_agent_t, lin_Bf) && offsetof(dgsqp_vehicle_t, lin_Br) == offsetof(dgsqp_agent_t, lin_Br),
+              "dgsqp_vehicle_t is the vehicle prefix of dgsqp_agent_t");
+#else
+_Static_assert(sizeof(dgsqp_vehicle_t) == 160 && offsetof(dgsqp_agent_t, w_in) == sizeof(dgsqp_vehicle_t) &&
+               offsetof(dgsqp_vehicle_t, L_f) == offsetof(dgsqp_agent_t, L_f) && offsetof(dgsqp_vehicle_t, lin_Br) == offsetof(dgsqp_agent_t, lin_Br),
+               "dgsqp_vehicle_t is the vehicle prefix of dgsqp_agent_t");
+#endif
+/* A plant PER CHAIN: chain b of a launch of exactly B chains integrates with vehicles[b][a] in place of the plant's agents[a] and, when
+   delay is given, with delay[b][a][channel] in place of the plant's delay.  Integrator, substeps and sim_steps stay those of
+   dgsqp_set_plant, so u_plant keeps its shape; delay lines start empty for every chain as before.  Both arrays are copied.
+   vehicles = NULL or B = 0: off.  DGSQP_E_ARG, message starting "plant ensemble: ": no plant set, B < 0, a vehicle of another model
+   class than the game's agent, a delay outside 0 .. DGSQP_MAX_DELAY; and, from dgsqp_closed_loop_batch, a launch whose B differs. */
+int dgsqp_set_plant_ensemble(dgsqp_handle_t h, int64_t B, const dgsqp_vehicle_t* vehicles /* [B][M] */, const int32_t* delay /* [B][M][DGSQP_NUA] or NULL */);
+/* State estimates: solve t of chain b starts from q_est[t][b] = q[t][b] + v[t][b] (one fp64 add per entry) and not from q[t][b]; the plant
+   goes on advancing the TRUE q[t][b], and every solve still is, bit for bit, the one dgsqp_solve_batch performs from (q_est[t][b],
+   u_ws[t][b]).  A non-finite q_est[t][b] ends chain b BEFORE that solve: steps_done[b] = t (0 is possible) and the slice keeps the value.
+   v is copied; v = NULL or T = 0 or B = 0: off.  DGSQP_E_ARG: no plant set; from dgsqp_closed_loop_batch, a launch whose T or B differs.
+   dgsqp_fetch_q_est: q_est [T][B][n_q] of the last launch with estimates, NaN where a step never started. */
+int dgsqp_set_estimate_noise(dgsqp_handle_t h, int32_t T, int64_t B, const double* v /* [T][B][n_q] */);
+int dgsqp_fetch_q_est(dgsqp_handle_t h, double* out /* [T][B][n_q] */, int64_t capacity_doubles);
+/* Safety monitor of what happens BETWEEN control steps.  mode 0 off, 1 record, 2 record and stop.  For a control step t of chain b that
+   ran, let z_0 .. z_{S-1} be the joint states after each of the S = sim_steps simulation steps, z_{S-1} with w[t][b] added (it is
+   q[t+1][b]).  Then
+     clearance[t][b]  = min over j and pairs i < k of sqrt(dx^2 + dy^2) - (radius_i + radius_k), (dx, dy) the difference of the first two
+                        entries of the two agents' state blocks (the positions the obstacle rows read); +inf for M = 1;
+     box_excess[t][b] = max over j, agents and state entries with a finite bound of max(z - st_ub, st_lb - z), with the GAME's bounds;
+                        -inf when no entry has one;
+   both NaN for a step that never ran and for a step with a non-finite entry in one of its z_j;
+     hit_step[b]      = the smallest t * S + j whose pairwise clearance is < 0, or -1.
+   In mode 2 chain b ends after the control step of its first hit: steps_done[b] = t + 1, q[t+1][b] is kept, u_ws[t+1][b] is not written
+   (as after a non-finite state).  DGSQP_E_ARG: a mode other than 0, 1, 2; no plant set.
+   dgsqp_fetch_monitor: the records of the last launch with the monitor on; clearance, box_excess [T][B], hit_step [B], none may be NULL. */
+int dgsqp_set_monitor(dgsqp_handle_t h, int mode);
+int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess, int32_t* hit_step);
 
 /*
  * Device-resident variant used by bench.py: inputs are staged once with

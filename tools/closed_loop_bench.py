@@ -14,6 +14,14 @@ asserts that both produce identical status, num_iters and q.
 
     python tools/closed_loop_bench.py [--out profiles/closed_loop_dyn_curve_N25.txt]
     python tools/closed_loop_bench.py --plant --out profiles/closed_loop_plant_dyn_curve_N25.txt
+
+``--ensemble`` times the launch kinds of a robustness study instead, each ``--repeats`` times, alternated, after one warm-up each:
+``plain`` (no plant), ``plant`` ((c)'s plant), ``ensemble`` (that plant with a vehicle per chain: mass, drag and tyre D +-10 %, and a
+delay per chain), ``estimates`` (that plant, solves from q + 1e-3 N(0, 1)), and the last two with the monitor recording
+(``ensemble+monitor``, ``estimates+monitor``).  ``--kinds`` restricts the list (a library without the newer entry points can still time
+``plain,plant``), ``--label`` names the build in the output, ``--append`` adds to ``--out`` instead of replacing it.
+
+    python tools/closed_loop_bench.py --ensemble --repeats 5 --out profiles/closed_loop_ensemble_dyn_curve_N25.txt
 """
 import argparse
 import pathlib
@@ -51,6 +59,54 @@ def host_loop(s, x0, u_am, T):
     return dict(q=q, status=status, num_iters=iters, kernel_ms=kernel_ms)
 
 
+KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor')
+
+
+def ensemble_bench(args, g, s, x0, u_am):
+    """The launch kinds of ``--ensemble``; returns the report's lines."""
+    import copy
+    from dgsqp_amd import closed_loop
+    B, T = args.batch, args.steps
+    kinds = [k for k in args.kinds.split(',') if k]
+    unknown = [k for k in kinds if k not in KINDS]
+    if unknown:
+        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS}')
+    base = dict(method='rk4', M=10, sim_steps=2)
+    calls = {'plain': lambda: s.step_batch(x0, u_am, T)}
+    plant = closed_loop.PlantModel(delay_steps=[[0, 1], [0, 0]], **base)
+    calls['plant'] = lambda: s.step_batch(x0, u_am, T, plant=plant)
+    if any(k not in ('plain', 'plant') for k in kinds):
+        cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
+        spread = dict(mass=0.1, drag_coefficient=0.1, pacejka_d_front=0.1, pacejka_d_rear=0.1)
+        delays = np.random.default_rng(args.seed).integers(0, 3, size=(B, len(cfgs), 2))
+        ens = closed_loop.PlantModel(per_chain_configs=closed_loop.perturbed_configs(cfgs, spread, B, args.seed), per_chain_delay_steps=delays, **base)
+        v = 1e-3 * np.random.default_rng(args.seed + 1).standard_normal((B, T, s.n_q))
+        calls['ensemble'] = lambda: s.step_batch(x0, u_am, T, plant=ens)
+        calls['ensemble+monitor'] = lambda: s.step_batch(x0, u_am, T, plant=ens, monitor=True)
+        calls['estimates'] = lambda: s.step_batch(x0, u_am, T, plant=plant, estimate_noise=v)
+        calls['estimates+monitor'] = lambda: s.step_batch(x0, u_am, T, plant=plant, estimate_noise=v, monitor=True)
+    wall, kern, last = {k: [] for k in kinds}, {k: [] for k in kinds}, {}
+    for k in kinds:
+        calls[k]()                                                 # warm-up of each (code objects, buffers)
+    for _ in range(args.repeats):
+        for k in kinds:
+            t0 = time.perf_counter()
+            r = calls[k]()
+            wall[k].append(time.perf_counter() - t0)
+            kern[k].append(r['kernel_ms'] / 1e3)
+            last[k] = r
+    ms = lambda v: f'median {np.median(v) * 1e3:8.1f} ms (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f}; spread {(max(v) - min(v)) / np.median(v) * 100:.1f} %)'
+    lines = [f'[{args.label}] closed loop, dyn_curve_N25 (BASELINE configs[1]), B = {B} chains x T = {T} steps, device-sampled inputs (seed {args.seed}); '
+             f'{args.repeats} alternated repeats of every kind after one warm-up each; plant: rk4, 10 sub-steps, 2 simulation steps per control step']
+    for k in kinds:
+        r = last[k]
+        note = f'steps run {int((r["status"] >= 0).sum())} of {B * T}, iterations per chain: mean {r["num_iters"].sum(axis=1).mean():.1f}'
+        if 'hit_step' in r:
+            note += f'; chains with a contact {int((r["hit_step"] >= 0).sum())}, mean box_excess {np.nanmean(r["box_excess"]):.4f}'
+        lines.append(f'[{args.label}] {k:18s} kernel {ms(kern[k])}; wall {ms(wall[k])}; kernel times {", ".join(f"{v * 1e3:.1f}" for v in kern[k])} ms; {note}')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=1024)
@@ -58,6 +114,10 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--plant', action='store_true', help='also time step_batch with a plant of its own (c)')
+    ap.add_argument('--ensemble', action='store_true', help='time the launch kinds of a robustness study instead (see the module docstring)')
+    ap.add_argument('--kinds', default=','.join(KINDS), help='with --ensemble: comma-separated subset of ' + ', '.join(KINDS))
+    ap.add_argument('--label', default='this build', help='with --ensemble: names the build in the report')
+    ap.add_argument('--append', action='store_true', help='with --ensemble: add to --out instead of replacing it')
     ap.add_argument('--out', default=str(ROOT / 'profiles' / 'closed_loop_dyn_curve_N25.txt'))
     args = ap.parse_args()
     from dgsqp_amd.montecarlo import dynamic_racing_game
@@ -67,6 +127,13 @@ def main():
     B, T = args.batch, args.steps
     smp = s.sample_batch(g, B, seed=args.seed)
     x0, u_am = smp['x0'], s._to_agent_major(smp['u_ws'])
+    if args.ensemble:
+        text = '\n'.join(ensemble_bench(args, g, s, x0, u_am))
+        print(text)
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, 'a' if args.append else 'w') as f:
+            f.write(text + '\n')
+        return
 
     def timed(fn):
         t0 = time.perf_counter()
