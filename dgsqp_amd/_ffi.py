@@ -91,6 +91,14 @@ class PidT(C.Structure):
     ]
 
 
+class DriversT(C.Structure):
+    """dgsqp_drivers_t: who produces each agent's command in closed-loop launches (closed_loop.Drivers lowers to it)."""
+    _fields_ = [('kind', C.c_int32 * MAX_AGENTS), ('pid', PidT * MAX_AGENTS)]
+
+
+DRIVER_GAME, DRIVER_PID, DRIVER_REPLAY = 0, 1, 2        # DGSQP_DRIVER_*
+
+
 class StatRecordT(C.Structure):
     _fields_ = [('status', C.c_int32), ('iters', C.c_int32), ('qp_solves', C.c_int32), ('rank', C.c_int32),
                 ('p_feas', C.c_double), ('comp', C.c_double), ('stat', C.c_double), ('cost', C.c_double * MAX_AGENTS)]
@@ -132,6 +140,8 @@ SIGNATURES = {
     'dgsqp_fetch_q_est': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_set_monitor': (C.c_int, [_H, C.c_int]),
     'dgsqp_fetch_monitor': (C.c_int, [_H, _PD, _PD, _PI]),
+    'dgsqp_set_drivers': (C.c_int, [_H, C.POINTER(DriversT), C.c_int32, C.c_int64, _PI, _PD, _PD]),
+    'dgsqp_fetch_u_cmd': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_stage_inputs': (C.c_int, [_H, C.c_int64, _PD, _PD]),
     'dgsqp_solve_staged': (C.c_int, [_H, _TM]),
     'dgsqp_launch_staged': (C.c_int, [_H]),

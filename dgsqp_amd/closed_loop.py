@@ -12,7 +12,12 @@ Everything here is exact data movement apart from that one add, so device and ho
 A closed-loop launch may instead run a plant of its own (``PlantModel``, ``dgsqp_set_plant``; reference
 DGSQP/dynamics/dynamics_simulator.py:11-40): the game's model class with its own vehicle parameters and integrator, several simulation
 steps per control step, every input channel behind a delay line.  ``plant_feedback`` is the documented mirror of that rule
-(``dev_plant_feedback``, csrc/dgsqp_closed_loop.h); its delay lines are data movement again, the integration is the caller's."""
+(``dev_plant_feedback``, csrc/dgsqp_closed_loop.h); its delay lines are data movement again, the integration is the caller's.
+
+A launch with a plant may also choose, per agent and per chain, who produces the command that enters the plant (``Drivers``,
+``dgsqp_set_drivers``): the game, the reference's PID lane follower run closed-loop on the true state, or a replayed sequence.
+``pid_driver_step`` and ``drive`` are the documented mirrors of that choice (``dev_pid_law`` in csrc/dgsqp_pid.h, the drivers overload of
+``dev_plant_feedback``); the command they return is what ``plant_feedback`` takes as ``u_new``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -280,3 +285,151 @@ def monitor(z: np.ndarray, radii, st_lb, st_ub, qoff):
     first = np.where(hit.any(axis=-1), hit.argmax(axis=-1), -1)
     bad = ~np.isfinite(z).all(axis=(-1, -2))
     return np.where(bad, np.nan, clearance), np.where(bad, np.nan, box), first
+
+
+DRIVER_KINDS = {'game': _ffi.DRIVER_GAME, 'pid': _ffi.DRIVER_PID, 'replay': _ffi.DRIVER_REPLAY}
+UNICYCLE = 2                    # DGSQP_MODEL_UNICYCLE: no e_y / e_psi, so no lane follower
+
+
+@dataclass
+class PidGains:
+    """The lane follower of ``dgsqp_pid_t`` (defaults: what the warm-start PID runs with): speed P gain, steering PI gains on
+    ``ey_gain (e_y - lat_ref) + e_psi``, the integrator clamp, and per input (u_a, u_steer) the magnitude limit and the largest change
+    per control step."""
+    kp_v: float = 1.0
+    kp_s: float = 1.0
+    ki_s: float = 0.005
+    ey_gain: float = 5.0
+    ei_max: float = 100.0
+    u_max: Sequence = (2.1, 0.436)
+    du_max: Sequence = (10.0, 4.5)
+
+    def fill(self, out: _ffi.PidT):
+        out.kp_v, out.kp_s, out.ki_s, out.ey_gain, out.ei_max = float(self.kp_v), float(self.kp_s), float(self.ki_s), float(self.ey_gain), float(self.ei_max)
+        for j in range(NUA):
+            out.u_max[j], out.du_max[j] = float(self.u_max[j]), float(self.du_max[j])
+        out.substeps = 1            # (not read by the driver: the plant integrates)
+
+
+def _kind_id(k) -> int:
+    if isinstance(k, str):
+        if k not in DRIVER_KINDS:
+            raise ValueError(f"driver kind {k!r} not recognized: 'game', 'pid' or 'replay'")
+        return DRIVER_KINDS[k]
+    if int(k) != k or int(k) not in DRIVER_KINDS.values():
+        raise ValueError(f'driver kind {k!r} not recognized: 0 (game), 1 (pid) or 2 (replay)')
+    return int(k)
+
+
+@dataclass
+class Drivers:
+    """Who produces the command that enters each agent's plant in ``DGSQP.step_batch(..., drivers=...)`` (``dgsqp_set_drivers``):
+
+    * ``kinds`` [M]: 'game' (stage 0 of the game's solution, as without drivers), 'pid' (the lane follower ``pid`` run closed-loop on the
+      TRUE state; 6- and 8-state models only) or 'replay' (``u_replay``), or the numbers 0, 1, 2;
+    * ``pid``: one ``PidGains`` for all agents or one per agent (default: ``PidGains()``);
+    * ``per_chain_kinds`` [B][M]: the kinds of every chain, in place of ``kinds``;
+    * ``refs`` [B][M][2]: (v_ref, lat_ref) of the PID agents per chain; None: (v, e_y) of the chain's x0, as the warm-start PID does;
+    * ``u_replay`` [B][T][n_u]: the commands of the 'replay' agents (joint inputs, agent after agent; other agents' entries are not read).
+
+    The solves do not change and the warm start stays the shifted joint solution: the game's belief about everybody."""
+    kinds: Optional[Sequence] = None
+    pid: object = None
+    per_chain_kinds: Optional[Sequence] = None
+    refs: Optional[Sequence] = None
+    u_replay: Optional[Sequence] = None
+
+    def gains(self, n_agents: int) -> list:
+        """One ``PidGains`` per agent."""
+        if self.pid is None:
+            return [PidGains() for _ in range(n_agents)]
+        if isinstance(self.pid, PidGains):
+            return [self.pid] * n_agents
+        if len(self.pid) != n_agents or not all(isinstance(p, PidGains) for p in self.pid):
+            raise ValueError(f'pid must be one PidGains or one per agent ({n_agents})')
+        return list(self.pid)
+
+    def lower(self, problem: _ffi.ProblemT, B: int, T: int):
+        """``(drivers, kind, ref, u_replay)`` for ``dgsqp_set_drivers`` with a launch of ``B`` chains and ``T`` steps: a ``DriversT``, an
+        int32 array [B, M] or None, a float64 array [B, M, 2] or None and a float64 array [T, B, n_u] (step-major, as the library takes
+        it) or None (host only); ``ValueError`` for what the library would refuse."""
+        M = int(problem.M)
+        n_u = M * NUA
+        if int(T) < 1:
+            raise ValueError(f'drivers: T must be at least 1, got {T}')
+        if int(B) < 0:
+            raise ValueError('drivers: B must not be negative')
+        kinds = [_ffi.DRIVER_GAME] * M if self.kinds is None else [_kind_id(k) for k in self.kinds]
+        if len(kinds) != M:
+            raise ValueError(f'Number of agents: {M}, but {len(kinds)} driver kinds were provided')
+        per_chain = None
+        if self.per_chain_kinds is not None:
+            if np.shape(self.per_chain_kinds) != (B, M):
+                raise ValueError(f'per_chain_kinds must be [B][M] = {(B, M)}, got {np.shape(self.per_chain_kinds)}')
+            per_chain = np.array([[_kind_id(k) for k in row] for row in self.per_chain_kinds], dtype=np.int32).reshape(B, M)
+        every = np.array([kinds], dtype=np.int32) if per_chain is None else np.concatenate((np.array([kinds], dtype=np.int32), per_chain))
+        for a in range(M):
+            if (every[:, a] == _ffi.DRIVER_PID).any() and problem.agents[a].model == UNICYCLE:
+                raise ValueError(f'PID driver for agent {a}, a unicycle: the lane follower needs e_y and e_psi (the 6- and 8-state models)')
+        ref = None
+        if self.refs is not None:
+            ref = np.ascontiguousarray(self.refs, dtype=np.float64)
+            if ref.shape != (B, M, 2):
+                raise ValueError(f'refs must be [B][M][2] = {(B, M, 2)}, got {ref.shape}')
+        rep = None
+        if self.u_replay is not None:
+            rep = np.asarray(self.u_replay, dtype=np.float64)
+            if rep.shape != (B, T, n_u):
+                raise ValueError(f'u_replay must be [B, steps, n_u] = {(B, T, n_u)}, got {rep.shape}')
+            rep = np.ascontiguousarray(rep.transpose(1, 0, 2))
+        elif (every == _ffi.DRIVER_REPLAY).any():
+            raise ValueError("a 'replay' driver needs u_replay")
+        dt = _ffi.DriversT()
+        for a, g in enumerate(self.gains(M)):
+            dt.kind[a] = kinds[a]
+            g.fill(dt.pid[a])
+        return dt, per_chain, ref, rep
+
+
+def new_pid_state(lead=()) -> np.ndarray:
+    """The lane follower's state when a chain starts: [*lead, 3] zeros (integrator, previous u_a, previous u_steer)."""
+    return np.zeros(tuple(lead) + (3,))
+
+
+def pid_driver_step(pid: PidGains, q_agent, ref, state, dt: float):
+    """One control step of the PID driver for one agent -- the host mirror of ``dev_pid_law``: the operations of ``pid.PID.solve`` in its
+    order, with Kd = 0, symmetric limits and u_ref = 0.  ``q_agent`` [n_qa] the agent's TRUE state (6- or 8-state model: v at 2, e_psi at 3
+    or 5, e_y last), ``ref`` (v_ref, lat_ref), ``state`` [3] (integrator, previous u_a, previous u_steer), ``dt`` the control step.
+    Returns ``(u [2], state [3])``; ``state`` itself is not changed."""
+    q_agent = np.asarray(q_agent, dtype=np.float64)
+    if q_agent.shape[-1] not in (6, 8):
+        raise ValueError(f'the lane follower needs e_y and e_psi: a 6- or 8-state agent, got {q_agent.shape[-1]} states')
+    v, epsi, ey = float(q_agent[2]), float(q_agent[5 if q_agent.shape[-1] == 8 else 3]), float(q_agent[-1])
+    ei, up0, up1 = (float(x) for x in state)
+    ua = -(pid.kp_v * (v - float(ref[0])))
+    e = pid.ey_gain * (ey - float(ref[1])) + epsi
+    ei = min(max(ei + e * dt, -pid.ei_max), pid.ei_max)
+    us = -(pid.kp_s * e + pid.ki_s * ei)
+    ua = min(max(min(max(ua - up0, -pid.du_max[0]), pid.du_max[0]) + up0, -pid.u_max[0]), pid.u_max[0])
+    us = min(max(min(max(us - up1, -pid.du_max[1]), pid.du_max[1]) + up1, -pid.u_max[1]), pid.u_max[1])
+    return np.array([ua, us]), np.array([ei, ua, us])
+
+
+def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None):
+    """The commands of one control step of one chain -- the host mirror of the drivers overload of ``dev_plant_feedback``.  Per agent a:
+    kind 0 takes ``u_game[2a:2a+2]`` (stage 0 of the solution), kind 1 ``pid_driver_step(gains[a], q[qoff[a]:qoff[a+1]], refs[a],
+    states[a], dt)``, kind 2 ``u_replay[2a:2a+2]``.  ``kinds`` [M], ``u_game`` [n_u], ``q`` [n_q] the TRUE state, ``refs`` [M, 2],
+    ``states`` [M, 3].  Returns ``(u_cmd [n_u], states [M, 3])``; only PID agents' states change (in the returned copy)."""
+    u_game = np.asarray(u_game, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    states = np.array(states, dtype=np.float64)
+    u_cmd = u_game.copy()
+    for a, k in enumerate(kinds):
+        k = _kind_id(k)
+        if k == _ffi.DRIVER_PID:
+            u_cmd[NUA * a:NUA * a + NUA], states[a] = pid_driver_step(gains[a], q[qoff[a]:qoff[a + 1]], refs[a], states[a], dt)
+        elif k == _ffi.DRIVER_REPLAY:
+            if u_replay is None:
+                raise ValueError("a 'replay' driver needs u_replay")
+            u_cmd[NUA * a:NUA * a + NUA] = np.asarray(u_replay, dtype=np.float64)[NUA * a:NUA * a + NUA]
+    return u_cmd, states

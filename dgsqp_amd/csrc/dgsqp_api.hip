@@ -292,6 +292,17 @@ struct DgEnsembleState {
   bool any() const { return B > 0 || est_T > 0 || monitor != 0; }
 };
 
+// The drivers of closed-loop launches with a plant (dgsqp_set_drivers) and what such a launch leaves behind for dgsqp_fetch_u_cmd.
+struct DgDriversState {
+  bool set = false;
+  int32_t T = 0;                      // the launch shape the arrays were given for
+  int64_t B = 0;
+  bool has_ref = false, has_replay = false;
+  DgBuf kind, pid, ref, u_replay;     // [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
+  DgBuf u_cmd, cmd, pid_state;        // [T][B][nu] of the last launch with drivers; per workgroup: [grid][n], [grid][M][3]
+  int64_t u_cmd_doubles = 0;          // what that launch wrote (0: none yet)
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -314,6 +325,7 @@ struct dgsqp_solver {
   DgLog trace{false}, itlog{true};
   DgPlantState plant;
   DgEnsembleState ens;
+  DgDriversState drv;
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -724,6 +736,26 @@ static int ensemble_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, 
   return DGSQP_OK;
 }
 
+// what a closed-loop launch with drivers hands the kernel on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes
+// before it reads them) and the u_cmd record, filled with NaN on h's stream.  The caller has checked the shape the drivers were set for.
+static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgEnsembleDev& ex, DgPlantDriversDev* out) {
+  DgDriversState& R = h->drv;
+  R.u_cmd_doubles = 0;
+  const size_t bytes = sizeof(double) * (size_t)TB * h->hp.nu;
+  { const int rc = buf_reserve(h, R.u_cmd, bytes); if (rc) return rc; }
+  { const int rc = buf_reserve(h, R.cmd, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }   // n per row, 2 M used: read as u_t is
+  { const int rc = buf_reserve(h, R.pid_state, sizeof(double) * (size_t)grid * h->hp.M * 3); if (rc) return rc; }
+  HIPCHK(h, hipMemsetAsync(R.u_cmd.p, 0xff, bytes, h->stream));
+  R.u_cmd_doubles = TB * h->hp.nu;
+  DgPlantDriversDev dd{};
+  dd.ex = ex;
+  dd.kind = (const int32_t*)R.kind.p; dd.pid = (const dgsqp_pid_t*)R.pid.p;
+  dd.ref = R.has_ref ? (const double*)R.ref.p : nullptr; dd.u_replay = R.has_replay ? (const double*)R.u_replay.p : nullptr;
+  dd.u_cmd = (double*)R.u_cmd.p; dd.cmd = (double*)R.cmd.p; dd.pid_state = (double*)R.pid_state.p;
+  *out = dd;
+  return DGSQP_OK;
+}
+
 // The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
 // L's first -- all of them behind one ticket queue.  `total` scenarios in all.  Leaves L marked in flight.  Everything it enqueues goes
 // to the next launch stream of the device's pool, which L records: waits, queries and timing follow that record.
@@ -815,7 +847,8 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc((void**)&h->d_coop, h->coop_bytes) != hipSuccess) return fail("hipMalloc(coop) failed");
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
   const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>};
+                           (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>,
+                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -873,7 +906,8 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->plant.dev) (void)hipFree(h->plant.dev);
   if (h->plant.lines) (void)hipFree(h->plant.lines);
   if (h->plant.u_buf) (void)hipFree(h->plant.u_buf);
-  for (DgBuf* b : {&h->ens.vehicles, &h->ens.delay, &h->ens.wg_plant, &h->ens.v, &h->ens.q_est, &h->ens.scratch, &h->ens.clearance, &h->ens.box_excess, &h->ens.hit_step})
+  for (DgBuf* b : {&h->ens.vehicles, &h->ens.delay, &h->ens.wg_plant, &h->ens.v, &h->ens.q_est, &h->ens.scratch, &h->ens.clearance, &h->ens.box_excess, &h->ens.hit_step,
+                   &h->drv.kind, &h->drv.pid, &h->drv.ref, &h->drv.u_replay, &h->drv.u_cmd, &h->drv.cmd, &h->drv.pid_state})
     if (b->p) (void)hipFree(b->p);
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1231,8 +1265,72 @@ int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess,
   return DGSQP_OK;
 }
 
+int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int64_t B, const int32_t* kind, const double* ref, const double* u_replay) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  DgDriversState& R = h->drv;
+  if (!d) { R.set = false; return DGSQP_OK; }
+  auto bad = [&](const std::string& m) { h->err = "drivers: " + m; return DGSQP_E_ARG; };
+  if (!h->plant.set) return bad("no plant set (dgsqp_set_plant first; the identity plant will do)");
+  if (T < 1) return bad("T must be at least 1, got " + std::to_string(T));
+  if (B < 0) return bad("B must not be negative");
+  const dgsqp_problem_t& P = h->hp.P;
+  const int M = P.M;
+  // the kinds of every chain: d->kind where the caller gives none per chain; both are checked, whichever the launch will read
+  std::vector<int32_t> kinds((size_t)B * M);
+  bool replay = false;
+  auto check = [&](int32_t k, int a, const std::string& where) {
+    if (k != DGSQP_DRIVER_GAME && k != DGSQP_DRIVER_PID && k != DGSQP_DRIVER_REPLAY)
+      return bad("kind of " + where + " is " + std::to_string(k) + ", allowed 0 (game), 1 (PID), 2 (replay)");
+    if (k == DGSQP_DRIVER_PID && P.agents[a].model == DGSQP_MODEL_UNICYCLE)
+      return bad("PID driver for " + where + ", a unicycle: the lane follower needs e_y and e_psi (the 6- and 8-state models)");
+    replay = replay || k == DGSQP_DRIVER_REPLAY;
+    return DGSQP_OK;
+  };
+  for (int a = 0; a < M; a++) { const int rc = check(d->kind[a], a, "agent " + std::to_string(a)); if (rc) return rc; }
+  for (int64_t b = 0; b < B; b++)
+    for (int a = 0; a < M; a++) {
+      const int32_t k = kind ? kind[b * M + a] : d->kind[a];
+      if (kind) { const int rc = check(k, a, "chain " + std::to_string(b) + ", agent " + std::to_string(a)); if (rc) return rc; }
+      kinds[(size_t)b * M + a] = k;
+    }
+  if (replay && !u_replay) return bad("a REPLAY driver needs u_replay");
+  R.set = false;
+  const size_t nk = sizeof(int32_t) * kinds.size(), nr = sizeof(double) * (size_t)B * M * 2, nu = sizeof(double) * (size_t)T * (size_t)B * h->hp.nu;
+  { const int rc = buf_reserve(h, R.pid, sizeof(d->pid)); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(R.pid.p, d->pid, sizeof(d->pid), hipMemcpyHostToDevice));
+  if (B > 0) {
+    { const int rc = buf_reserve(h, R.kind, nk); if (rc) return rc; }
+    HIPCHK(h, hipMemcpy(R.kind.p, kinds.data(), nk, hipMemcpyHostToDevice));
+    if (ref) {
+      { const int rc = buf_reserve(h, R.ref, nr); if (rc) return rc; }
+      HIPCHK(h, hipMemcpy(R.ref.p, ref, nr, hipMemcpyHostToDevice));
+    }
+    if (u_replay) {
+      { const int rc = buf_reserve(h, R.u_replay, nu); if (rc) return rc; }
+      HIPCHK(h, hipMemcpy(R.u_replay.p, u_replay, nu, hipMemcpyHostToDevice));
+    }
+  }
+  R.has_ref = ref != nullptr; R.has_replay = u_replay != nullptr;
+  R.T = T; R.B = B;
+  R.set = true;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_u_cmd(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  if (!h) return DGSQP_E_ARG;
+  const DgDriversState& R = h->drv;
+  if (!out || !R.u_cmd.p || R.u_cmd_doubles <= 0) { h->err = "no closed-loop launch with drivers has run"; return DGSQP_E_ARG; }
+  if (capacity_doubles < R.u_cmd_doubles) { h->err = "u_cmd buffer too small: need " + std::to_string(R.u_cmd_doubles) + " doubles"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(out, R.u_cmd.p, sizeof(double) * (size_t)R.u_cmd_doubles, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
-// DgPlantDev argument when the handle has a plant and a DgEnsembleDev when one of the further settings is on as well.
+// DgPlantDev argument when the handle has a plant, a DgEnsembleDev when one of the further settings is on as well, and a DgPlantDriversDev
+// when drivers are set.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1247,6 +1345,12 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   const bool further = h->ens.any();
   if (further && !h->plant.set) {
     h->err = std::string(h->ens.B > 0 ? "plant ensemble" : h->ens.est_T > 0 ? "estimate noise" : "monitor") + ": no plant set for this launch";
+    return DGSQP_E_ARG;
+  }
+  const bool drivers = h->drv.set;
+  if (drivers && !h->plant.set) { h->err = "drivers: no plant set for this launch"; return DGSQP_E_ARG; }
+  if (drivers && (h->drv.T != T || h->drv.B != B)) {
+    h->err = "drivers: launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the drivers were set for T = " + std::to_string(h->drv.T) + ", B = " + std::to_string(h->drv.B);
     return DGSQP_E_ARG;
   }
   {
@@ -1285,13 +1389,16 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   DgPlantDev pd{};
   DgEnsembleDev ex{};
   if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
-  if (further) { const int rc = ensemble_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
+  DgPlantDriversDev dd{};
+  if (further || drivers) { const int rc = ensemble_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
+  if (drivers) { const int rc = drivers_for_launch(h, grid, TB, ex, &dd); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (further) hipLaunchKernelGGL(dg_closed_loop_kernel<DgEnsembleDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, ex);
+    if (drivers) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDriversDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, dd);
+    else if (further) hipLaunchKernelGGL(dg_closed_loop_kernel<DgEnsembleDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, ex);
     else if (h->plant.set) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd);
     else hipLaunchKernelGGL(dg_closed_loop_kernel<>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
     HIPCHK(h, hipGetLastError());

@@ -2,6 +2,7 @@
 // (DGSQP.py:283-297), so that a launch is bounded by its longest CHAIN and no intermediate state leaves the device.
 // Included by dgsqp_api.hip after dg_solve_kernel; host mirror of the feedback rule: dgsqp_amd/closed_loop.py.
 #pragma once
+#include "dgsqp_pid.h"      // dev_pid_law, the PID driver's law
 
 // Step-major buffers of one closed-loop launch.  q and uws are FED BACK: the workgroup writes slice t + 1 and its own next solve
 // reads it, so they are plain pointers -- never const, never __restrict__ -- and every slice has an address of its own.
@@ -40,6 +41,23 @@ struct DgEnsembleDev {
   double* clearance;                  // [T][B]
   double* box_excess;                 // [T][B]
   int32_t* hit_step;                  // [B], -1 until the chain's first hit
+};
+
+// Drivers (dgsqp_set_drivers): who produces the command entering agent a's plant at control step t of chain b -- the game (stage 0 of its
+// solution), the lane follower dev_pid_law closed-loop on the TRUE state, or the caller's u_replay.  The pack of the fourth instantiation of
+// dg_closed_loop_kernel; it wraps DgEnsembleDev, so the further settings combine with drivers.  cmd and pid_state are written and read by
+// the same lane (lane a for agent a), like lines: plain pointers.  The NAME matters: LDS kernel ids follow the mangled kernel names, and this
+// one sorts behind dg_closed_loop_kernel<DgEnsembleDev>, which so keeps its id and with it its register allocation.  To check after a rename:
+// compile --offload-device-only -S before and after (same -cuid, also -DDG_BLOCK=256); that kernel's instructions must not change.
+struct DgPlantDriversDev {
+  DgEnsembleDev ex;
+  const int32_t* kind;                // [B][M] DGSQP_DRIVER_*
+  const dgsqp_pid_t* pid;             // [M] the gains of agent a's lane follower (read for PID agents)
+  const double* ref;                  // [B][M][2] (v_ref, lat_ref), or null: from the chain's x0 = q[0][b], as the warm-start PID does
+  const double* u_replay;             // [T][B][nu], or null (no REPLAY agent)
+  double* u_cmd;                      // [T][B][nu] the command each agent's plant received
+  double* cmd;                        // [grid][n] the workgroup's commands where the plant step reads stage 0 of u_t (agent-major)
+  double* pid_state;                  // [grid][M][3] ei, previous u_a, previous u_steer: cleared when a chain starts
 };
 
 // Agent a's monitor record of one simulation step, from its state block z: the position and the largest excess over the GAME's bounds
@@ -239,6 +257,44 @@ __device__ __noinline__ int dev_plant_feedback(DgEnsembleDev ex, int t, int64_t 
   return bad;
 }
 
+// The same feedback with drivers: lane a < M forms its agent's command, stores it to u_cmd[t][b] and to the workgroup's cmd, which is then
+// handed to the feedback above in place of u_t -- everything downstream of the command (delay lines, the S simulation steps, u_plant, the
+// monitor) is that function's.  The PID driver reads the TRUE state q_t, also when the solves start from estimates; its dt is the control
+// step; its state is cleared where the delay lines are (t == 0), so a workgroup's next chain starts from zero like every other.
+__device__ __noinline__ int dev_plant_feedback(DgPlantDriversDev dd, int t, int64_t tb_b, const double* q_t, const double* u_t, const double* w_t,
+                                               double* q_next) {
+  const DgProb& D = dg_prob;
+  const int a = TID, M = D.M;
+  double* cmd = dd.cmd + (int64_t)blockIdx.x * D.n;
+  if (a < M) {
+    const int64_t b = tb_b - (int64_t)t * dd.ex.B;
+    const int kind = dd.kind[b * M + a];
+    double* st = dd.pid_state + ((int64_t)blockIdx.x * M + a) * 3;
+    if (t == 0) { st[0] = 0.0; st[1] = 0.0; st[2] = 0.0; }
+    double c[DGSQP_NUA];
+    if (kind == DGSQP_DRIVER_PID) {
+      const int nqa = D.nqa[a], epsi = nqa == 8 ? 5 : 3, ey = nqa - 1;        // (state layout: dev_pid_agent)
+      const double* qa = q_t + D.qoff[a];
+      const double* q0 = qa - (int64_t)t * dd.ex.B * D.nq;                     // the chain's x0: slice 0 of q
+      const double* ref = dd.ref ? dd.ref + (b * M + a) * 2 : nullptr;
+      const double v_ref = ref ? ref[0] : q0[2], lat_ref = ref ? ref[1] : q0[ey];
+      double ei = st[0], up0 = st[1], up1 = st[2];
+      dev_pid_law(dd.pid[a], D.P.dt, qa[2], v_ref, qa[ey], lat_ref, qa[epsi], ei, up0, up1);
+      st[0] = ei; st[1] = up0; st[2] = up1;
+      c[0] = up0; c[1] = up1;
+    }
+    else if (kind == DGSQP_DRIVER_REPLAY)
+      for (int j = 0; j < DGSQP_NUA; j++) c[j] = dd.u_replay[tb_b * D.nu + a * DGSQP_NUA + j];
+    else
+      for (int j = 0; j < DGSQP_NUA; j++) c[j] = u_t[am_col(D, a, 0, j)];
+    for (int j = 0; j < DGSQP_NUA; j++) {
+      dd.u_cmd[tb_b * D.nu + a * DGSQP_NUA + j] = c[j];
+      cmd[am_col(D, a, 0, j)] = c[j];
+    }
+  }
+  return dev_plant_feedback(dd.ex, t, tb_b, q_t, cmd, w_t, q_next);
+}
+
 // The state solve t of chain b starts from.  With estimates: the lanes write q_est[t][b] = q[t][b] + v[t][b], and the slice is handed to
 // the solve through memory (fence + barrier) like every other state; returns non-zero when it is not finite (the chain ends before
 // the solve).  Out of line, as the feedback.
@@ -258,9 +314,14 @@ __device__ __noinline__ int dev_estimate(DgEnsembleDev ex, int64_t tb_b, const d
   return __syncthreads_or(bad);
 }
 
+__device__ __noinline__ int dev_estimate(DgPlantDriversDev dd, int64_t tb_b, const double* q_t, const double** x0) {
+  return dev_estimate(dd.ex, tb_b, q_t, x0);
+}
+
 // Per ticket b, for t = 0 .. T-1: solve from (q[t][b], uws[t][b]) exactly as dg_solve_kernel would, then
 //   q[t+1][b]   = x_t[b][1] (+ w[t][b])                          the game's own discrete model is the plant
 //            or = plant(q[t][b], stage 0 of u_t[b]) (+ w[t][b])  with a PLANT: dev_plant_feedback
+//            or = plant(q[t][b], u_cmd[t][b]) (+ w[t][b])         with DRIVERS: each agent's command is the game's, a PID's or replayed
 //   uws[t+1][b] = shift(u_t[b]), or uws[t][b] after 'diverged' / 'qp_fail'   (DGSQP.py:293-295)
 // shift, per agent: row k takes row k + 1, the last row is repeated (np.vstack((u_pred[1:], u_pred[-1]))).
 // A non-finite q[t+1][b] ends the chain: steps_done[b] = t + 1, and no solve starts from such a state (q[t+1][b] keeps that state,
@@ -268,10 +329,12 @@ __device__ __noinline__ int dev_estimate(DgEnsembleDev ex, int64_t tb_b, const d
 // (status DGSQP_NOT_RUN, zero counts, NaN).
 // No cooperative line search, no deferral, no event or iterate log: a chain's next solve depends on its last one.
 // A non-finite q_est[t][b] (DgEnsembleDev with estimates) ends the chain BEFORE solve t: steps_done[b] = t.
-// PLANT is empty, one DgPlantDev, or one DgEnsembleDev: the instantiation without a plant has the argument list it always had and holds
-// nothing of the plant, the one with a DgPlantDev nothing of the further settings.
+// PLANT is empty, one DgPlantDev, one DgEnsembleDev, or one DgPlantDriversDev: the instantiation without a plant has the argument list it always
+// had and holds nothing of the plant, the one with a DgPlantDev nothing of the further settings, the one with a DgEnsembleDev nothing of
+// the drivers.
 template <class... PLANT> struct DgHasEstimates { static constexpr bool value = false; };
 template <> struct DgHasEstimates<DgEnsembleDev> { static constexpr bool value = true; };
+template <> struct DgHasEstimates<DgPlantDriversDev> { static constexpr bool value = true; };
 template <class... PLANT>
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket, PLANT... pd) {

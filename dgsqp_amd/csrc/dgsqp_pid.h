@@ -4,6 +4,20 @@
 // continuous model integrated with rk4 (10 sub-steps per dt by default), the same f_c the solver differentiates.
 #pragma once
 
+// One step of the lane follower (PID.solve): speed P controller on v - v_ref, steering PI on ey_gain (e_y - lat_ref) + e_psi; rate
+// saturation first, against the previous command (up0, up1), then magnitude.  ei, up0 and up1 are the law's state: the integrator and the
+// command it has just formed.  Stated once: the warm start below and the PID driver of closed-loop launches (dgsqp_closed_loop.h) run it.
+__device__ inline void dev_pid_law(const dgsqp_pid_t& pid, double dt, double v, double v_ref, double ey, double lat_ref, double epsi,
+                                   double& ei, double& up0, double& up1) {
+  double ua = -(pid.kp_v * (v - v_ref));
+  const double e = pid.ey_gain * (ey - lat_ref) + epsi;
+  ei = fmin(fmax(ei + e * dt, -pid.ei_max), pid.ei_max);
+  double us = -(pid.kp_s * e + pid.ki_s * ei);
+  ua = fmin(fmax(fmin(fmax(ua - up0, -pid.du_max[0]), pid.du_max[0]) + up0, -pid.u_max[0]), pid.u_max[0]);
+  us = fmin(fmax(fmin(fmax(us - up1, -pid.du_max[1]), pid.du_max[1]) + up1, -pid.u_max[1]), pid.u_max[1]);
+  up0 = ua; up1 = us;
+}
+
 template <int NQA, bool SPL = false>
 __device__ inline void dev_pid_agent(const DgProb& D, int a, cgptr q0, const dgsqp_pid_t& pid, gptr u_out, gptr q_out) {
   typedef Ty<0> T;
@@ -19,14 +33,8 @@ __device__ inline void dev_pid_agent(const DgProb& D, int a, cgptr q0, const dgs
   double ei = 0.0, up0 = 0.0, up1 = 0.0;
   const double dt = P.dt, h = dt / pid.substeps;
   for (int k = 0; k < D.N; k++) {
-    // PID.solve: speed P controller, steering PI on ey_gain (e_y - e_y0) + e_psi; rate saturation first, then magnitude
-    double ua = -(pid.kp_v * (q[V].c[0] - v_ref));
-    const double e = pid.ey_gain * (q[EY].c[0] - lat_ref) + q[EPSI].c[0];
-    ei = fmin(fmax(ei + e * dt, -pid.ei_max), pid.ei_max);
-    double us = -(pid.kp_s * e + pid.ki_s * ei);
-    ua = fmin(fmax(fmin(fmax(ua - up0, -pid.du_max[0]), pid.du_max[0]) + up0, -pid.u_max[0]), pid.u_max[0]);
-    us = fmin(fmax(fmin(fmax(us - up1, -pid.du_max[1]), pid.du_max[1]) + up1, -pid.u_max[1]), pid.u_max[1]);
-    up0 = ua; up1 = us;
+    dev_pid_law(pid, dt, q[V].c[0], v_ref, q[EY].c[0], lat_ref, q[EPSI].c[0], ei, up0, up1);
+    const double ua = up0, us = up1;
     u_out[am_col(D, a, k, 0)] = ua;
     u_out[am_col(D, a, k, 1)] = us;
     u[0].c[0] = ua; u[1].c[0] = us;

@@ -507,7 +507,7 @@ class DGSQP(AbstractSolver):
         return self._finish(out, t0, tm)
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
-                   keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False) -> dict:
+                   keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False, drivers=None) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -530,6 +530,12 @@ class DGSQP(AbstractSolver):
         * ``monitor`` True, or 'stop' to end a chain after the control step of its first contact: the result gains clearance [B, T],
           box_excess [B, T] (over all simulation steps of a control step; host mirror ``closed_loop.monitor``) and hit_step [B].
 
+        ``drivers`` (``closed_loop.Drivers``; with ``plant=None`` the identity plant ``PlantModel()`` is used), for this call only: who
+        produces the command that enters each agent's plant -- the game (stage 0 of its solution, as without drivers), the PID lane
+        follower run closed-loop on the true state, or a replayed sequence (``dgsqp_set_drivers``; host mirror ``closed_loop.drive``).
+        The solves and the warm-start chain do not change.  The result gains u_cmd [B, T, n_u], the commands the plants received (NaN
+        where a step never ran); u_applied stays stage 0 of the prediction.
+
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
         steps_done [B], time, kernel_ms; with ``keep_predictions`` also x [B, T, N+1, n_q] and l [B, T, n_c]."""
@@ -547,7 +553,10 @@ class DGSQP(AbstractSolver):
         sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), **self._records((T, B), predictions=keep_predictions))
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
-        u_plant = noise = q_est = mon = ensemble = None
+        u_plant = noise = q_est = mon = ensemble = drv = u_cmd = None
+        if drivers is not None and plant is None:
+            from .closed_loop import PlantModel
+            plant = PlantModel()
         if monitor not in (False, None, True, 'stop'):
             raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
         if plant is None and (estimate_noise is not None or monitor):
@@ -564,6 +573,9 @@ class DGSQP(AbstractSolver):
             pt = plant.lower(self._problem)
             ensemble = plant.lower_ensemble(self._problem, B) if plant.per_chain else None
             u_plant = np.empty((T, B, pt.sim_steps, self.n_u))
+        if drivers is not None:
+            drv = drivers.lower(self._problem, B, T)
+            u_cmd = np.empty((T, B, self.n_u))
         err = lambda what: ValueError(f'{what} failed: ' + self._lib.dgsqp_last_error(self._h).decode())
         t0 = time.time()
         try:
@@ -576,6 +588,8 @@ class DGSQP(AbstractSolver):
                     raise err('dgsqp_set_estimate_noise')
                 if mon is not None and self._lib.dgsqp_set_monitor(self._h, 2 if monitor == 'stop' else 1) != 0:
                     raise err('dgsqp_set_monitor')
+                if drv is not None and self._lib.dgsqp_set_drivers(self._h, C.byref(drv[0]), T, B, _ffi.iptr(drv[1]), _ffi.dptr(drv[2]), _ffi.dptr(drv[3])) != 0:
+                    raise err('dgsqp_set_drivers')
             rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
                                                    *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
             if rc != 0:
@@ -587,8 +601,11 @@ class DGSQP(AbstractSolver):
             if mon is not None and B > 0 and self._lib.dgsqp_fetch_monitor(self._h, _ffi.dptr(mon['clearance']), _ffi.dptr(mon['box_excess']),
                                                                            _ffi.iptr(mon['hit_step'])) != 0:
                 raise RuntimeError('dgsqp_fetch_monitor failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+            if u_cmd is not None and B > 0 and self._lib.dgsqp_fetch_u_cmd(self._h, _ffi.dptr(u_cmd), u_cmd.size) != 0:
+                raise RuntimeError('dgsqp_fetch_u_cmd failed: ' + self._lib.dgsqp_last_error(self._h).decode())
         finally:
             if plant is not None:
+                self._lib.dgsqp_set_drivers(self._h, None, 0, 0, None, None, None)
                 self._lib.dgsqp_set_monitor(self._h, 0)
                 self._lib.dgsqp_set_estimate_noise(self._h, 0, 0, None)
                 self._lib.dgsqp_set_plant_ensemble(self._h, 0, None, None)
@@ -597,6 +614,8 @@ class DGSQP(AbstractSolver):
             sm['u_plant'] = u_plant
         if q_est is not None:
             sm['q_est'] = q_est
+        if u_cmd is not None:
+            sm['u_cmd'] = u_cmd
         if mon is not None:
             sm['clearance'], sm['box_excess'] = mon['clearance'], mon['box_excess']
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}

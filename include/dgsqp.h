@@ -417,6 +417,41 @@ int dgsqp_set_monitor(dgsqp_handle_t h, int mode);
 int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess, int32_t* hit_step);
 
 /*
+ * Drivers: who produces the command that enters agent a's plant at control step t of chain b (closed-loop launches WITH A PLANT SET).
+ * Without drivers every agent applies stage 0 of the joint game solution: self-play.  With them the ego car can apply its part of the
+ * solution while the others are driven by a lane follower or by a recorded drive (the reference's closed-loop script drives its cars by
+ * their own controllers: scripts/race/race_main.py).  Everything downstream of the command is unchanged: it passes through the agent's
+ * delay lines, is held for the sim_steps simulation steps, and u_plant records what was integrated.  The solves do not change: solve t
+ * still is, bit for bit, the dgsqp_solve_batch solve from (q[t][b] or q_est[t][b], u_ws[t][b]), and the warm start still is the shifted
+ * JOINT solution -- the game's belief about everybody, drivers included.
+ *   DGSQP_DRIVER_GAME    stage 0 of the game's solution, as without drivers.
+ *   DGSQP_DRIVER_PID     the lane follower of dgsqp_pid_t run closed-loop on the TRUE state q[t][b], also when the solves start from
+ *                        estimates: speed P control on v - v_ref, steering PI control on ey_gain (e_y - lat_ref) + e_psi; rate
+ *                        saturation first, against the agent's previous command, then magnitude.  The law's dt is the control step.  The
+ *                        integrator and the previous command persist along the chain and start at 0 for every chain.  `substeps` is
+ *                        not read.  For the 6- and 8-state models only (the unicycle has no e_y / e_psi).
+ *   DGSQP_DRIVER_REPLAY  u_replay[t][b] of that agent.  A non-finite entry makes the next state non-finite and ends that chain.
+ */
+enum { DGSQP_DRIVER_GAME = 0, DGSQP_DRIVER_PID = 1, DGSQP_DRIVER_REPLAY = 2 };
+typedef struct {
+  int32_t kind[DGSQP_MAX_AGENTS];     /* DGSQP_DRIVER_*; entries beyond M are not read */
+  dgsqp_pid_t pid[DGSQP_MAX_AGENTS];  /* read for PID agents */
+} dgsqp_drivers_t;
+/* The drivers of the handle's SUBSEQUENT closed-loop launches of exactly T steps and B chains; every array is copied.  d = NULL: off.
+   kind: the kinds per chain, or NULL for d->kind in every chain.  ref: (v_ref, lat_ref) per chain and agent for the PID agents, or NULL
+   for (v, e_y) of the chain's x0, as the warm-start PID takes them.  u_replay: joint inputs, agent after agent; only the entries of
+   REPLAY agents are read.  DGSQP_E_ARG, message starting "drivers: ": no plant set, a kind outside 0 .. 2 (in d or in kind), PID for a
+   unicycle agent, a REPLAY kind anywhere without u_replay, T < 1 or B < 0; and, from dgsqp_closed_loop_batch, a launch whose T or B
+   differs.  dgsqp_solve_batch and launches without drivers are not affected.
+   dgsqp_fetch_u_cmd: the commands of the last launch with drivers, [T][B][n_u]; NaN where a step never ran; for a GAME agent stage 0 of
+   u.  capacity_doubles = what out can hold (DGSQP_E_ARG when it is too small or when no such launch has run). */
+int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int64_t B,
+                      const int32_t* kind     /* [B][M] or NULL: d->kind for every chain */,
+                      const double*  ref      /* [B][M][2] or NULL: from x0 */,
+                      const double*  u_replay /* [T][B][n_u] or NULL; only REPLAY agents' entries are read */);
+int dgsqp_fetch_u_cmd(dgsqp_handle_t h, double* out /* [T][B][n_u] */, int64_t capacity_doubles);
+
+/*
  * Device-resident variant used by bench.py: inputs are staged once with
  * dgsqp_stage_inputs(); dgsqp_solve_staged() runs only the solve kernel on
  * the handle's stream; dgsqp_fetch_results() copies results back.

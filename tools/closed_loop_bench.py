@@ -18,7 +18,9 @@ asserts that both produce identical status, num_iters and q.
 ``--ensemble`` times the launch kinds of a robustness study instead, each ``--repeats`` times, alternated, after one warm-up each:
 ``plain`` (no plant), ``plant`` ((c)'s plant), ``ensemble`` (that plant with a vehicle per chain: mass, drag and tyre D +-10 %, and a
 delay per chain), ``estimates`` (that plant, solves from q + 1e-3 N(0, 1)), and the last two with the monitor recording
-(``ensemble+monitor``, ``estimates+monitor``).  ``--kinds`` restricts the list (a library without the newer entry points can still time
+(``ensemble+monitor``, ``estimates+monitor``); and two launches with drivers (``closed_loop.Drivers``) on that plant: ``pid`` (car 2 on the
+PID lane follower with its default gains, references from x0) and ``replay`` (car 2 replays the commands the game gave it in the ``plant``
+launch: the same chains as ``plant``, bit for bit, through the drivers' kernel).  ``--kinds`` restricts the list (a library without the newer entry points can still time
 ``plain,plant``), ``--label`` names the build in the output, ``--append`` adds to ``--out`` instead of replacing it.
 
     python tools/closed_loop_bench.py --ensemble --repeats 5 --out profiles/closed_loop_ensemble_dyn_curve_N25.txt
@@ -59,7 +61,7 @@ def host_loop(s, x0, u_am, T):
     return dict(q=q, status=status, num_iters=iters, kernel_ms=kernel_ms)
 
 
-KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor')
+KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor', 'pid', 'replay')
 
 
 def ensemble_bench(args, g, s, x0, u_am):
@@ -75,7 +77,17 @@ def ensemble_bench(args, g, s, x0, u_am):
     calls = {'plain': lambda: s.step_batch(x0, u_am, T)}
     plant = closed_loop.PlantModel(delay_steps=[[0, 1], [0, 0]], **base)
     calls['plant'] = lambda: s.step_batch(x0, u_am, T, plant=plant)
-    if any(k not in ('plain', 'plant') for k in kinds):
+    if 'pid' in kinds:
+        pid = closed_loop.Drivers(kinds=['game', 'pid'])
+        calls['pid'] = lambda: s.step_batch(x0, u_am, T, plant=plant, drivers=pid)
+    if 'replay' in kinds:
+        own = calls['plant']()
+        replay = closed_loop.Drivers(kinds=['game', 'replay'], u_replay=own['u_applied'])
+        calls['replay'] = lambda: s.step_batch(x0, u_am, T, plant=plant, drivers=replay)
+        again = calls['replay']()
+        for key in ('status', 'num_iters', 'q', 'u_plant'):
+            assert np.array_equal(again[key], own[key], equal_nan=True), f'{key}: the replay of the plant launch\'s own commands differs from it'
+    if any(k not in ('plain', 'plant', 'pid', 'replay') for k in kinds):
         cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
         spread = dict(mass=0.1, drag_coefficient=0.1, pacejka_d_front=0.1, pacejka_d_rear=0.1)
         delays = np.random.default_rng(args.seed).integers(0, 3, size=(B, len(cfgs), 2))
