@@ -259,48 +259,46 @@ struct DgLog {
   int64_t doubles(const DgProb& D) const { return 1 + (int64_t)cap * (iterates ? D.n + D.nc : 2); }
 };
 
-// The plant of closed-loop launches (dgsqp_set_plant) and what such a launch leaves behind for dgsqp_fetch_u_plant.
-struct DgPlantState {
-  bool set = false;
-  dgsqp_plant_t host;                 // resolved: agents[] hold the game's records when the plant uses the game's parameters
-  dgsqp_plant_t* dev = nullptr;
-  double* lines = nullptr;            // delay lines, one set per workgroup
-  size_t lines_groups = 0;
-  double* u_buf = nullptr;            // u_plant [T][B][S][nu] of the last launch with a plant
-  size_t u_bytes = 0;
-  int64_t u_doubles = 0;              // what that launch wrote (0: none yet)
+// The settings of closed-loop launches (dgsqp_set_plant and, on top of a plant, dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise,
+// dgsqp_set_monitor, dgsqp_set_drivers).  Every device buffer they need is one entry of DgSide, stated once here: what a setter uploads,
+// what a launch sizes per workgroup, and the records a launch leaves behind for a dgsqp_fetch_*.  Every buffer grows exactly to what is
+// asked of it and never shrinks.
+enum DgSideBuf {
+  SB_PLANT, SB_LINES, SB_U_PLANT,                             // the plant: one dgsqp_plant_t; delay lines per workgroup; u_plant [T][B][S][nu]
+  SB_VEHICLES, SB_DELAY, SB_WG_PLANT,                         // the ensemble: [B][M] dgsqp_vehicle_t, [B][M][DGSQP_NUA] int32; one dgsqp_plant_t per workgroup
+  SB_V, SB_Q_EST,                                             // estimate noise: v and q_est [T][B][nq]
+  SB_MON_SCRATCH, SB_CLEARANCE, SB_BOX_EXCESS, SB_HIT_STEP,   // the monitor: [grid][S][M][3]; clearance and box_excess [T][B], hit_step [B] int32
+  SB_KIND, SB_PID, SB_REF, SB_U_REPLAY,                       // the drivers: [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
+  SB_U_CMD, SB_CMD, SB_PID_STATE,                             // ... u_cmd [T][B][nu]; per workgroup: [grid][n] (2 M used: read as u_t is), [grid][M][3]
+  DG_SIDE_COUNT
 };
-
-// The further settings of closed-loop launches with a plant (dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise, dgsqp_set_monitor) and
-// what such a launch leaves behind for dgsqp_fetch_q_est / dgsqp_fetch_monitor.  A device buffer that only grows: DgBuf.
 struct DgBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+struct DgSide {
+  DgBuf b[DG_SIDE_COUNT];
+  int64_t left[DG_SIDE_COUNT] = {};   // a record: elements the last launch that filled it left behind (0: none yet)
+  template <class T> T* at(int i) const { return (T*)b[i].p; }
+};
+// what is set, and for which launch shape: the plant; the further settings on top of it; the drivers
+struct DgPlantState {
+  bool set = false;
+  dgsqp_plant_t host;                 // resolved: agents[] hold the game's records when the plant uses the game's parameters
+};
 struct DgEnsembleState {
   int64_t B = 0;                      // chains of the plant ensemble (0: off)
   bool has_delay = false;
-  DgBuf vehicles, delay;              // [B][M] dgsqp_vehicle_t, [B][M][DGSQP_NUA] int32
-  DgBuf wg_plant;                     // one dgsqp_plant_t per workgroup
-  int32_t est_T = 0;                  // estimate noise: its shape (0: off) ...
+  int32_t est_T = 0;                  // estimate noise: its shape (0: off)
   int64_t est_B = 0;
-  DgBuf v, q_est;                     // ... v and q_est [T][B][nq]
-  int64_t q_est_doubles = 0;          // what the last launch with estimates wrote (0: none yet)
   int monitor = 0;                    // 0 off, 1 record, 2 record and stop
-  DgBuf scratch, clearance, box_excess, hit_step;
-  int64_t mon_TB = 0, mon_B = 0;      // shape of the last launch with the monitor on (0: none yet)
   bool any() const { return B > 0 || est_T > 0 || monitor != 0; }
 };
-
-// The drivers of closed-loop launches with a plant (dgsqp_set_drivers) and what such a launch leaves behind for dgsqp_fetch_u_cmd.
 struct DgDriversState {
   bool set = false;
   int32_t T = 0;                      // the launch shape the arrays were given for
   int64_t B = 0;
   bool has_ref = false, has_replay = false;
-  DgBuf kind, pid, ref, u_replay;     // [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
-  DgBuf u_cmd, cmd, pid_state;        // [T][B][nu] of the last launch with drivers; per workgroup: [grid][n], [grid][M][3]
-  int64_t u_cmd_doubles = 0;          // what that launch wrote (0: none yet)
 };
 
 struct dgsqp_comm_state;
@@ -323,9 +321,10 @@ struct dgsqp_solver {
   DgRecords staged;                       // ... and its arrays
   DgRecords closed;                       // closed-loop launches (dgsqp_closed_loop_batch): step-major arrays
   DgLog trace{false}, itlog{true};
-  DgPlantState plant;
+  DgPlantState plant;                      // closed-loop settings ...
   DgEnsembleState ens;
   DgDriversState drv;
+  DgSide side;                             // ... and their device buffers
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -664,32 +663,9 @@ static int log_fetch(dgsqp_solver* h, DgLog& g, double* out, int64_t capacity_do
   return DGSQP_OK;
 }
 
-// ---- the plant of closed-loop launches (DgPlantState) ----
-// what a closed-loop launch of `grid` workgroups over TB (step, scenario) pairs hands the plant kernel: delay lines per workgroup (the
-// kernel clears them when a chain starts) and the u_plant record, filled with NaN on h's stream
-static int plant_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantDev* out) {
-  DgPlantState& S = h->plant;
-  if ((size_t)grid > S.lines_groups) {
-    if (S.lines) (void)hipFree(S.lines);
-    S.lines = nullptr; S.lines_groups = 0;
-    HIPCHK(h, hipMalloc((void**)&S.lines, sizeof(double) * (size_t)grid * DGSQP_MAX_AGENTS * DGSQP_NUA * DGSQP_MAX_DELAY));
-    S.lines_groups = (size_t)grid;
-  }
-  S.u_doubles = 0;
-  const int64_t doubles = TB * S.host.sim_steps * h->hp.nu;
-  if (sizeof(double) * (size_t)doubles > S.u_bytes) {
-    if (S.u_buf) (void)hipFree(S.u_buf);
-    S.u_buf = nullptr; S.u_bytes = 0;
-    HIPCHK(h, hipMalloc((void**)&S.u_buf, sizeof(double) * (size_t)doubles));
-    S.u_bytes = sizeof(double) * (size_t)doubles;
-  }
-  HIPCHK(h, hipMemsetAsync(S.u_buf, 0xff, sizeof(double) * (size_t)doubles, h->stream));
-  S.u_doubles = doubles;
-  *out = DgPlantDev{S.dev, S.lines, S.u_buf};
-  return DGSQP_OK;
-}
-
-static int buf_reserve(dgsqp_solver* h, DgBuf& b, size_t bytes) {
+// ---- the settings of closed-loop launches and their side buffers (DgSide) ----
+static int side_reserve(dgsqp_solver* h, int i, size_t bytes) {
+  DgBuf& b = h->side.b[i];
   if (bytes <= b.bytes) return DGSQP_OK;
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr; b.bytes = 0;
@@ -697,63 +673,136 @@ static int buf_reserve(dgsqp_solver* h, DgBuf& b, size_t bytes) {
   b.bytes = bytes;
   return DGSQP_OK;
 }
-// what a closed-loop launch of `grid` workgroups, B chains and T steps hands the kernel when one of the further settings is on: sizes the
-// per-workgroup buffers and fills the records on h's stream (NaN, hit_step -1).  The caller has checked the shapes the settings were made for.
-static int ensemble_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, const DgPlantDev& pd, DgEnsembleDev* out) {
-  DgEnsembleState& E = h->ens;
+// what a setter hands the device: reserve, then a synchronous copy
+static int side_upload(dgsqp_solver* h, int i, const void* src, size_t bytes) {
+  { const int rc = side_reserve(h, i, bytes); if (rc) return rc; }
+  HIPCHK(h, hipMemcpy(h->side.b[i].p, src, bytes, hipMemcpyHostToDevice));
+  return DGSQP_OK;
+}
+// A record a launch leaves behind for its dgsqp_fetch_*: `count` elements of `elem` bytes, every byte 0xff on h's stream (NaN, hit_step -1)
+// for the kernel to write on top of.  The count is zero while anything can still fail.
+static int side_record(dgsqp_solver* h, int i, int64_t count, size_t elem) {
+  h->side.left[i] = 0;
+  { const int rc = side_reserve(h, i, (size_t)count * elem); if (rc) return rc; }
+  HIPCHK(h, hipMemsetAsync(h->side.b[i].p, 0xff, (size_t)count * elem, h->stream));
+  h->side.left[i] = count;
+  return DGSQP_OK;
+}
+// What every dgsqp_fetch_* of such records does: all of `what` as the last launch that filled them left them.  `name`: the records are
+// doubles and `capacity` of them fit behind each pointer (null: the caller's arrays have the launch's shape).
+struct DgFetch { int buf; void* out; size_t elem; };
+static int side_fetch(dgsqp_solver* h, std::initializer_list<DgFetch> what, const char* none, const char* null_out, const char* name, int64_t capacity) {
+  const DgSide& S = h->side;
+  for (const DgFetch& f : what) if (S.left[f.buf] <= 0) { h->err = none; return DGSQP_E_ARG; }
+  for (const DgFetch& f : what) if (!f.out) { h->err = null_out; return DGSQP_E_ARG; }
+  for (const DgFetch& f : what)
+    if (name && capacity < S.left[f.buf]) { h->err = std::string(name) + " buffer too small: need " + std::to_string(S.left[f.buf]) + " doubles"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  for (const DgFetch& f : what) HIPCHK(h, hipMemcpy(f.out, S.b[f.buf].p, f.elem * (size_t)S.left[f.buf], hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+// what every dgsqp_set_* of these settings begins with: a handle, its device, no launch in flight
+static int setter_begin(dgsqp_solver* h) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  return wait_idle(h);
+}
+static int refuse(dgsqp_solver* h, const char* setting, const std::string& m) { h->err = setting + m; return DGSQP_E_ARG; }
+// every setting on top of the plant is refused without one
+static int need_plant(dgsqp_solver* h, const char* setting) {
+  return h->plant.set ? DGSQP_OK : refuse(h, setting, "no plant set (dgsqp_set_plant first; the identity plant will do)");
+}
+// The two checks the plant and the ensemble share, of `who` (an agent, or a chain's agent): "" or what is wrong.
+static std::string delay_fault(const std::string& who, int j, int32_t d) {
+  if (d >= 0 && d <= DGSQP_MAX_DELAY) return "";
+  return "delay of " + who + ", input " + std::to_string(j) + " is " + std::to_string(d) + " simulation steps, allowed 0 .. " + std::to_string(DGSQP_MAX_DELAY);
+}
+static std::string model_fault(const std::string& who, int model, int game_model) {
+  if (model == game_model) return "";
+  return who + " is of model class " + std::to_string(model) + ", the game's is " + std::to_string(game_model);
+}
+
+// Per setting: what a launch of T steps and B chains must find (the order of these checks in dgsqp_closed_loop_batch decides which message
+// a caller sees), and what a launch of `grid` workgroups hands the kernel -- per-workgroup buffers sized, records filled on h's stream.
+static int further_check_plant(dgsqp_solver* h) {
+  const DgEnsembleState& E = h->ens;
+  if (!E.any() || h->plant.set) return DGSQP_OK;
+  return refuse(h, E.B > 0 ? "plant ensemble" : E.est_T > 0 ? "estimate noise" : "monitor", ": no plant set for this launch");
+}
+static int drivers_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
+  const DgDriversState& R = h->drv;
+  if (!R.set) return DGSQP_OK;
+  if (!h->plant.set) return refuse(h, "drivers: ", "no plant set for this launch");
+  if (R.T != T || R.B != B)
+    return refuse(h, "drivers: ", "launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the drivers were set for T = " + std::to_string(R.T) + ", B = " + std::to_string(R.B));
+  return DGSQP_OK;
+}
+static int further_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
+  const DgEnsembleState& E = h->ens;
+  if (E.B > 0 && E.B != B) return refuse(h, "plant ensemble: ", "launch of B = " + std::to_string(B) + " chains, the ensemble holds " + std::to_string(E.B));
+  if (E.est_T > 0 && (E.est_T != T || E.est_B != B))
+    return refuse(h, "estimate noise: ", "launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the noise was set for T = " + std::to_string(E.est_T) + ", B = " + std::to_string(E.est_B));
+  return DGSQP_OK;
+}
+// the plant: delay lines per workgroup (the kernel clears them when a chain starts) and the u_plant record
+static int plant_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantDev* out) {
+  const DgSide& S = h->side;
+  { const int rc = side_reserve(h, SB_LINES, sizeof(double) * (size_t)grid * DGSQP_MAX_AGENTS * DGSQP_NUA * DGSQP_MAX_DELAY); if (rc) return rc; }
+  { const int rc = side_record(h, SB_U_PLANT, TB * h->plant.host.sim_steps * h->hp.nu, sizeof(double)); if (rc) return rc; }
+  *out = DgPlantDev{S.at<const dgsqp_plant_t>(SB_PLANT), S.at<double>(SB_LINES), S.at<double>(SB_U_PLANT)};
+  return DGSQP_OK;
+}
+// the further settings, whichever are on, around `pd`
+static int further_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, const DgPlantDev& pd, DgEnsembleDev* out) {
+  const DgEnsembleState& E = h->ens;
+  DgSide& S = h->side;
   const int64_t TB = (int64_t)T * B;
   DgEnsembleDev ex{};
   ex.pd = pd; ex.B = B;
   if (E.B > 0) {
-    if (sizeof(dgsqp_plant_t) * (size_t)grid > E.wg_plant.bytes) {
-      { const int rc = buf_reserve(h, E.wg_plant, sizeof(dgsqp_plant_t) * (size_t)grid); if (rc) return rc; }
-      HIPCHK(h, hipMemsetAsync(E.wg_plant.p, 0, E.wg_plant.bytes, h->stream));
+    if (sizeof(dgsqp_plant_t) * (size_t)grid > S.b[SB_WG_PLANT].bytes) {
+      { const int rc = side_reserve(h, SB_WG_PLANT, sizeof(dgsqp_plant_t) * (size_t)grid); if (rc) return rc; }
+      HIPCHK(h, hipMemsetAsync(S.b[SB_WG_PLANT].p, 0, S.b[SB_WG_PLANT].bytes, h->stream));
     }
-    ex.vehicles = (const dgsqp_vehicle_t*)E.vehicles.p; ex.delay = E.has_delay ? (const int32_t*)E.delay.p : nullptr; ex.wg_plant = (dgsqp_plant_t*)E.wg_plant.p;
+    ex.vehicles = S.at<const dgsqp_vehicle_t>(SB_VEHICLES); ex.delay = E.has_delay ? S.at<const int32_t>(SB_DELAY) : nullptr; ex.wg_plant = S.at<dgsqp_plant_t>(SB_WG_PLANT);
   }
   if (E.est_T > 0) {
-    const size_t bytes = sizeof(double) * (size_t)TB * h->hp.nq;
-    E.q_est_doubles = 0;
-    { const int rc = buf_reserve(h, E.q_est, bytes); if (rc) return rc; }
-    HIPCHK(h, hipMemsetAsync(E.q_est.p, 0xff, bytes, h->stream));
-    E.q_est_doubles = TB * h->hp.nq;
-    ex.v = (const double*)E.v.p; ex.q_est = (double*)E.q_est.p;
+    { const int rc = side_record(h, SB_Q_EST, TB * h->hp.nq, sizeof(double)); if (rc) return rc; }
+    ex.v = S.at<const double>(SB_V); ex.q_est = S.at<double>(SB_Q_EST);
   }
   if (E.monitor) {
-    E.mon_TB = E.mon_B = 0;
-    { const int rc = buf_reserve(h, E.scratch, sizeof(double) * (size_t)grid * h->plant.host.sim_steps * h->hp.M * 3); if (rc) return rc; }
-    { const int rc = buf_reserve(h, E.clearance, sizeof(double) * (size_t)TB); if (rc) return rc; }
-    { const int rc = buf_reserve(h, E.box_excess, sizeof(double) * (size_t)TB); if (rc) return rc; }
-    { const int rc = buf_reserve(h, E.hit_step, sizeof(int32_t) * (size_t)B); if (rc) return rc; }
-    HIPCHK(h, hipMemsetAsync(E.clearance.p, 0xff, sizeof(double) * (size_t)TB, h->stream));
-    HIPCHK(h, hipMemsetAsync(E.box_excess.p, 0xff, sizeof(double) * (size_t)TB, h->stream));
-    HIPCHK(h, hipMemsetAsync(E.hit_step.p, 0xff, sizeof(int32_t) * (size_t)B, h->stream));
-    E.mon_TB = TB; E.mon_B = B;
-    ex.monitor = E.monitor; ex.mon_scratch = (double*)E.scratch.p; ex.clearance = (double*)E.clearance.p; ex.box_excess = (double*)E.box_excess.p;
-    ex.hit_step = (int32_t*)E.hit_step.p;
+    S.left[SB_CLEARANCE] = S.left[SB_BOX_EXCESS] = S.left[SB_HIT_STEP] = 0;      // one record in three arrays: none of it while any can fail
+    { const int rc = side_reserve(h, SB_MON_SCRATCH, sizeof(double) * (size_t)grid * h->plant.host.sim_steps * h->hp.M * 3); if (rc) return rc; }
+    { const int rc = side_record(h, SB_CLEARANCE, TB, sizeof(double)); if (rc) return rc; }
+    { const int rc = side_record(h, SB_BOX_EXCESS, TB, sizeof(double)); if (rc) return rc; }
+    { const int rc = side_record(h, SB_HIT_STEP, B, sizeof(int32_t)); if (rc) return rc; }
+    ex.monitor = E.monitor; ex.mon_scratch = S.at<double>(SB_MON_SCRATCH); ex.clearance = S.at<double>(SB_CLEARANCE); ex.box_excess = S.at<double>(SB_BOX_EXCESS);
+    ex.hit_step = S.at<int32_t>(SB_HIT_STEP);
   }
   *out = ex;
   return DGSQP_OK;
 }
-
-// what a closed-loop launch with drivers hands the kernel on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes
-// before it reads them) and the u_cmd record, filled with NaN on h's stream.  The caller has checked the shape the drivers were set for.
+// the drivers, on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes before it reads them) and the u_cmd record
 static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgEnsembleDev& ex, DgPlantDriversDev* out) {
-  DgDriversState& R = h->drv;
-  R.u_cmd_doubles = 0;
-  const size_t bytes = sizeof(double) * (size_t)TB * h->hp.nu;
-  { const int rc = buf_reserve(h, R.u_cmd, bytes); if (rc) return rc; }
-  { const int rc = buf_reserve(h, R.cmd, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }   // n per row, 2 M used: read as u_t is
-  { const int rc = buf_reserve(h, R.pid_state, sizeof(double) * (size_t)grid * h->hp.M * 3); if (rc) return rc; }
-  HIPCHK(h, hipMemsetAsync(R.u_cmd.p, 0xff, bytes, h->stream));
-  R.u_cmd_doubles = TB * h->hp.nu;
+  const DgDriversState& R = h->drv;
+  DgSide& S = h->side;
+  S.left[SB_U_CMD] = 0;
+  { const int rc = side_reserve(h, SB_CMD, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }
+  { const int rc = side_reserve(h, SB_PID_STATE, sizeof(double) * (size_t)grid * h->hp.M * 3); if (rc) return rc; }
+  { const int rc = side_record(h, SB_U_CMD, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
   DgPlantDriversDev dd{};
   dd.ex = ex;
-  dd.kind = (const int32_t*)R.kind.p; dd.pid = (const dgsqp_pid_t*)R.pid.p;
-  dd.ref = R.has_ref ? (const double*)R.ref.p : nullptr; dd.u_replay = R.has_replay ? (const double*)R.u_replay.p : nullptr;
-  dd.u_cmd = (double*)R.u_cmd.p; dd.cmd = (double*)R.cmd.p; dd.pid_state = (double*)R.pid_state.p;
+  dd.kind = S.at<const int32_t>(SB_KIND); dd.pid = S.at<const dgsqp_pid_t>(SB_PID);
+  dd.ref = R.has_ref ? S.at<const double>(SB_REF) : nullptr; dd.u_replay = R.has_replay ? S.at<const double>(SB_U_REPLAY) : nullptr;
+  dd.u_cmd = S.at<double>(SB_U_CMD); dd.cmd = S.at<double>(SB_CMD); dd.pid_state = S.at<double>(SB_PID_STATE);
   *out = dd;
   return DGSQP_OK;
+}
+// the one launch of dg_closed_loop_kernel, instantiated for the argument pack the settings call for (none: no plant)
+template <class... PLANT>
+static void launch_closed_loop(dgsqp_solver* h, int grid, int64_t B, const DgClosedLoop& cl, const PLANT&... pd) {
+  hipLaunchKernelGGL(dg_closed_loop_kernel<PLANT...>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd...);
 }
 
 // The one launch of dg_solve_kernel: L's staged batch, or -- with `group`, the host image of `count` batches of L->B scenarios each,
@@ -903,12 +952,7 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->drained_host) (void)hipHostFree(h->drained_host);
   if (h->trace.buf) (void)hipFree(h->trace.buf);
   if (h->itlog.buf) (void)hipFree(h->itlog.buf);
-  if (h->plant.dev) (void)hipFree(h->plant.dev);
-  if (h->plant.lines) (void)hipFree(h->plant.lines);
-  if (h->plant.u_buf) (void)hipFree(h->plant.u_buf);
-  for (DgBuf* b : {&h->ens.vehicles, &h->ens.delay, &h->ens.wg_plant, &h->ens.v, &h->ens.q_est, &h->ens.scratch, &h->ens.clearance, &h->ens.box_excess, &h->ens.hit_step,
-                   &h->drv.kind, &h->drv.pid, &h->drv.ref, &h->drv.u_replay, &h->drv.u_cmd, &h->drv.cmd, &h->drv.pid_state})
-    if (b->p) (void)hipFree(b->p);
+  for (DgBuf& b : h->side.b) if (b.p) (void)hipFree(b.p);
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1149,130 +1193,87 @@ int dgsqp_solve_batch(dgsqp_handle_t h, int64_t B, const double* x0, const doubl
 }
 
 int dgsqp_set_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant) {
-  if (!h) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
+  { const int rc = setter_begin(h); if (rc) return rc; }
   DgPlantState& S = h->plant;
   if (!plant) { S.set = false; return DGSQP_OK; }
-  auto bad = [&](const std::string& m) { h->err = "plant: " + m; return DGSQP_E_ARG; };
+  auto bad = [&](const std::string& m) { return refuse(h, "plant: ", m); };
   const int integ = plant->integrator;
   if (integ != DGSQP_INT_EULER && integ != DGSQP_INT_RK4 && integ != DGSQP_INT_RK3 && integ != DGSQP_INT_RK2) return bad("unknown integrator " + std::to_string(integ));
   if (plant->substeps < 1) return bad("substeps must be at least 1, got " + std::to_string(plant->substeps));
   if (plant->sim_steps < 1) return bad("sim_steps must be at least 1, got " + std::to_string(plant->sim_steps));
   const dgsqp_problem_t& P = h->hp.P;
   for (int a = 0; a < P.M; a++) {
-    for (int j = 0; j < DGSQP_NUA; j++)
-      if (plant->delay[a][j] < 0 || plant->delay[a][j] > DGSQP_MAX_DELAY)
-        return bad("delay of agent " + std::to_string(a) + ", input " + std::to_string(j) + " is " + std::to_string(plant->delay[a][j]) + " simulation steps, allowed 0 .. " + std::to_string(DGSQP_MAX_DELAY));
-    if (!plant->use_game_agents && plant->agents[a].model != P.agents[a].model)
-      return bad("agent " + std::to_string(a) + " is of model class " + std::to_string(plant->agents[a].model) + ", the game's is " + std::to_string(P.agents[a].model));
+    const std::string who = "agent " + std::to_string(a);
+    for (int j = 0; j < DGSQP_NUA; j++) { const std::string m = delay_fault(who, j, plant->delay[a][j]); if (!m.empty()) return bad(m); }
+    if (!plant->use_game_agents) { const std::string m = model_fault(who, plant->agents[a].model, P.agents[a].model); if (!m.empty()) return bad(m); }
   }
   S.host = *plant;
   if (plant->use_game_agents) memcpy(S.host.agents, P.agents, sizeof(P.agents));
-  if (!S.dev) HIPCHK(h, hipMalloc((void**)&S.dev, sizeof(dgsqp_plant_t)));
-  HIPCHK(h, hipMemcpy(S.dev, &S.host, sizeof(dgsqp_plant_t), hipMemcpyHostToDevice));
+  { const int rc = side_upload(h, SB_PLANT, &S.host, sizeof(dgsqp_plant_t)); if (rc) return rc; }
   S.set = true;
   return DGSQP_OK;
 }
 int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
-  if (!h) return DGSQP_E_ARG;
-  const DgPlantState& S = h->plant;
-  if (!out || !S.u_buf || S.u_doubles <= 0) { h->err = "no closed-loop launch with a plant has run"; return DGSQP_E_ARG; }
-  if (capacity_doubles < S.u_doubles) { h->err = "u_plant buffer too small: need " + std::to_string(S.u_doubles) + " doubles"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(out, S.u_buf, sizeof(double) * (size_t)S.u_doubles, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  const char* none = "no closed-loop launch with a plant has run";
+  return h ? side_fetch(h, {{SB_U_PLANT, out, sizeof(double)}}, none, none, "u_plant", capacity_doubles) : DGSQP_E_ARG;
 }
 
 int dgsqp_set_plant_ensemble(dgsqp_handle_t h, int64_t B, const dgsqp_vehicle_t* vehicles, const int32_t* delay) {
-  if (!h) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
+  { const int rc = setter_begin(h); if (rc) return rc; }
   DgEnsembleState& E = h->ens;
   if (!vehicles || B == 0) { E.B = 0; return DGSQP_OK; }
-  auto bad = [&](const std::string& m) { h->err = "plant ensemble: " + m; return DGSQP_E_ARG; };
-  if (!h->plant.set) return bad("no plant set (dgsqp_set_plant first; the identity plant will do)");
+  auto bad = [&](const std::string& m) { return refuse(h, "plant ensemble: ", m); };
+  { const int rc = need_plant(h, "plant ensemble: "); if (rc) return rc; }
   if (B < 0) return bad("B must not be negative");
   const int M = h->hp.P.M;
   for (int64_t b = 0; b < B; b++)
     for (int a = 0; a < M; a++) {
-      if (vehicles[b * M + a].model != h->hp.P.agents[a].model)
-        return bad("vehicle of chain " + std::to_string(b) + ", agent " + std::to_string(a) + " is of model class " + std::to_string(vehicles[b * M + a].model) + ", the game's is " + std::to_string(h->hp.P.agents[a].model));
-      for (int j = 0; delay && j < DGSQP_NUA; j++) {
-        const int32_t d = delay[(b * M + a) * DGSQP_NUA + j];
-        if (d < 0 || d > DGSQP_MAX_DELAY)
-          return bad("delay of chain " + std::to_string(b) + ", agent " + std::to_string(a) + ", input " + std::to_string(j) + " is " + std::to_string(d) + " simulation steps, allowed 0 .. " + std::to_string(DGSQP_MAX_DELAY));
-      }
+      const std::string who = "chain " + std::to_string(b) + ", agent " + std::to_string(a);
+      { const std::string m = model_fault("vehicle of " + who, vehicles[b * M + a].model, h->hp.P.agents[a].model); if (!m.empty()) return bad(m); }
+      for (int j = 0; delay && j < DGSQP_NUA; j++) { const std::string m = delay_fault(who, j, delay[(b * M + a) * DGSQP_NUA + j]); if (!m.empty()) return bad(m); }
     }
   E.B = 0;
-  const size_t nv = sizeof(dgsqp_vehicle_t) * (size_t)B * M, nd = sizeof(int32_t) * (size_t)B * M * DGSQP_NUA;
-  { const int rc = buf_reserve(h, E.vehicles, nv); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(E.vehicles.p, vehicles, nv, hipMemcpyHostToDevice));
-  if (delay) {
-    { const int rc = buf_reserve(h, E.delay, nd); if (rc) return rc; }
-    HIPCHK(h, hipMemcpy(E.delay.p, delay, nd, hipMemcpyHostToDevice));
-  }
+  { const int rc = side_upload(h, SB_VEHICLES, vehicles, sizeof(dgsqp_vehicle_t) * (size_t)B * M); if (rc) return rc; }
+  if (delay) { const int rc = side_upload(h, SB_DELAY, delay, sizeof(int32_t) * (size_t)B * M * DGSQP_NUA); if (rc) return rc; }
   E.has_delay = delay != nullptr;
   E.B = B;
   return DGSQP_OK;
 }
 int dgsqp_set_estimate_noise(dgsqp_handle_t h, int32_t T, int64_t B, const double* v) {
-  if (!h) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
+  { const int rc = setter_begin(h); if (rc) return rc; }
   DgEnsembleState& E = h->ens;
   if (!v || T == 0 || B == 0) { E.est_T = 0; E.est_B = 0; return DGSQP_OK; }
-  if (!h->plant.set) { h->err = "estimate noise: no plant set (dgsqp_set_plant first; the identity plant will do)"; return DGSQP_E_ARG; }
-  if (T < 0 || B < 0) { h->err = "estimate noise: T and B must not be negative"; return DGSQP_E_ARG; }
+  { const int rc = need_plant(h, "estimate noise: "); if (rc) return rc; }
+  if (T < 0 || B < 0) return refuse(h, "estimate noise: ", "T and B must not be negative");
   E.est_T = 0; E.est_B = 0;
-  const size_t bytes = sizeof(double) * (size_t)T * (size_t)B * h->hp.nq;
-  { const int rc = buf_reserve(h, E.v, bytes); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(E.v.p, v, bytes, hipMemcpyHostToDevice));
+  { const int rc = side_upload(h, SB_V, v, sizeof(double) * (size_t)T * (size_t)B * h->hp.nq); if (rc) return rc; }
   E.est_T = T; E.est_B = B;
   return DGSQP_OK;
 }
 int dgsqp_fetch_q_est(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
-  if (!h) return DGSQP_E_ARG;
-  const DgEnsembleState& E = h->ens;
-  if (!out || !E.q_est.p || E.q_est_doubles <= 0) { h->err = "no closed-loop launch with state estimates has run"; return DGSQP_E_ARG; }
-  if (capacity_doubles < E.q_est_doubles) { h->err = "q_est buffer too small: need " + std::to_string(E.q_est_doubles) + " doubles"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(out, E.q_est.p, sizeof(double) * (size_t)E.q_est_doubles, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  const char* none = "no closed-loop launch with state estimates has run";
+  return h ? side_fetch(h, {{SB_Q_EST, out, sizeof(double)}}, none, none, "q_est", capacity_doubles) : DGSQP_E_ARG;
 }
 int dgsqp_set_monitor(dgsqp_handle_t h, int mode) {
-  if (!h) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
+  { const int rc = setter_begin(h); if (rc) return rc; }
   if (mode == 0) { h->ens.monitor = 0; return DGSQP_OK; }
-  if (mode != 1 && mode != 2) { h->err = "monitor: mode must be 0 (off), 1 (record) or 2 (record and stop), got " + std::to_string(mode); return DGSQP_E_ARG; }
-  if (!h->plant.set) { h->err = "monitor: no plant set (dgsqp_set_plant first; the identity plant will do)"; return DGSQP_E_ARG; }
+  if (mode != 1 && mode != 2) return refuse(h, "monitor: ", "mode must be 0 (off), 1 (record) or 2 (record and stop), got " + std::to_string(mode));
+  { const int rc = need_plant(h, "monitor: "); if (rc) return rc; }
   h->ens.monitor = mode;
   return DGSQP_OK;
 }
 int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess, int32_t* hit_step) {
   if (!h) return DGSQP_E_ARG;
-  const DgEnsembleState& E = h->ens;
-  if (E.mon_TB <= 0) { h->err = "no closed-loop launch with the monitor on has run"; return DGSQP_E_ARG; }
-  if (!clearance || !box_excess || !hit_step) { h->err = "monitor: null argument"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(clearance, E.clearance.p, sizeof(double) * (size_t)E.mon_TB, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(box_excess, E.box_excess.p, sizeof(double) * (size_t)E.mon_TB, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(hit_step, E.hit_step.p, sizeof(int32_t) * (size_t)E.mon_B, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  return side_fetch(h, {{SB_CLEARANCE, clearance, sizeof(double)}, {SB_BOX_EXCESS, box_excess, sizeof(double)}, {SB_HIT_STEP, hit_step, sizeof(int32_t)}},
+                    "no closed-loop launch with the monitor on has run", "monitor: null argument", nullptr, 0);
 }
 
 int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int64_t B, const int32_t* kind, const double* ref, const double* u_replay) {
-  if (!h) return DGSQP_E_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
+  { const int rc = setter_begin(h); if (rc) return rc; }
   DgDriversState& R = h->drv;
   if (!d) { R.set = false; return DGSQP_OK; }
-  auto bad = [&](const std::string& m) { h->err = "drivers: " + m; return DGSQP_E_ARG; };
-  if (!h->plant.set) return bad("no plant set (dgsqp_set_plant first; the identity plant will do)");
+  auto bad = [&](const std::string& m) { return refuse(h, "drivers: ", m); };
+  { const int rc = need_plant(h, "drivers: "); if (rc) return rc; }
   if (T < 1) return bad("T must be at least 1, got " + std::to_string(T));
   if (B < 0) return bad("B must not be negative");
   const dgsqp_problem_t& P = h->hp.P;
@@ -1280,7 +1281,7 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
   // the kinds of every chain: d->kind where the caller gives none per chain; both are checked, whichever the launch will read
   std::vector<int32_t> kinds((size_t)B * M);
   bool replay = false;
-  auto check = [&](int32_t k, int a, const std::string& where) {
+  auto check = [&](int32_t k, int a, const std::string& where) -> int {
     if (k != DGSQP_DRIVER_GAME && k != DGSQP_DRIVER_PID && k != DGSQP_DRIVER_REPLAY)
       return bad("kind of " + where + " is " + std::to_string(k) + ", allowed 0 (game), 1 (PID), 2 (replay)");
     if (k == DGSQP_DRIVER_PID && P.agents[a].model == DGSQP_MODEL_UNICYCLE)
@@ -1297,20 +1298,11 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
     }
   if (replay && !u_replay) return bad("a REPLAY driver needs u_replay");
   R.set = false;
-  const size_t nk = sizeof(int32_t) * kinds.size(), nr = sizeof(double) * (size_t)B * M * 2, nu = sizeof(double) * (size_t)T * (size_t)B * h->hp.nu;
-  { const int rc = buf_reserve(h, R.pid, sizeof(d->pid)); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(R.pid.p, d->pid, sizeof(d->pid), hipMemcpyHostToDevice));
+  { const int rc = side_upload(h, SB_PID, d->pid, sizeof(d->pid)); if (rc) return rc; }
   if (B > 0) {
-    { const int rc = buf_reserve(h, R.kind, nk); if (rc) return rc; }
-    HIPCHK(h, hipMemcpy(R.kind.p, kinds.data(), nk, hipMemcpyHostToDevice));
-    if (ref) {
-      { const int rc = buf_reserve(h, R.ref, nr); if (rc) return rc; }
-      HIPCHK(h, hipMemcpy(R.ref.p, ref, nr, hipMemcpyHostToDevice));
-    }
-    if (u_replay) {
-      { const int rc = buf_reserve(h, R.u_replay, nu); if (rc) return rc; }
-      HIPCHK(h, hipMemcpy(R.u_replay.p, u_replay, nu, hipMemcpyHostToDevice));
-    }
+    { const int rc = side_upload(h, SB_KIND, kinds.data(), sizeof(int32_t) * kinds.size()); if (rc) return rc; }
+    if (ref) { const int rc = side_upload(h, SB_REF, ref, sizeof(double) * (size_t)B * M * 2); if (rc) return rc; }
+    if (u_replay) { const int rc = side_upload(h, SB_U_REPLAY, u_replay, sizeof(double) * (size_t)T * (size_t)B * h->hp.nu); if (rc) return rc; }
   }
   R.has_ref = ref != nullptr; R.has_replay = u_replay != nullptr;
   R.T = T; R.B = B;
@@ -1318,14 +1310,8 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
   return DGSQP_OK;
 }
 int dgsqp_fetch_u_cmd(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
-  if (!h) return DGSQP_E_ARG;
-  const DgDriversState& R = h->drv;
-  if (!out || !R.u_cmd.p || R.u_cmd_doubles <= 0) { h->err = "no closed-loop launch with drivers has run"; return DGSQP_E_ARG; }
-  if (capacity_doubles < R.u_cmd_doubles) { h->err = "u_cmd buffer too small: need " + std::to_string(R.u_cmd_doubles) + " doubles"; return DGSQP_E_ARG; }
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rc = wait_idle(h); if (rc) return rc; }
-  HIPCHK(h, hipMemcpy(out, R.u_cmd.p, sizeof(double) * (size_t)R.u_cmd_doubles, hipMemcpyDeviceToHost));
-  return DGSQP_OK;
+  const char* none = "no closed-loop launch with drivers has run";
+  return h ? side_fetch(h, {{SB_U_CMD, out, sizeof(double)}}, none, none, "u_cmd", capacity_doubles) : DGSQP_E_ARG;
 }
 
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
@@ -1342,25 +1328,10 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
   }
-  const bool further = h->ens.any();
-  if (further && !h->plant.set) {
-    h->err = std::string(h->ens.B > 0 ? "plant ensemble" : h->ens.est_T > 0 ? "estimate noise" : "monitor") + ": no plant set for this launch";
-    return DGSQP_E_ARG;
-  }
-  const bool drivers = h->drv.set;
-  if (drivers && !h->plant.set) { h->err = "drivers: no plant set for this launch"; return DGSQP_E_ARG; }
-  if (drivers && (h->drv.T != T || h->drv.B != B)) {
-    h->err = "drivers: launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the drivers were set for T = " + std::to_string(h->drv.T) + ", B = " + std::to_string(h->drv.B);
-    return DGSQP_E_ARG;
-  }
-  {
-    const DgEnsembleState& E = h->ens;
-    if (E.B > 0 && E.B != B) { h->err = "plant ensemble: launch of B = " + std::to_string(B) + " chains, the ensemble holds " + std::to_string(E.B); return DGSQP_E_ARG; }
-    if (E.est_T > 0 && (E.est_T != T || E.est_B != B)) {
-      h->err = "estimate noise: launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the noise was set for T = " + std::to_string(E.est_T) + ", B = " + std::to_string(E.est_B);
-      return DGSQP_E_ARG;
-    }
-  }
+  const bool further = h->ens.any(), drivers = h->drv.set;
+  { const int rc = further_check_plant(h); if (rc) return rc; }
+  { const int rc = drivers_check_launch(h, T, B); if (rc) return rc; }
+  { const int rc = further_check_launch(h, T, B); if (rc) return rc; }
   HIPCHK(h, hipSetDevice(h->device));
   // Step-major arrays: T x B of every record, one more slice of the state and warm-start chains; c = scenarios per record, keep = the
   // leading ones that are copied in and not filled.  Without x_out one [B][N+1][nq] slice serves every step, without l_out there is no l.
@@ -1390,17 +1361,17 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   DgEnsembleDev ex{};
   if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
   DgPlantDriversDev dd{};
-  if (further || drivers) { const int rc = ensemble_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
+  if (further || drivers) { const int rc = further_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
   if (drivers) { const int rc = drivers_for_launch(h, grid, TB, ex, &dd); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (drivers) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDriversDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, dd);
-    else if (further) hipLaunchKernelGGL(dg_closed_loop_kernel<DgEnsembleDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, ex);
-    else if (h->plant.set) hipLaunchKernelGGL(dg_closed_loop_kernel<DgPlantDev>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket, pd);
-    else hipLaunchKernelGGL(dg_closed_loop_kernel<>, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, B, cl, h->ws, h->ticket);
+    if (drivers) launch_closed_loop(h, grid, B, cl, dd);
+    else if (further) launch_closed_loop(h, grid, B, cl, ex);
+    else if (h->plant.set) launch_closed_loop(h, grid, B, cl, pd);
+    else launch_closed_loop(h, grid, B, cl);
     HIPCHK(h, hipGetLastError());
     h->launch_stream = h->stream;
     h->in_flight = true;       // (a launch of another game waits for this kernel before it replaces the constants)

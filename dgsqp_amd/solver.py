@@ -13,7 +13,7 @@ import copy
 import ctypes as C
 import time
 import warnings
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -293,6 +293,17 @@ def _record_ptrs(out: dict, fptr=_ffi.dptr) -> tuple:
             _ffi.iptr(out['qp_solves']), fptr(out['cond']), fptr(out['cost']))
 
 
+class _Setting(NamedTuple):
+    """One setting of a closed-loop launch as ``step_batch`` walks it (the table there says what each field is)."""
+    name: str
+    on: object
+    off: tuple
+    fetch: Optional[str] = None
+    steps: dict = {}
+    chains: tuple = ()
+    sized: bool = True
+
+
 def solve_batches(solvers, batches) -> list:
     """Several Monte-Carlo batches of the SAME game and size in ONE launch (``dgsqp_launch_staged_group``): ``solvers`` are DGSQP
     objects of that game (one per batch: every batch keeps its own device buffers), ``batches`` the matching ``(x0, u_ws)`` pairs as
@@ -553,7 +564,7 @@ class DGSQP(AbstractSolver):
         sm = dict(q=np.empty((T + 1, B, self.n_q)), u_ws=np.empty((T + 1, B, self.n)), **self._records((T, B), predictions=keep_predictions))
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
-        u_plant = noise = q_est = mon = ensemble = drv = u_cmd = None
+        dptr, iptr = _ffi.dptr, _ffi.iptr
         if drivers is not None and plant is None:
             from .closed_loop import PlantModel
             plant = PlantModel()
@@ -561,67 +572,50 @@ class DGSQP(AbstractSolver):
             raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
         if plant is None and (estimate_noise is not None or monitor):
             raise ValueError('estimate_noise and monitor need a plant (PlantModel() is the identity plant)')
+        noise = pt = ensemble = drv = None
         if estimate_noise is not None:
             noise = np.asarray(estimate_noise, dtype=np.float64)
             if noise.shape != (B, T, self.n_q):
                 raise ValueError(f'estimate_noise must be [B, steps, n_q] = {(B, T, self.n_q)}, got {noise.shape}')
             noise = np.ascontiguousarray(noise.transpose(1, 0, 2))
-            q_est = np.empty((T, B, self.n_q))
-        if monitor:
-            mon = dict(clearance=np.empty((T, B)), box_excess=np.empty((T, B)), hit_step=np.empty(B, np.int32))
         if plant is not None:
             pt = plant.lower(self._problem)
             ensemble = plant.lower_ensemble(self._problem, B) if plant.per_chain else None
-            u_plant = np.empty((T, B, pt.sim_steps, self.n_u))
         if drivers is not None:
             drv = drivers.lower(self._problem, B, T)
-            u_cmd = np.empty((T, B, self.n_u))
-        err = lambda what: ValueError(f'{what} failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+        # Every setting once, in the order they are set: dgsqp_set_<name>(*on) when it is asked for and, afterwards, (*off);
+        # dgsqp_fetch_<fetch> fills the records it adds to the result -- ``steps`` step-major [T, B, ...] doubles, ``chains`` [B] int32 --
+        # and takes their size when ``sized``.
+        settings = [_Setting('plant', pt is not None and (C.byref(pt),), (None,), 'u_plant', dict(u_plant=(getattr(pt, 'sim_steps', 0), self.n_u))),
+                    _Setting('plant_ensemble', ensemble is not None and (B, ensemble[0], iptr(ensemble[1])), (0, None, None)),
+                    _Setting('estimate_noise', noise is not None and (T, B, dptr(noise)), (0, 0, None), 'q_est', dict(q_est=(self.n_q,))),
+                    _Setting('monitor', bool(monitor) and (2 if monitor == 'stop' else 1,), (0,), 'monitor', dict(clearance=(), box_excess=()), ('hit_step',), sized=False),
+                    _Setting('drivers', drv is not None and (C.byref(drv[0]), T, B, iptr(drv[1]), dptr(drv[2]), dptr(drv[3])), (None, 0, 0, None, None, None),
+                             'u_cmd', dict(u_cmd=(self.n_u,)))]
+        on = [st for st in settings if st.on]
+        chains = {k: np.empty(B, np.int32) for st in on for k in st.chains}
+        sm.update({k: np.empty((T, B) + tail) for st in on for k, tail in st.steps.items()})
+        last_error = lambda: self._lib.dgsqp_last_error(self._h).decode()
         t0 = time.time()
         try:
-            if plant is not None:
-                if self._lib.dgsqp_set_plant(self._h, C.byref(pt)) != 0:
-                    raise err('dgsqp_set_plant')
-                if ensemble is not None and self._lib.dgsqp_set_plant_ensemble(self._h, B, ensemble[0], _ffi.iptr(ensemble[1])) != 0:
-                    raise err('dgsqp_set_plant_ensemble')
-                if noise is not None and self._lib.dgsqp_set_estimate_noise(self._h, T, B, _ffi.dptr(noise)) != 0:
-                    raise err('dgsqp_set_estimate_noise')
-                if mon is not None and self._lib.dgsqp_set_monitor(self._h, 2 if monitor == 'stop' else 1) != 0:
-                    raise err('dgsqp_set_monitor')
-                if drv is not None and self._lib.dgsqp_set_drivers(self._h, C.byref(drv[0]), T, B, _ffi.iptr(drv[1]), _ffi.dptr(drv[2]), _ffi.dptr(drv[3])) != 0:
-                    raise err('dgsqp_set_drivers')
-            rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, _ffi.dptr(x0), _ffi.dptr(u_ws), _ffi.dptr(w), _ffi.dptr(sm['q']), _ffi.dptr(sm['u_ws']),
-                                                   *_record_ptrs(sm), _ffi.iptr(steps_done), C.byref(tm))
+            for st in on:
+                if getattr(self._lib, 'dgsqp_set_' + st.name)(self._h, *st.on) != 0:
+                    raise ValueError(f'dgsqp_set_{st.name} failed: ' + last_error())
+            rc = self._lib.dgsqp_closed_loop_batch(self._h, B, T, dptr(x0), dptr(u_ws), dptr(w), dptr(sm['q']), dptr(sm['u_ws']),
+                                                   *_record_ptrs(sm), iptr(steps_done), C.byref(tm))
             if rc != 0:
-                raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
-            if u_plant is not None and B > 0 and self._lib.dgsqp_fetch_u_plant(self._h, _ffi.dptr(u_plant), u_plant.size) != 0:
-                raise RuntimeError('dgsqp_fetch_u_plant failed: ' + self._lib.dgsqp_last_error(self._h).decode())
-            if q_est is not None and B > 0 and self._lib.dgsqp_fetch_q_est(self._h, _ffi.dptr(q_est), q_est.size) != 0:
-                raise RuntimeError('dgsqp_fetch_q_est failed: ' + self._lib.dgsqp_last_error(self._h).decode())
-            if mon is not None and B > 0 and self._lib.dgsqp_fetch_monitor(self._h, _ffi.dptr(mon['clearance']), _ffi.dptr(mon['box_excess']),
-                                                                           _ffi.iptr(mon['hit_step'])) != 0:
-                raise RuntimeError('dgsqp_fetch_monitor failed: ' + self._lib.dgsqp_last_error(self._h).decode())
-            if u_cmd is not None and B > 0 and self._lib.dgsqp_fetch_u_cmd(self._h, _ffi.dptr(u_cmd), u_cmd.size) != 0:
-                raise RuntimeError('dgsqp_fetch_u_cmd failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+                raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): ' + last_error())
+            for st in on:
+                if st.fetch and B > 0:
+                    into = [dptr(sm[k]) for k in st.steps] + [iptr(chains[k]) for k in st.chains] + [sm[k].size for k in st.steps if st.sized]
+                    if getattr(self._lib, 'dgsqp_fetch_' + st.fetch)(self._h, *into) != 0:
+                        raise RuntimeError(f'dgsqp_fetch_{st.fetch} failed: ' + last_error())
         finally:
             if plant is not None:
-                self._lib.dgsqp_set_drivers(self._h, None, 0, 0, None, None, None)
-                self._lib.dgsqp_set_monitor(self._h, 0)
-                self._lib.dgsqp_set_estimate_noise(self._h, 0, 0, None)
-                self._lib.dgsqp_set_plant_ensemble(self._h, 0, None, None)
-                self._lib.dgsqp_set_plant(self._h, None)
-        if u_plant is not None:
-            sm['u_plant'] = u_plant
-        if q_est is not None:
-            sm['q_est'] = q_est
-        if u_cmd is not None:
-            sm['u_cmd'] = u_cmd
-        if mon is not None:
-            sm['clearance'], sm['box_excess'] = mon['clearance'], mon['box_excess']
+                for st in reversed(settings):
+                    getattr(self._lib, 'dgsqp_set_' + st.name)(self._h, *st.off)
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
-        out['steps_done'] = steps_done
-        if mon is not None:
-            out['hit_step'] = mon['hit_step']
+        out.update(chains, steps_done=steps_done)
         self._finish(out, t0, tm)
         out['u_applied'] = np.ascontiguousarray(out['u_pred'][:, :, 0])
         return out

@@ -1,66 +1,16 @@
 """Closed-loop batches on the device: DGSQP.step_batch (dgsqp_closed_loop_batch, csrc/dgsqp_closed_loop.h).
 
-The check is the same in every case -- TEACHER FORCING: every (state, warm start) pair a chain went through is stacked into ONE
-``solve_batch`` call on the same solver, and u, l, x, cond, cost, status, num_iters and qp_solves of that call must equal the closed-loop
+The check is the same in every case (its helpers are those of tests/closed_loop_checks.py) -- TEACHER FORCING: every (state, warm start)
+pair a chain went through is stacked into ONE ``solve_batch`` call on the same solver, and u, l, x, cond, cost, status, num_iters and qp_solves of that call must equal the closed-loop
 records bit for bit: every closed-loop step is the very solve the product already performs, whatever path the chain took.  Separately the
 feedback between two steps is checked exactly against the host mirror ``dgsqp_amd.closed_loop.feedback``."""
 import numpy as np
 import pytest
 
+from closed_loop_checks import COUNTS, DOUBLES, check_feedback, same, scenarios, solver_of, teacher_force      # noqa: F401  (solver_of is a fixture)
 from conftest import agent_major
 
 pytestmark = pytest.mark.gpu
-
-DOUBLES = ('u', 'l', 'x', 'cond', 'cost')
-COUNTS = ('status', 'num_iters', 'qp_solves')
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def same(a, b):
-    """Bit for bit (stricter than np.array_equal: NaN payloads and the sign of zero count)."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and (np.array_equal(bits(a), bits(b)) if a.dtype == np.float64 else np.array_equal(a, b))
-
-
-def teacher_force(s, res):
-    """One solve_batch over every step that ran; returns how many steps that were."""
-    bb, tt = np.nonzero(np.arange(res['status'].shape[1])[None, :] < res['steps_done'][:, None])
-    ref = s.solve_batch(res['q'][bb, tt], res['u_ws'][bb, tt])
-    for key in DOUBLES + COUNTS:
-        got = res[key][bb, tt]
-        bad = [(int(bb[i]), int(tt[i])) for i in range(len(bb)) if not same(got[i], ref[key][i])]
-        assert not bad, f'{key}: closed-loop steps (scenario, step) {bad[:8]} differ from solve_batch on the same inputs'
-    assert [res['msg'][b][t] for b, t in zip(bb, tt)] == ref['msg']
-    assert same(res['converged'][bb, tt], ref['converged'])
-    return len(bb)
-
-
-def check_feedback(s, res, x0, u_am, w=None):
-    """q / u_ws chains, u_applied and the records of steps that never ran."""
-    from dgsqp_amd import closed_loop
-    B, T = res['status'].shape
-    done = res['steps_done']
-    assert same(res['q'][:, 0], x0) and same(res['u_ws'][:, 0], u_am)
-    assert res['q'].shape == (B, T + 1, s.n_q) and res['u_ws'].shape == (B, T + 1, s.n) and res['u_pred'].shape == (B, T, s.N, s.n_u)
-    assert same(res['u_applied'], res['u_pred'][:, :, 0]) and same(res['u_pred'], s._to_time_major(res['u']))
-    for t in range(T):
-        ran = t < done
-        q_next, ws_next, ok = closed_loop.feedback(res['x'][:, t], res['u'][:, t], res['status'][:, t], res['u_ws'][:, t],
-                                                   w=None if w is None else w[:, t], num_ua_d=s.num_ua_d)
-        assert np.array_equal(res['q'][ran, t + 1], q_next[ran], equal_nan=True) and same(res['q'][ran & ok, t + 1], q_next[ran & ok]), t
-        assert same(res['u_ws'][ran & ok, t + 1], ws_next[ran & ok]), t
-        assert np.array_equal(done[ran], np.where(ok[ran], np.maximum(done[ran], t + 1), t + 1)), t      # a chain ends at its first non-finite state
-        # steps that never ran: status -1 / 'not_run', zero counts, NaN everywhere -- and nothing was started from a non-finite state
-        idle = ~ran
-        assert (res['status'][idle, t] == -1).all() and (res['num_iters'][idle, t] == 0).all() and (res['qp_solves'][idle, t] == 0).all()
-        assert all(res['msg'][b][t] == 'not_run' for b in np.nonzero(idle)[0]) and not res['converged'][idle, t].any()
-        for key in DOUBLES:
-            assert np.isnan(res[key][idle, t]).all(), (key, t)
-        assert np.isnan(res['u_ws'][idle | ~ok, t + 1]).all() and np.isnan(res['q'][idle, t + 1]).all(), t
-    assert ((done >= 1) & (done <= T)).all()
 
 
 def run_and_check(s, x0, u_tm, T, w=None):
@@ -68,26 +18,6 @@ def run_and_check(s, x0, u_tm, T, w=None):
     check_feedback(s, res, x0, s._to_agent_major(np.asarray(u_tm, float)), w)
     teacher_force(s, res)
     return res
-
-
-@pytest.fixture(scope='module')
-def solver_of(games):
-    """name -> DGSQP of conftest's game of that name, built once per module."""
-    from dgsqp_amd.solver import DGSQP
-    cache = {}
-
-    def get(name, **kw):
-        key = (name, tuple(sorted(kw.items())))
-        if key not in cache:
-            cache[key] = DGSQP(*games[name][0].solver_args(), print_method=None, **kw)
-        return cache[key]
-    yield get
-    cache.clear()
-
-
-def scenarios(g, B, seed):
-    from dgsqp_amd.montecarlo import sample_scenarios
-    return sample_scenarios(g, B, seed=seed)
 
 
 def test_basic_chain_with_disturbance(games, solver_of):

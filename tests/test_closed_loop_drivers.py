@@ -2,8 +2,8 @@
 DgPlantDriversDev instantiation of dg_closed_loop_kernel, csrc/dgsqp_closed_loop.h): per agent and per chain the command that enters the plant
 is stage 0 of the game's solution, the PID lane follower run closed-loop on the true state, or a replayed sequence.
 
-The idiom is that of tests/test_closed_loop_ensemble.py, whose helpers are used as they are: TEACHER FORCING, the warm-start chain, u_plant
-bit for bit against the delay-line mirror -- now fed with u_cmd, the commands the plants received -- and q[t+1] against the CPU oracle at
+The idiom is that of tests/test_closed_loop_ensemble.py, with the helpers of tests/closed_loop_checks.py: TEACHER FORCING, the warm-start
+chain, u_plant bit for bit against the delay-line mirror -- now fed with u_cmd, the commands the plants received -- and q[t+1] against the CPU oracle at
 1e-12 relative to max(1, |q|_inf).  On top of that ``check_commands``: u_cmd of a game agent is bit for bit stage 0 of u, of a replay agent
 bit for bit u_replay, of a PID agent within 1e-12 max(1, |q[t]|_inf) of ``closed_loop.pid_driver_step`` stepped from the device's own
 q[t].  That bar: the law is under twenty roundings of 2^-53 per step, the device may contract multiply-add pairs (so it is not bit for
@@ -14,12 +14,11 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_closed_loop_ensemble import (CHAIN, COUNTS, DELAYS, DOUBLES, check_chain, check_monitor, check_plant, configs_of, same, scenarios,
-                                       solver_of, teacher_force)      # noqa: F401  (solver_of is a fixture)
+from closed_loop_checks import (BAR, CHAIN, COUNTS, DELAYS, DOUBLES, check_chain, check_monitor, check_plant, configs_of, same, scenarios,
+                                 solver_of, teacher_force)      # noqa: F401  (solver_of is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-BAR = 1e-12
 PLANT_KW = dict(method='rk4', M=3, sim_steps=2, delay_steps=DELAYS)
 
 

@@ -1,123 +1,22 @@
 """A plant of its own in closed-loop batches on the device: DGSQP.step_batch(..., plant=PlantModel(...)) / dgsqp_set_plant
 (dev_plant_feedback, csrc/dgsqp_closed_loop.h).
 
-Every case first repeats the two checks of tests/test_closed_loop.py -- TEACHER FORCING (every step that ran is, bit for bit, the
-``solve_batch`` solve from the recorded (q[t], u_ws[t]): a plant only changes which state is fed back) and the warm-start chain with the
+Every case first repeats the two checks of tests/test_closed_loop.py (the helpers are those of tests/closed_loop_checks.py) -- TEACHER
+FORCING (every step that ran is, bit for bit, the ``solve_batch`` solve from the recorded (q[t], u_ws[t]): a plant only changes which state is fed back) and the warm-start chain with the
 records of steps that never ran.  Then the plant itself:
 
 * ``q[t+1]`` against the CPU oracle's next state (``oracle.dynamics`` on a copy of the game's POD with dt / S, the plant's integrator,
   sub-steps and vehicle fields), applied one control step at a time from the device's own ``q[t]`` and ``u_plant[t]`` so that errors do
   not compound along a chain: 1e-12 relative to max(1, |q|_inf), the device-against-oracle bar for x;
 * ``u_plant`` against the delay lines of the host mirror ``closed_loop.plant_feedback``: bit for bit, it is data movement."""
-import copy
-
 import numpy as np
 import pytest
 
+from closed_loop_checks import (BAR, COUNTS, DELAYS, DOUBLES, check_chain, check_plant, configs_of, same, scenarios, solver_of,
+                                 teacher_force)      # noqa: F401  (solver_of is a fixture)
 from conftest import agent_major
 
 pytestmark = pytest.mark.gpu
-
-DOUBLES = ('u', 'l', 'x', 'cond', 'cost')
-COUNTS = ('status', 'num_iters', 'qp_solves')
-BAR = 1e-12
-WORST = {}          # case -> largest relative deviation of q[t+1] from the oracle (printed by every case)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def same(a, b):
-    """Bit for bit (stricter than np.array_equal: NaN payloads and the sign of zero count)."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and (np.array_equal(bits(a), bits(b)) if a.dtype == np.float64 else np.array_equal(a, b))
-
-
-def teacher_force(s, res):
-    """One solve_batch over every step that ran; returns how many steps that were."""
-    bb, tt = np.nonzero(np.arange(res['status'].shape[1])[None, :] < res['steps_done'][:, None])
-    ref = s.solve_batch(res['q'][bb, tt], res['u_ws'][bb, tt])
-    for key in DOUBLES + COUNTS:
-        got = res[key][bb, tt]
-        bad = [(int(bb[i]), int(tt[i])) for i in range(len(bb)) if not same(got[i], ref[key][i])]
-        assert not bad, f'{key}: closed-loop steps (scenario, step) {bad[:8]} differ from solve_batch on the same inputs'
-    assert [res['msg'][b][t] for b, t in zip(bb, tt)] == ref['msg']
-    assert same(res['converged'][bb, tt], ref['converged'])
-    return len(bb)
-
-
-def check_chain(s, res, x0, u_am):
-    """The warm-start chain, u_applied, steps_done and the records of steps that never ran (check_feedback of tests/test_closed_loop.py
-    without its q rule: with a plant the next state is checked against the oracle instead)."""
-    from dgsqp_amd import closed_loop
-    B, T = res['status'].shape
-    done = res['steps_done']
-    assert same(res['q'][:, 0], x0) and same(res['u_ws'][:, 0], u_am)
-    assert res['q'].shape == (B, T + 1, s.n_q) and res['u_ws'].shape == (B, T + 1, s.n) and res['u_pred'].shape == (B, T, s.N, s.n_u)
-    assert same(res['u_applied'], res['u_pred'][:, :, 0]) and same(res['u_pred'], s._to_time_major(res['u']))
-    for t in range(T):
-        ran = t < done
-        ok = np.isfinite(res['q'][:, t + 1]).all(axis=-1)
-        _, ws_next, _ = closed_loop.feedback(res['x'][:, t], res['u'][:, t], res['status'][:, t], res['u_ws'][:, t], num_ua_d=s.num_ua_d)
-        assert same(res['u_ws'][ran & ok, t + 1], ws_next[ran & ok]), t
-        assert np.array_equal(done[ran], np.where(ok[ran], np.maximum(done[ran], t + 1), t + 1)), t      # a chain ends at its first non-finite state
-        idle = ~ran
-        assert (res['status'][idle, t] == -1).all() and (res['num_iters'][idle, t] == 0).all() and (res['qp_solves'][idle, t] == 0).all()
-        assert all(res['msg'][b][t] == 'not_run' for b in np.nonzero(idle)[0]) and not res['converged'][idle, t].any()
-        for key in DOUBLES:
-            assert np.isnan(res[key][idle, t]).all(), (key, t)
-        assert np.isnan(res['u_ws'][idle | ~ok, t + 1]).all() and np.isnan(res['q'][idle, t + 1]).all(), t
-        if 'u_plant' in res:
-            assert np.isnan(res['u_plant'][idle, t]).all() and np.isfinite(res['u_plant'][ran, t]).all(), t
-    assert ((done >= 1) & (done <= T)).all()
-
-
-def plant_problem(P, pt):
-    """The game's POD as the plant's ONE simulation step: dt / S, the plant's integrator, sub-steps and vehicle fields."""
-    from dgsqp_amd import _ffi
-    P2 = _ffi.ProblemT.from_buffer_copy(P)
-    P2.dt = P.dt / pt.sim_steps
-    P2.integrator, P2.substeps = pt.integrator, pt.substeps
-    if not pt.use_game_agents:
-        for a in range(P.M):
-            for name, _ in _ffi.AgentT._fields_[:22]:               # model .. lin_Br
-                setattr(P2.agents[a], name, getattr(pt.agents[a], name))
-    return P2
-
-
-def check_plant(oracle, s, res, plant, w=None, tag=''):
-    """q[t+1] against the oracle, u_plant against the host mirror's delay lines; returns the largest relative deviation."""
-    from dgsqp_amd import closed_loop
-    pt = plant.lower(s._problem)
-    P2 = plant_problem(s._problem, pt)
-    B, T = res['status'].shape
-    S, M = pt.sim_steps, s.M
-    assert res['u_plant'].shape == (B, T, S, s.n_u)
-    delay = [[pt.delay[a][j] for j in range(2)] for a in range(M)]
-    lines = closed_loop.new_lines(delay, lead=(B,))
-    qoff = np.concatenate(([0], np.cumsum(s.num_qa_d)))
-    worst = 0.0
-    for t in range(T):
-        ran = t < res['steps_done']
-        _, used, _ = closed_loop.plant_feedback(lambda q, u: q, res['q'][:, t], res['u_applied'][:, t], lines, sim_steps=S)
-        assert same(res['u_plant'][ran, t], used[ran]), f'{tag}: u_plant of step {t} is not what the delay lines deliver'
-        for b in np.nonzero(ran)[0]:
-            q = res['q'][b, t].copy()
-            for j in range(S):
-                for a in range(M):
-                    q[qoff[a]:qoff[a + 1]] = oracle.dynamics(P2, a, q[qoff[a]:qoff[a + 1]], res['u_plant'][b, t, j, 2 * a:2 * a + 2], derivs=False)[1]
-            if w is not None:
-                q = q + w[b, t]
-            got = res['q'][b, t + 1]
-            if not np.isfinite(q).all():
-                assert np.array_equal(np.isfinite(got), np.isfinite(q)), (tag, b, t)
-                continue
-            worst = max(worst, float(np.abs(got - q).max() / max(1.0, np.abs(q).max())))
-    WORST[tag] = worst
-    print(f'{tag}: max |q[t+1] - oracle| / max(1, |q|_inf) = {worst:.3e} over {int(res["steps_done"].sum())} control steps (bar {BAR:g})')
-    assert worst < BAR, (tag, worst)
-    return worst
 
 
 def run_and_check(oracle, s, x0, u_tm, T, plant, w=None, tag=''):
@@ -126,36 +25,6 @@ def run_and_check(oracle, s, x0, u_tm, T, plant, w=None, tag=''):
     teacher_force(s, res)
     check_plant(oracle, s, res, plant, w, tag)
     return res
-
-
-@pytest.fixture(scope='module')
-def solver_of(games):
-    """name -> DGSQP of conftest's game of that name, built once per module."""
-    from dgsqp_amd.solver import DGSQP
-    cache = {}
-
-    def get(name, **kw):
-        key = (name, tuple(sorted(kw.items())))
-        if key not in cache:
-            cache[key] = DGSQP(*games[name][0].solver_args(), print_method=None, **kw)
-        return cache[key]
-    yield get
-    cache.clear()
-
-
-def scenarios(g, B, seed):
-    from dgsqp_amd.montecarlo import sample_scenarios
-    return sample_scenarios(g, B, seed=seed)
-
-
-def configs_of(g, **scale):
-    """Copies of the game's per-agent dynamics configs; ``scale``: field -> factor (every agent) or {agent: factor}."""
-    cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
-    for field, f in scale.items():
-        for a, c in enumerate(cfgs):
-            k = f.get(a, 1.0) if isinstance(f, dict) else f
-            setattr(c, field, getattr(c, field) * k)
-    return cfgs
 
 
 def test_identity_plant(oracle, games, solver_of):
@@ -190,9 +59,6 @@ def test_mismatch_and_finer_integration(oracle, games, solver_of):
     for integ in ('rk2', 'rk3', 'euler'):                               # the other integrators, one control step each
         run_and_check(oracle, s, x0[:2], u_tm[:2], 1, PlantModel(dynamics_configs=plant.dynamics_configs, method=integ, M=2, sim_steps=3),
                       tag=f'mismatch kb_curve_N10 {integ}')
-
-
-DELAYS = [[2, 1], [0, 3]]
 
 
 def test_input_delay(oracle, games, solver_of):

@@ -98,3 +98,68 @@ def test_one_handle_through_every_entry_point(games):
         assert np.array_equal(got[k], ref[k]), ('qp_batch', k)
 
     solve(9, 113, 'B=9 (last)')
+
+
+def test_one_handle_through_every_closed_loop_setting(games):
+    """One long-lived DGSQP object runs step_batch launches whose shapes go up and down and whose settings change from launch to launch;
+    every key of every result must equal, bit for bit, the same launch on a handle created for it alone.  After the smaller launches the
+    fetchers are called through the C-ABI with exactly that launch's size: a side buffer that only grows must not make them ask for more,
+    and they return that launch's data."""
+    from closed_loop_checks import DELAYS, configs_of, same
+    from dgsqp_amd import _ffi
+    from dgsqp_amd.closed_loop import Drivers, PlantModel, perturbed_configs
+    from dgsqp_amd.montecarlo import sample_scenarios
+    from dgsqp_amd.solver import DGSQP
+    g = games['kb_curve_N10'][0]
+    make = lambda: DGSQP(*g.solver_args(), print_method=None)
+    old = make()
+    kw = dict(method='rk4', M=2, sim_steps=2)
+    plain = PlantModel(delay_steps=DELAYS, **kw)
+    rng = np.random.default_rng(7)
+
+    def per_chain(B):
+        return PlantModel(per_chain_configs=perturbed_configs(configs_of(g), dict(mass=0.2), B, seed=B), per_chain_delay_steps=rng.integers(0, 4, size=(B, 2, 2)), **kw)
+
+    def noise(B, T):
+        return 1e-2 * rng.standard_normal((B, T, old.n_q))
+
+    def replay(B, T):
+        rep = np.zeros((B, T, old.n_u))
+        rep[:, :, 2:4] = [0.3, 0.02]
+        return Drivers(kinds=['game', 'replay'], u_replay=rep)
+
+    def everything(B, T):
+        return dict(plant=per_chain(B), estimate_noise=noise(B, T), monitor='stop', drivers=Drivers(kinds=['pid', 'replay'], u_replay=replay(B, T).u_replay))
+
+    def fetched(name, shape):
+        """What dgsqp_fetch_<name> returns into a buffer of exactly the last launch's size, scenario-major."""
+        buf = np.empty(shape)
+        assert getattr(old._lib, 'dgsqp_fetch_' + name)(old._h, _ffi.dptr(buf), buf.size) == 0, (name, old._lib.dgsqp_last_error(old._h))
+        return buf.swapaxes(0, 1)
+
+    launches = [((5, 3), 'everything at once', everything),
+                ((2, 2), 'plain plant with delays', lambda B, T: dict(plant=plain)),
+                ((7, 1), 'vehicles and delays per chain', lambda B, T: dict(plant=per_chain(B))),
+                ((5, 3), 'estimates', lambda B, T: dict(plant=plain, estimate_noise=noise(B, T))),
+                ((2, 2), 'estimates and monitor', lambda B, T: dict(plant=plain, estimate_noise=noise(B, T), monitor=True)),
+                ((7, 1), "monitor 'stop'", lambda B, T: dict(plant=per_chain(B), monitor='stop')),
+                ((5, 3), 'PID driver on one car', lambda B, T: dict(plant=plain, drivers=Drivers(kinds=['game', 'pid']))),
+                ((2, 2), 'replay', lambda B, T: dict(plant=plain, drivers=replay(B, T))),
+                ((7, 1), 'no setting', lambda B, T: {}),
+                ((5, 3), 'everything at once, again', everything)]
+    for i, ((B, T), tag, settings) in enumerate(launches):
+        x0, u_ws = sample_scenarios(g, B, seed=120 + i)
+        args = settings(B, T)
+        got, ref = old.step_batch(x0, u_ws, T, keep_predictions=True, **args), make().step_batch(x0, u_ws, T, keep_predictions=True, **args)
+        assert sorted(got) == sorted(ref), tag
+        for k in ref:
+            if k not in ('time', 'kernel_ms'):
+                assert same(got[k], ref[k]) if isinstance(ref[k], np.ndarray) else got[k] == ref[k], (tag, k)
+        added = dict(u_plant='plant', q_est='estimate_noise', clearance='monitor', box_excess='monitor', hit_step='monitor', u_cmd='drivers')
+        assert all((k in got) == (arg in args) for k, arg in added.items()), tag
+        if (B, T) == (2, 2):              # smaller than an earlier launch with the same records
+            assert same(fetched('u_plant', (T, B, 2, old.n_u)), got['u_plant']), tag
+            if 'estimate_noise' in args:
+                assert same(fetched('q_est', (T, B, old.n_q)), got['q_est']), tag
+            if 'drivers' in args:
+                assert same(fetched('u_cmd', (T, B, old.n_u)), got['u_cmd']), tag
