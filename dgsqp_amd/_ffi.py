@@ -142,6 +142,9 @@ SIGNATURES = {
     'dgsqp_fetch_monitor': (C.c_int, [_H, _PD, _PD, _PI]),
     'dgsqp_set_drivers': (C.c_int, [_H, C.POINTER(DriversT), C.c_int32, C.c_int64, _PI, _PD, _PD]),
     'dgsqp_fetch_u_cmd': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_u_prev': (C.c_int, [_H, C.c_int64, _PD]),
+    'dgsqp_set_closed_loop_u_prev': (C.c_int, [_H, C.c_int, C.c_int64, _PD]),
+    'dgsqp_fetch_u_prev': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_stage_inputs': (C.c_int, [_H, C.c_int64, _PD, _PD]),
     'dgsqp_solve_staged': (C.c_int, [_H, _TM]),
     'dgsqp_launch_staged': (C.c_int, [_H]),

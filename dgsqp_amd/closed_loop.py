@@ -17,7 +17,10 @@ steps per control step, every input channel behind a delay line.  ``plant_feedba
 A launch with a plant may also choose, per agent and per chain, who produces the command that enters the plant (``Drivers``,
 ``dgsqp_set_drivers``): the game, the reference's PID lane follower run closed-loop on the true state, or a replayed sequence.
 ``pid_driver_step`` and ``drive`` are the documented mirrors of that choice (``dev_pid_law`` in csrc/dgsqp_pid.h, the drivers overload of
-``dev_plant_feedback``); the command they return is what ``plant_feedback`` takes as ``u_new``."""
+``dev_plant_feedback``); the command they return is what ``plant_feedback`` takes as ``u_new``.
+
+A launch may carry the command of step t into solve t + 1 as the input before its stage 0 (``step_batch(..., u_prev=True)``,
+``dgsqp_set_closed_loop_u_prev``): ``next_u_prev`` is the mirror of that rule."""
 from __future__ import annotations
 
 import ctypes as C
@@ -433,3 +436,16 @@ def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None)
                 raise ValueError("a 'replay' driver needs u_replay")
             u_cmd[NUA * a:NUA * a + NUA] = np.asarray(u_replay, dtype=np.float64)[NUA * a:NUA * a + NUA]
     return u_cmd, states
+
+
+def next_u_prev(u_t_stage0, u_cmd=None) -> np.ndarray:
+    """The input a chain's next solve takes as applied before its stage 0 (``step_batch(..., u_prev=...)``,
+    ``dgsqp_set_closed_loop_u_prev``) -- the host mirror of the carry in ``dg_closed_loop_kernel``: per agent, the command that entered that
+    agent's plant at this step.  ``u_t_stage0`` [..., n_u] is stage 0 of the solve's solution as returned (``u_applied``; also after
+    'diverged' / 'qp_fail', the feedback applies it then as well); ``u_cmd`` [..., n_u] the commands of a launch with drivers (``drive``), which
+    then take its place: a PID or replay agent's own command is what the game sees as that agent's previous input.  With delay lines this
+    is the value appended to the line, not the delayed one the plant integrated under.  Pure data movement: a copy."""
+    src = np.asarray(u_t_stage0 if u_cmd is None else u_cmd, dtype=np.float64)
+    if u_cmd is not None and src.shape != np.shape(u_t_stage0):
+        raise ValueError(f'u_cmd has shape {src.shape}, stage 0 of the solution {np.shape(u_t_stage0)}')
+    return src.copy()

@@ -2,6 +2,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC -o libdgsqp_hip.so dgsqp_api.hip
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,7 +20,8 @@
 
 
 // one staged batch of a grouped launch: its inputs and its outputs
-struct DgBatch { const double* x0; const double* u_ws; SolveOutPtrs O; };
+// (up, up_stride: the batch's u_prev as dg_solve_kernel takes it)
+struct DgBatch { const double* x0; const double* u_ws; SolveOutPtrs O; const double* up; int64_t up_stride; };
 #define DG_GROUP_MAX 64
 
 // ------------------------------------------------------------------------------------------------
@@ -32,7 +34,10 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
                 SolveOutPtrs O, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket,
                 double* __restrict__ trace, int trace_cap, unsigned int* __restrict__ drained,
                 double* __restrict__ itlog, int itlog_cap, const DgBatch* __restrict__ group, int group_n,
-                DgCoop* coop, double* coop_payload, int coop_start, int coop_verify, int coop_window, int coop_helpers, DgPark park) {
+                DgCoop* coop, double* coop_payload, int coop_start, int coop_verify, int coop_window, int coop_helpers, DgPark park,
+                const double* __restrict__ up, int64_t up_stride) {
+  // up: scenario b's u_prev is the n_u doubles at up + b * up_stride -- [B][n_u] with stride n_u (dgsqp_set_u_prev), or the handle's n_u
+  // zeros with stride 0
   Ctx c;
   c.coop = coop;
   c.park = park;
@@ -78,9 +83,10 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
     if (group) {        // grouped launch (dgsqp_launch_staged_group): ticket -> (staged batch, scenario); every batch has its own buffers
       const int64_t gi = b / B;
       b -= gi * B;
-      x0 = group[gi].x0; u_ws = group[gi].u_ws; O = group[gi].O;
+      x0 = group[gi].x0; u_ws = group[gi].u_ws; O = group[gi].O; up = group[gi].up; up_stride = group[gi].up_stride;
     }
     c.x0 = (cgptr)x0 + b * dg_prob.nq;
+    c.up = (cgptr)up + b * up_stride;
     c.trace = trace ? (gptr)trace + b * (int64_t)(1 + 2 * trace_cap) : nullptr;
     if (c.trace && TID == 0 && !resume) c.trace[0] = 0.0;
     c.itlog = itlog ? (gptr)itlog + b * (1 + (int64_t)itlog_cap * (dg_prob.n + dg_prob.nc)) : nullptr;
@@ -127,7 +133,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_evaluate_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restrict__ x0, const double* __restrict__ u,
                    const double* __restrict__ l, double* q, double* g, double* G, double* Q, double* x, double* l0,
-                   double* __restrict__ ws_all) {
+                   double* __restrict__ ws_all, const double* __restrict__ up, int64_t up_stride) {
   Ctx c;
   c.coop = nullptr; c.coop_payload = nullptr; c.coop_total = 0; c.coop_start = 0; c.coop_verify = 0; c.coop_window = 0; c.coop_helpers = 0;
   c.ws = (gptr)ws_all + (int64_t)blockIdx.x * dg_prob.ws_doubles;
@@ -137,6 +143,7 @@ dg_evaluate_kernel(const DgProb* __restrict__ D, int64_t B, const double* __rest
   dev_load_tables();
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     c.x0 = (cgptr)x0 + b * dg_prob.nq;
+    c.up = (cgptr)up + b * up_stride;
     __syncthreads();
     if (TID == 0) { dg_lds[L.scal + DG_XVALID] = 0.0; dg_lds[L.scal + DG_REG] = dg_prob.par.reg; dg_lds[L.scal + DG_OSQP_RHO] = 0.1; }
     for (int i = TID; i < n; i += NT) dg_lds[L.u + i] = u[b * n + i];
@@ -165,7 +172,8 @@ dg_evaluate_kernel(const DgProb* __restrict__ D, int64_t B, const double* __rest
 // Test hook: _solve_qp at the linearisation point (u, l).
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_qp_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restrict__ x0, const double* __restrict__ u,
-             const double* __restrict__ l, double* du, double* lhat, double* Qpd, int32_t* flag, double* info8, double* __restrict__ ws_all) {
+             const double* __restrict__ l, double* du, double* lhat, double* Qpd, int32_t* flag, double* info8, double* __restrict__ ws_all,
+             const double* __restrict__ up, int64_t up_stride) {
   Ctx c;
   c.coop = nullptr; c.coop_payload = nullptr; c.coop_total = 0; c.coop_start = 0; c.coop_verify = 0; c.coop_window = 0; c.coop_helpers = 0;
   c.ws = (gptr)ws_all + (int64_t)blockIdx.x * dg_prob.ws_doubles;
@@ -178,6 +186,7 @@ dg_qp_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restrict__
   if (TID == 0) { dg_lds[L.scal + DG_QP_NPREV] = 0.0; dg_lds[L.scal + DG_PSD_PD] = 0.0; }
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     c.x0 = (cgptr)x0 + b * dg_prob.nq;
+    c.up = (cgptr)up + b * up_stride;
     __syncthreads();
     if (TID == 0) { dg_lds[L.scal + DG_XVALID] = 0.0; dg_lds[L.scal + DG_REG] = dg_prob.par.reg; dg_lds[L.scal + DG_OSQP_RHO] = 0.1; }
     for (int i = TID; i < n; i += NT) dg_lds[L.u + i] = u[b * n + i];
@@ -270,6 +279,7 @@ enum DgSideBuf {
   SB_MON_SCRATCH, SB_CLEARANCE, SB_BOX_EXCESS, SB_HIT_STEP,   // the monitor: [grid][S][M][3]; clearance and box_excess [T][B], hit_step [B] int32
   SB_KIND, SB_PID, SB_REF, SB_U_REPLAY,                       // the drivers: [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
   SB_U_CMD, SB_CMD, SB_PID_STATE,                             // ... u_cmd [T][B][nu]; per workgroup: [grid][n] (2 M used: read as u_t is), [grid][M][3]
+  SB_U_PREV,                                                  // the carried input (dgsqp_set_closed_loop_u_prev): u_prev [T][B][nu]
   DG_SIDE_COUNT
 };
 struct DgBuf {
@@ -301,6 +311,21 @@ struct DgDriversState {
   bool has_ref = false, has_replay = false;
 };
 
+// u_{-1}, the input applied before stage 0 (Ctx.up).  dgsqp_set_u_prev keeps a host copy; staging a batch captures it in a device buffer of
+// the handle's own, so a later set does not reach a batch that is already staged.  A kernel is handed (pointer, stride between scenarios):
+// the captured [B][n_u] with stride n_u, or `zero` -- n_u zeros, allocated with the handle -- with stride 0.
+struct DgUPrevState {
+  std::vector<double> host;           // [B][n_u] as set (sticky)
+  int64_t B = 0;                      // 0: off
+  DgBuf staged;                       // what the staged batch captured ...
+  int64_t staged_stride = 0;          // ... n_u, or 0: the staged batch runs from `zero`
+  double* zero = nullptr;
+  const double* ptr() const { return staged_stride ? (const double*)staged.p : zero; }
+  int cl_mode = 0;                    // closed loop (dgsqp_set_closed_loop_u_prev): 0 off, 1 carry
+  int64_t cl_B = 0;                   // chains u_prev0 was given for (0: none, every chain starts from zeros)
+  std::vector<double> cl_host;        // u_prev0 [cl_B][n_u]
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -325,6 +350,7 @@ struct dgsqp_solver {
   DgEnsembleState ens;
   DgDriversState drv;
   DgSide side;                             // ... and their device buffers
+  DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -829,7 +855,8 @@ static int launch_solve(dgsqp_solver* L, int64_t total, const DgBatch* group, in
   hipLaunchKernelGGL(dg_solve_kernel, dim3(grid), dim3(DG_BLOCK), L->lds_bytes, stream, L->dp, L->B, L->staged.dbl(DG_Q), L->staged.dbl(DG_UWS),
                      L->staged.out(rec_count_batch(L->B)), L->ws, L->ticket, trace, L->trace.cap, L->drained_dev, itlog, L->itlog.cap,
                      group ? (const DgBatch*)L->d_group : (const DgBatch*)nullptr, group ? count : 0,
-                     coop ? L->d_coop : (DgCoop*)nullptr, L->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park);
+                     coop ? L->d_coop : (DgCoop*)nullptr, L->d_coop_payload, coop_start_trials(), coop_verify_mode(), coop_window_trials(), coop_max_helpers(), park,
+                     L->up.ptr(), L->up.staged_stride);
   HIPCHK(L, hipGetLastError());
   pool.next++;
   L->launch_stream = stream;
@@ -889,6 +916,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc(&h->dp, sizeof(DgProb)) != hipSuccess) return fail("hipMalloc(problem) failed");
   if (hipMemcpy(h->dp, &h->hp, sizeof(DgProb), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy(problem) failed");
   if (hipMalloc(&h->ticket, sizeof(unsigned long long)) != hipSuccess) return fail("hipMalloc(ticket) failed");
+  if (hipMalloc((void**)&h->up.zero, sizeof(double) * h->hp.nu) != hipSuccess || hipMemset(h->up.zero, 0, sizeof(double) * h->hp.nu) != hipSuccess) return fail("hipMalloc(u_prev zeros) failed");
   if (hipHostMalloc((void**)&h->drained_host, sizeof(unsigned int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail("hipHostMalloc(flag) failed");
   *h->drained_host = 1u;
   if (hipHostGetDevicePointer((void**)&h->drained_dev, h->drained_host, 0) != hipSuccess) return fail("hipHostGetDevicePointer failed");
@@ -926,6 +954,8 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->dp) (void)hipFree(h->dp);
   if (h->ticket) (void)hipFree(h->ticket);
+  if (h->up.zero) (void)hipFree(h->up.zero);
+  if (h->up.staged.p) (void)hipFree(h->up.staged.p);
   if (h->d_coop) (void)hipFree(h->d_coop);
   if (h->d_coop_payload) (void)hipFree(h->d_coop_payload);
   {
@@ -980,6 +1010,7 @@ const char* dgsqp_last_error(dgsqp_handle_t h) { return h ? h->err.c_str() : g_c
 static int stage_begin(dgsqp_solver* h, int64_t B) {
   HIPCHK(h, hipSetDevice(h->device));
   { const int rc = wait_idle(h); if (rc) return rc; }            // the buffers below belong to the launch in flight, if any
+  h->up.staged_stride = 0;          // (a batch staged without dgsqp_set_u_prev's array -- the sampler's -- runs from zeros)
   if (B == 0) return DGSQP_OK;
   int rc = rec_reserve(h, h->staged, rec_count_batch(B));
   if (!rc) rc = ensure_ws(h, (size_t)grid_for(h, B));
@@ -987,12 +1018,85 @@ static int stage_begin(dgsqp_solver* h, int64_t B) {
   return rc;
 }
 
+// dgsqp_set_u_prev and the entry points it applies to.  A call of another batch size is refused before it touches anything.
+static int u_prev_check(dgsqp_solver* h, int64_t B) {
+  if (h->up.B == 0 || B == 0 || h->up.B == B) return DGSQP_OK;
+  return refuse(h, "u_prev: ", "set for B = " + std::to_string(h->up.B) + " scenarios, this call has B = " + std::to_string(B) + " (dgsqp_set_u_prev with the new batch, or with B = 0 to switch it off)");
+}
+// after stage_begin: the staged batch captures the array (copy on h's stream, which every launch waits for)
+static int u_prev_stage(dgsqp_solver* h, int64_t B) {
+  if (h->up.B == 0 || h->up.B != B) return DGSQP_OK;
+  const size_t bytes = sizeof(double) * (size_t)B * h->hp.nu;
+  DgBuf& b = h->up.staged;
+  if (bytes > b.bytes) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.bytes = 0;
+    HIPCHK(h, hipMalloc(&b.p, bytes));
+    b.bytes = bytes;
+  }
+  HIPCHK(h, hipMemcpyAsync(b.p, h->up.host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  h->up.staged_stride = h->hp.nu;
+  return DGSQP_OK;
+}
+// the two synchronous hooks: the array (set for exactly this B) in a temporary buffer of the call, or the handle's zeros
+static int u_prev_hook(dgsqp_solver* h, int64_t B, TmpBuf& tb, const double** up, int64_t* stride) {
+  *up = h->up.zero; *stride = 0;
+  if (h->up.B == 0 || h->up.B != B) return DGSQP_OK;
+  double* d = tb.alloc<double>((size_t)B * h->hp.nu);
+  if (!d) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  HIPCHK(h, hipMemcpy(d, h->up.host.data(), sizeof(double) * (size_t)B * h->hp.nu, hipMemcpyHostToDevice));
+  *up = d; *stride = h->hp.nu;
+  return DGSQP_OK;
+}
+// both setters refuse entries that are not finite
+static int64_t first_non_finite(const double* v, int64_t count) {
+  for (int64_t i = 0; i < count; i++) if (!std::isfinite(v[i])) return i;
+  return -1;
+}
+
+int dgsqp_set_u_prev(dgsqp_handle_t h, int64_t B, const double* u_prev) {
+  { const int rc = setter_begin(h); if (rc) return rc; }
+  DgUPrevState& U = h->up;
+  if (!u_prev && B == 0) { U.B = 0; U.host.clear(); return DGSQP_OK; }
+  if (!u_prev || B <= 0) return refuse(h, "u_prev: ", "needs B > 0 scenarios and an array [B][n_u] (NULL with B = 0 switches it off)");
+  const int nu = h->hp.nu;
+  const int64_t bad = first_non_finite(u_prev, B * nu);
+  if (bad >= 0) return refuse(h, "u_prev: ", "entry [" + std::to_string(bad / nu) + "][" + std::to_string(bad % nu) + "] is not finite");
+  U.host.assign(u_prev, u_prev + B * nu);
+  U.B = B;
+  return DGSQP_OK;
+}
+
+int dgsqp_set_closed_loop_u_prev(dgsqp_handle_t h, int mode, int64_t B, const double* u_prev0) {
+  { const int rc = setter_begin(h); if (rc) return rc; }
+  DgUPrevState& U = h->up;
+  if (mode == 0) { U.cl_mode = 0; U.cl_B = 0; U.cl_host.clear(); return DGSQP_OK; }
+  if (mode != 1) return refuse(h, "closed-loop u_prev: ", "mode must be 0 (off) or 1 (carry), got " + std::to_string(mode));
+  if (B < 0) return refuse(h, "closed-loop u_prev: ", "B must not be negative");
+  const int nu = h->hp.nu;
+  if (u_prev0) {
+    const int64_t bad = first_non_finite(u_prev0, B * nu);
+    if (bad >= 0) return refuse(h, "closed-loop u_prev: ", "u_prev0 entry [" + std::to_string(bad / nu) + "][" + std::to_string(bad % nu) + "] is not finite");
+    U.cl_host.assign(u_prev0, u_prev0 + B * nu);
+    U.cl_B = B;
+  } else { U.cl_host.clear(); U.cl_B = 0; }
+  U.cl_mode = 1;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_u_prev(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  const char* none = "no closed-loop launch that carries u_prev has run";
+  return h ? side_fetch(h, {{SB_U_PREV, out, sizeof(double)}}, none, none, "u_prev", capacity_doubles) : DGSQP_E_ARG;
+}
+
 int dgsqp_stage_inputs(dgsqp_handle_t h, int64_t B, const double* x0, const double* u_ws) {
   if (!h || B < 0 || (B > 0 && (!x0 || !u_ws))) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
-  int rc = stage_begin(h, B);
+  int rc = u_prev_check(h, B);
+  if (rc) return rc;
+  rc = stage_begin(h, B);
   if (rc) return rc;
   h->B = B;
   if (B == 0) return DGSQP_OK;
+  if ((rc = u_prev_stage(h, B))) return rc;
   void* in[DG_REC_COUNT] = {};
   in[DG_Q] = (void*)x0; in[DG_UWS] = (void*)u_ws;
   if ((rc = rec_copy(h, h->staged, rec_count_batch(B), in, hipMemcpyHostToDevice))) return rc;
@@ -1028,7 +1132,7 @@ int dgsqp_launch_staged_group(const dgsqp_handle_t* hs, int count) {
   { const int rce = ensure_ws(L, (size_t)grid_for(L, L->B * count)); if (rce) return rce; }
   if (!L->d_group) HIPCHK(L, hipMalloc(&L->d_group, sizeof(DgBatch) * DG_GROUP_MAX));
   if (!L->group_host) HIPCHK(L, hipHostMalloc((void**)&L->group_host, sizeof(DgBatch) * DG_GROUP_MAX, hipHostMallocDefault));
-  for (int i = 0; i < count; i++) L->group_host[i] = DgBatch{hs[i]->staged.dbl(DG_Q), hs[i]->staged.dbl(DG_UWS), hs[i]->staged.out(rec_count_batch(L->B))};
+  for (int i = 0; i < count; i++) L->group_host[i] = DgBatch{hs[i]->staged.dbl(DG_Q), hs[i]->staged.dbl(DG_UWS), hs[i]->staged.out(rec_count_batch(L->B)), hs[i]->up.ptr(), hs[i]->up.staged_stride};
   const int rc = launch_solve(L, L->B * count, L->group_host, count);
   // (every handle was idle above: the leader is in flight exactly when the kernel was enqueued, and then so are the members' batches)
   if (L->in_flight)
@@ -1332,6 +1436,9 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   { const int rc = further_check_plant(h); if (rc) return rc; }
   { const int rc = drivers_check_launch(h, T, B); if (rc) return rc; }
   { const int rc = further_check_launch(h, T, B); if (rc) return rc; }
+  const DgUPrevState& U = h->up;
+  if (U.cl_mode && U.cl_B > 0 && U.cl_B != B)
+    return refuse(h, "closed-loop u_prev: ", "launch of B = " + std::to_string(B) + " chains, u_prev0 was set for " + std::to_string(U.cl_B));
   HIPCHK(h, hipSetDevice(h->device));
   // Step-major arrays: T x B of every record, one more slice of the state and warm-start chains; c = scenarios per record, keep = the
   // leading ones that are copied in and not filled.  Without x_out one [B][N+1][nq] slice serves every step, without l_out there is no l.
@@ -1357,6 +1464,16 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   cl.O = S.out(c);
   cl.x_step = x_out ? B * (int64_t)h->rec[DG_X].per : 0;
   cl.steps_done = (int32_t*)S.p[DG_DONE];
+  // the carried input: a record [T][B][nu] like u_cmd, slice 0 = u_prev0 (or zeros); without carry every solve reads the handle's zeros
+  cl.up = nullptr; cl.up_zero = U.zero;
+  h->side.left[SB_U_PREV] = 0;
+  if (U.cl_mode) {
+    const size_t slice = sizeof(double) * (size_t)B * h->hp.nu;
+    { const int rc = side_record(h, SB_U_PREV, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
+    cl.up = h->side.at<double>(SB_U_PREV);
+    if (U.cl_B > 0) HIPCHK(h, hipMemcpyAsync(cl.up, U.cl_host.data(), slice, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(h, hipMemsetAsync(cl.up, 0, slice, h->stream));
+  }
   DgPlantDev pd{};
   DgEnsembleDev ex{};
   if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
@@ -1407,10 +1524,13 @@ int dgsqp_solve_batch_f32(dgsqp_handle_t h, int64_t B, const float* x0, const fl
                           float* x_out, int32_t* status, int32_t* iters, int32_t* qp_solves, float* cond, float* cost,
                           dgsqp_timing_t* tm) {
   if (!h || B < 0 || (B > 0 && (!x0 || !u_ws))) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
-  int rc = stage_begin(h, B);
+  int rc = u_prev_check(h, B);
+  if (rc) return rc;
+  rc = stage_begin(h, B);
   if (rc) return rc;
   h->B = B;
   if (B == 0) return DGSQP_OK;
+  if ((rc = u_prev_stage(h, B))) return rc;          // (u_prev is fp64 also at the fp32 boundary: it is a setting, not one of the call's arrays)
   const DgRecCount c = rec_count_batch(B);
   const DgRecords& S = h->staged;
   size_t big = 0;
@@ -1507,9 +1627,13 @@ int dgsqp_evaluate_batch(dgsqp_handle_t h, int64_t B, const double* x0, const do
   HIPCHK(h, hipSetDevice(h->device));
   const DgProb& D = h->hp;
   const int grid = grid_for(h, B);
-  int rc = idle_with_ws(h, B);
+  int rc = u_prev_check(h, B);
+  if (rc) return rc;
+  rc = idle_with_ws(h, B);
   if (rc) return rc;
   TmpBuf tb;
+  const double* dup = nullptr; int64_t up_stride = 0;
+  if ((rc = u_prev_hook(h, B, tb, &dup, &up_stride))) return rc;
   const size_t n = D.n, nc = D.nc, nx = (size_t)(D.N + 1) * D.nq;
   double* dx0 = tb.alloc<double>(B * D.nq); double* du = tb.alloc<double>(B * n);
   double* dl = l ? tb.alloc<double>(B * nc) : nullptr;
@@ -1521,7 +1645,7 @@ int dgsqp_evaluate_batch(dgsqp_handle_t h, int64_t B, const double* x0, const do
   HIPCHK(h, hipMemcpy(du, u, sizeof(double) * B * n, hipMemcpyHostToDevice));
   if (l) HIPCHK(h, hipMemcpy(dl, l, sizeof(double) * B * nc, hipMemcpyHostToDevice));
   rc = run_sync(h, [&]() -> int {
-    hipLaunchKernelGGL(dg_evaluate_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, dq, dg, dG, dQ, dx, dl0, h->ws);
+    hipLaunchKernelGGL(dg_evaluate_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, dq, dg, dG, dQ, dx, dl0, h->ws, dup, up_stride);
     HIPCHK(h, hipGetLastError());
     return DGSQP_OK;
   });
@@ -1641,9 +1765,13 @@ int dgsqp_qp_batch_info(dgsqp_handle_t h, int64_t B, const double* x0, const dou
   HIPCHK(h, hipSetDevice(h->device));
   const DgProb& D = h->hp;
   const int grid = grid_for(h, B);
-  int rc = idle_with_ws(h, B);
+  int rc = u_prev_check(h, B);
+  if (rc) return rc;
+  rc = idle_with_ws(h, B);
   if (rc) return rc;
   TmpBuf tb;
+  const double* dup = nullptr; int64_t up_stride = 0;
+  if ((rc = u_prev_hook(h, B, tb, &dup, &up_stride))) return rc;
   const size_t n = D.n, nc = D.nc;
   double* dx0 = tb.alloc<double>(B * D.nq); double* du = tb.alloc<double>(B * n); double* dl = tb.alloc<double>(B * nc);
   double* ddu = du_out ? tb.alloc<double>(B * n) : nullptr; double* dlh = lhat ? tb.alloc<double>(B * nc) : nullptr;
@@ -1654,7 +1782,7 @@ int dgsqp_qp_batch_info(dgsqp_handle_t h, int64_t B, const double* x0, const dou
   HIPCHK(h, hipMemcpy(du, u, sizeof(double) * B * n, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(dl, l, sizeof(double) * B * nc, hipMemcpyHostToDevice));
   rc = run_sync(h, [&]() -> int {
-    hipLaunchKernelGGL(dg_qp_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, ddu, dlh, dQ, df, dinfo, h->ws);
+    hipLaunchKernelGGL(dg_qp_kernel, dim3(grid), dim3(DG_BLOCK), h->lds_bytes, h->stream, h->dp, B, dx0, du, dl, ddu, dlh, dQ, df, dinfo, h->ws, dup, up_stride);
     HIPCHK(h, hipGetLastError());
     return DGSQP_OK;
   });

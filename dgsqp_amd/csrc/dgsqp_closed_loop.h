@@ -15,6 +15,9 @@ struct DgClosedLoop {
   int64_t x_step;        // doubles between the prediction slices of consecutive steps: B (N+1) nq, or 0 when the caller keeps no
                          // predictions (one [B][N+1][nq] slice, reused by every step: x_t[b][1] has to exist somewhere)
   int32_t* steps_done;   // [B]
+  double* up;            // [T][B][nu]     carry on: slice t = the input applied before solve t (slice 0 from the host); fed back like q and
+                         // uws.  Null: carry off, every solve reads up_zero
+  const double* up_zero; // the handle's nu zeros
 };
 
 // A plant of its own (dgsqp_set_plant; reference DGSQP/dynamics/dynamics_simulator.py:11-40): after every solve the state is advanced by
@@ -332,6 +335,13 @@ __device__ __noinline__ int dev_estimate(DgPlantDriversDev dd, int64_t tb_b, con
 // PLANT is empty, one DgPlantDev, one DgEnsembleDev, or one DgPlantDriversDev: the instantiation without a plant has the argument list it always
 // had and holds nothing of the plant, the one with a DgPlantDev nothing of the further settings, the one with a DgEnsembleDev nothing of
 // the drivers.
+// Channel j of the command that entered agent a's plant at the step whose records start tb_b scenarios in: stage 0 of the solution u_t,
+// or with drivers what dev_plant_feedback stored in u_cmd.
+__device__ inline double dev_command(int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
+__device__ inline double dev_command(const DgPlantDev&, int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
+__device__ inline double dev_command(const DgEnsembleDev&, int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
+__device__ inline double dev_command(const DgPlantDriversDev& dd, int64_t tb_b, int a, int j, const double*) { return dd.u_cmd[tb_b * dg_prob.nu + a * DGSQP_NUA + j]; }
+
 template <class... PLANT> struct DgHasEstimates { static constexpr bool value = false; };
 template <> struct DgHasEstimates<DgEnsembleDev> { static constexpr bool value = true; };
 template <> struct DgHasEstimates<DgPlantDriversDev> { static constexpr bool value = true; };
@@ -368,6 +378,7 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
         c.x0 = (cgptr)x0;
       }
       else c.x0 = (cgptr)(cl.q + (tb + b) * nq);
+      c.up = cl.up ? (cgptr)(cl.up + (tb + b) * dg_prob.nu) : (cgptr)cl.up_zero;
       if (dg_prob.par.variant == DGSQP_VARIANT_V2) dev_solve_v2(c, (cgptr)uws_t, b, O);
       else dev_solve(c, (cgptr)uws_t, b, O);
       // feedback.  The solve's records were stored by other lanes of this workgroup: fence + barrier before they are read back.
@@ -395,6 +406,12 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
         const int k = (i % (N * DGSQP_NUA)) / DGSQP_NUA;    // agent-major: agent a holds rows k = 0 .. N-1 of DGSQP_NUA inputs
         uws_next[i] = keep ? uws_t[i] : u_t[k + 1 < N ? i + DGSQP_NUA : i];
       }
+      // carry: the command that entered each agent's plant at this step is the next solve's u_{-1} -- stage 0 of u_t as returned (also after
+      // 'diverged' / 'qp_fail': the feedback applied it), or with drivers u_cmd[t][b], read back by the lane that stored it.  With delay
+      // lines it is the value appended to the line, not the delayed one the plant integrated under.
+      if (cl.up && t < cl.T && TID < dg_prob.M)
+        for (int j = 0; j < DGSQP_NUA; j++)
+          cl.up[(tb + B + b) * dg_prob.nu + TID * DGSQP_NUA + j] = dev_command(pd..., tb + b, TID, j, u_t);
       // the next dev_solve of this workgroup reads q_next / uws_next through ordinary loads
       __threadfence_block();
       __syncthreads();

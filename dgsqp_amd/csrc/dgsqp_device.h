@@ -104,6 +104,7 @@ struct DgCoopJob {
   int pos, window;                // ... but none beyond pos + window, pos = the trial its owner is at (bounds the work wasted when the search ends early)
   double mu, phi, dphi, S0, S1;   // the Armijo test's constants
   const double* x0;               // the scenario's initial state
+  const double* up;               // ... and the input applied before its stage 0 (Ctx.up)
   double* payload;                // u[n], du[n], l[nc], lhat[nc] of the base point
   double phi_out[DG_COOP_PHI];
 };
@@ -167,6 +168,7 @@ struct Ctx {
   const unsigned long long* ticket;   // the launch's ticket counter (deferral only while fresh tickets remain)
   gptr ws;      // this workgroup's global workspace
   cgptr x0;
+  cgptr up;     // u_{-1}: the joint input applied before stage 0, n_u doubles in the order of u_pred[0] (agent a's at DGSQP_NUA a); the handle's zeros when none is set
   gptr trace;   // optional per-scenario event log: [0] = number of (code, value) pairs, then the pairs
   int trace_cap;   // capacity in pairs
   gptr itlog;   // optional per-scenario iterate log: [0] = number of records, then records of (n + n_c) doubles (u, l):

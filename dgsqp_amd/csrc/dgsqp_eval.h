@@ -651,7 +651,7 @@ __device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it) {
 #pragma unroll
     for (int i = 0; i < nqa; i++) v[i] = B[i * 2 + j];
     // direct part of dJ^a/du^a_{t0,j}
-    const double uk = ue[it], um = t0 > 0 ? ue[it - DGSQP_NUA] : 0.0;
+    const double uk = ue[it], um = t0 > 0 ? ue[it - DGSQP_NUA] : c.up[a * DGSQP_NUA + j];
     double qacc = ag.w_in[j] * uk + ag.w_rate[j] * (uk - um);
     if (t0 + 1 < D.N) qacc -= ag.w_rate[j] * (ue[it + DGSQP_NUA] - uk);
     int d = D.stage_dense0[t0 + 1];  // dense gradients are ordered by stage
@@ -719,7 +719,7 @@ __device__ __noinline__ void dev_constraint_values(const Ctx& c, clptr ue) {
       case DG_R_RATE_UB:
       case DG_R_RATE_LB: {
         const int col = am_col(D, R.a, R.k, R.idx);
-        const double du = ue[col] - (R.k > 0 ? ue[col - DGSQP_NUA] : 0.0);
+        const double du = ue[col] - (R.k > 0 ? ue[col - DGSQP_NUA] : c.up[R.a * DGSQP_NUA + R.idx]);
         g = R.type == DG_R_RATE_UB ? du - D.P.dt * ag.rate_ub[R.idx] : D.P.dt * ag.rate_lb[R.idx] - du;
       } break;
       case DG_R_IN_UB: g = ue[am_col(D, R.a, R.k, R.idx)] - ag.in_ub[R.idx]; break;
@@ -1298,7 +1298,7 @@ __device__ inline void dev_costs(const Ctx& c, clptr ue, double* Jout) {
     double s = 0;
     for (int k = 0; k < D.N; k++) {
       for (int j = 0; j < DGSQP_NUA; j++) {
-        const double uk = ue[am_col(D, a, k, j)], um = k > 0 ? ue[am_col(D, a, k - 1, j)] : 0.0;
+        const double uk = ue[am_col(D, a, k, j)], um = k > 0 ? ue[am_col(D, a, k - 1, j)] : c.up[a * DGSQP_NUA + j];
         s += 0.5 * ag.w_in[j] * uk * uk + 0.5 * ag.w_rate[j] * (uk - um) * (uk - um);
       }
       s += dev_state_cost(D, a, x + k * D.nq, false, (double*)nullptr, (double*)nullptr);

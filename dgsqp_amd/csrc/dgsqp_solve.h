@@ -1068,7 +1068,7 @@ __device__ __noinline__ double dev_v2_sum_obj(const Ctx& c, bool grad) {
   for (int i = TID; i < n; i += NT) {
     const int a = i / (N * DGSQP_NUA), rem = i % (N * DGSQP_NUA), t = rem / DGSQP_NUA, j = rem % DGSQP_NUA;
     const dgsqp_agent_t& ag = D.P.agents[a];
-    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : 0.0;
+    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : c.up[a * DGSQP_NUA + j];
     part += 0.5 * ag.w_in[j] * uk * uk + 0.5 * ag.w_rate[j] * (uk - um) * (uk - um);
   }
   const double obj = block_sum(part, lds + L.red);
@@ -1089,7 +1089,7 @@ __device__ __noinline__ double dev_v2_sum_obj(const Ctx& c, bool grad) {
   for (int i = TID; i < n; i += NT) {
     const int a = i / (N * DGSQP_NUA), rem = i % (N * DGSQP_NUA), t = rem / DGSQP_NUA, j = rem % DGSQP_NUA;
     const dgsqp_agent_t& ag = D.P.agents[a];
-    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : 0.0;
+    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : c.up[a * DGSQP_NUA + j];
     double sacc = ag.w_in[j] * uk + ag.w_rate[j] * (uk - um);
     if (t + 1 < N) sacc -= ag.w_rate[j] * (ue[i + DGSQP_NUA] - uk);
     const int nqa = D.nqa[a];
@@ -1172,7 +1172,7 @@ __device__ __noinline__ double dev_phi_trial_adjoint(const Ctx& c, double alpha,
   for (int i = TID; i < D.n; i += NT) {
     const int a = i / (D.N * DGSQP_NUA), rem = i % (D.N * DGSQP_NUA), t = rem / DGSQP_NUA, j = rem % DGSQP_NUA;
     const dgsqp_agent_t& ag = D.P.agents[a];
-    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : 0.0;
+    const double uk = ue[i], um = t > 0 ? ue[i - DGSQP_NUA] : c.up[a * DGSQP_NUA + j];
     double s = ag.w_in[j] * uk + ag.w_rate[j] * (uk - um);
     if (t + 1 < D.N) s -= ag.w_rate[j] * (ue[i + DGSQP_NUA] - uk);
     int r;
@@ -1367,6 +1367,7 @@ __device__ __noinline__ int dev_coop_help(Ctx& c) {
       for (int r = TID; r < D.nc; r += NT) { lds[L.l + r] = pl[2 * D.n + r]; lds[L.o_lhat + r] = pl[2 * D.n + D.nc + r]; }
       if (TID == 0) lds[L.scal + DG_XVALID] = 0.0;
       c.x0 = (cgptr)(const double*)__hip_atomic_load((unsigned long long*)&job->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      c.up = (cgptr)(const double*)__hip_atomic_load((unsigned long long*)&job->up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     dev_coop_trial(c, job, j);
@@ -1418,7 +1419,7 @@ __device__ inline double dev_line_search(const Ctx& c, double mu, double phi, do
             job->claimed = (1ull << lo) - 1ull; job->ready = 0ull; job->pruned = 0ull;        // trials below lo are the owner's
             job->lo = lo; job->iters = iters; job->pos = i; job->window = c.coop_window;
             job->mu = mu; job->phi = phi; job->dphi = dphi; job->S0 = S0; job->S1 = S1;
-            job->x0 = (const double*)c.x0; job->payload = pl;
+            job->x0 = (const double*)c.x0; job->up = (const double*)c.up; job->payload = pl;
             __threadfence();
             __hip_atomic_store(&job->seq, job->seq + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);     // even -> odd: open
             __hip_atomic_fetch_add(&c.coop->open, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);

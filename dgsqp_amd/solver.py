@@ -9,6 +9,7 @@ only lowers the game description to PODs and reshapes results.
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import ctypes as C
 import time
@@ -287,6 +288,17 @@ def coerce_inputs(x0, u_ws, dtype, N: int, n_q: int, num_ua_d):
     return x0, u_ws
 
 
+def coerce_u_prev(u_prev, B: int, n_u: int) -> np.ndarray:
+    """What every entry point makes of its ``u_prev``: a C-contiguous fp64 ``[B, n_u]`` array -- the joint input applied before stage 0 of
+    each scenario, in the order of ``u_pred[0]``.  Any other shape and entries that are not finite are refused.  Needs no handle."""
+    up = np.ascontiguousarray(u_prev, dtype=np.float64)
+    if up.shape != (B, n_u):
+        raise ValueError(f'u_prev must be [B, n_u] = {(B, n_u)}, got {up.shape}')
+    if not np.isfinite(up).all():
+        raise ValueError('u_prev has entries that are not finite')
+    return up
+
+
 def _record_ptrs(out: dict, fptr=_ffi.dptr) -> tuple:
     """The eight result arguments of the C-ABI, in its order, from a record dictionary (``None`` entries become NULL)."""
     return (fptr(out['u']), fptr(out['l']), fptr(out['x']), _ffi.iptr(out['status']), _ffi.iptr(out['num_iters']),
@@ -306,8 +318,8 @@ class _Setting(NamedTuple):
 
 def solve_batches(solvers, batches) -> list:
     """Several Monte-Carlo batches of the SAME game and size in ONE launch (``dgsqp_launch_staged_group``): ``solvers`` are DGSQP
-    objects of that game (one per batch: every batch keeps its own device buffers), ``batches`` the matching ``(x0, u_ws)`` pairs as
-    ``solve_batch`` takes them -- or the batch size alone for a batch that is staged on the device already (``sample_batch(stage=True)``:
+    objects of that game (one per batch: every batch keeps its own device buffers), ``batches`` the matching ``(x0, u_ws)`` pairs or
+    ``(x0, u_ws, u_prev)`` triples as ``solve_batch`` takes them -- or the batch size alone for a batch that is staged on the device already (``sample_batch(stage=True)``:
     sampling, solve and results never pass through host arrays in between).  A launch ends with its slowest scenario; grouping lets the workgroups that are done with one batch
     go on with the next instead of idling behind that tail.  Returns one ``solve_batch``-style dictionary per batch, bit-identical
     to separate ``solve_batch`` calls."""
@@ -319,10 +331,11 @@ def solve_batches(solvers, batches) -> list:
         if isinstance(bt, (int, np.integer)):          # already staged on the device (DGSQP.sample_batch(..., stage=True)): just its size
             staged.append(int(bt))
             continue
-        x0, u_ws = s._inputs(*bt)
+        x0, u_ws = s._inputs(*bt[:2])
         B = x0.shape[0]
-        if lib.dgsqp_stage_inputs(s._h, B, _ffi.dptr(x0), _ffi.dptr(u_ws)) != 0:
-            raise RuntimeError('dgsqp_stage_inputs failed: ' + lib.dgsqp_last_error(s._h).decode())
+        with s._u_prev_set(bt[2] if len(bt) > 2 else None, B):      # (captured by the staging; cleared again before the launch)
+            if lib.dgsqp_stage_inputs(s._h, B, _ffi.dptr(x0), _ffi.dptr(u_ws)) != 0:
+                raise RuntimeError('dgsqp_stage_inputs failed: ' + lib.dgsqp_last_error(s._h).decode())
         staged.append(B)
     t0 = time.time()
     arr = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
@@ -401,12 +414,16 @@ class DGSQP(AbstractSolver):
                  qp_method: Optional[str] = None,
                  osqp_rho_carry: bool = False,
                  mixed_precision: bool = False,
-                 workgroups_per_cu: int = 1):
+                 workgroups_per_cu: int = 1,
+                 carry_u_prev: bool = False):
         """``eig_floor``, ``snap_active_bounds``: implementation knobs, see ``build_params``; the defaults are the reference's
         literal formulas (``_nearestPD`` floor 1e-10, DGSQP.py:1293; no adjustment of the QP step).  ``qp_method``: 'active_set'
         (exact KKT point) or 'osqp' (OSQP's own ADMM + polish arithmetic), see ``resolve_qp_method``.  ``workgroups_per_cu=2``: this solver
         runs on ``libdgsqp_hip_b256.so`` (256-thread workgroups, half the LDS arena, two per CU): 1.2-1.5 x the throughput on batches >> 512 of
-        n <= 64 games, identical results; games it cannot hold raise (DGSQP_E_TOO_LARGE).  Solvers of different builds do not share launches."""
+        n <= 64 games, identical results; games it cannot hold raise (DGSQP_E_TOO_LARGE).  Solvers of different builds do not share launches.
+        ``carry_u_prev=True``: ``solve()`` / ``step()`` measure the stage-0 rate rows and rate cost against ``self.u_prev`` -- which ``step()``
+        sets to ``u_pred[0]``, the input it just applied -- instead of resetting it to zeros as the reference does (DGSQP.py:305-308)."""
+        self.carry_u_prev = bool(carry_u_prev)
         self.joint_dynamics = joint_dynamics
         self.M = joint_dynamics.n_a
         self.print_method = (lambda s: None) if print_method is None else print_method
@@ -479,6 +496,20 @@ class DGSQP(AbstractSolver):
     def _inputs(self, x0, u_ws, dtype=np.float64):
         return coerce_inputs(x0, u_ws, dtype, self.N, self.n_q, self.num_ua_d)
 
+    @contextlib.contextmanager
+    def _u_prev_set(self, u_prev, B: int):
+        """``dgsqp_set_u_prev`` around the calls of one entry point: set when ``u_prev`` is given, switched off again whatever happens."""
+        if u_prev is None:
+            yield
+            return
+        up = coerce_u_prev(u_prev, B, self.n_u)
+        if self._lib.dgsqp_set_u_prev(self._h, B, _ffi.dptr(up)) != 0:
+            raise ValueError('dgsqp_set_u_prev failed: ' + self._lib.dgsqp_last_error(self._h).decode())
+        try:
+            yield
+        finally:
+            self._lib.dgsqp_set_u_prev(self._h, 0, None)
+
     def _records(self, lead: tuple, ftype=np.float64, predictions: bool = True) -> dict:
         """Uninitialised record arrays of leading shape ``lead`` ([B], or [T, B] step-major) for the library to fill."""
         return dict(u=np.empty(lead + (self.n,), ftype),
@@ -499,10 +530,12 @@ class DGSQP(AbstractSolver):
         return out
 
     # ---- batched entry point -------------------------------------------------------------------
-    def solve_batch(self, x0: np.ndarray, u_ws: np.ndarray, dtype=np.float64) -> dict:
+    def solve_batch(self, x0: np.ndarray, u_ws: np.ndarray, dtype=np.float64, u_prev: Optional[np.ndarray] = None) -> dict:
         """B independent ``solve()`` calls.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] (time-major,
         as ``set_warm_start``) or [B, n] (agent-major).  ``dtype=np.float32``: single-precision arrays at the boundary
-        (``dgsqp_solve_batch_f32``: widened on the device, fp64 solve, results rounded to fp32)."""
+        (``dgsqp_solve_batch_f32``: widened on the device, fp64 solve, results rounded to fp32).  ``u_prev`` [B, n_u]: the joint input applied
+        before each scenario's stage 0 -- what the stage-0 rate rows and rate cost are measured against (``dgsqp_set_u_prev``, for this call
+        only; fp64 whatever ``dtype``); ``None``: zeros, the reference's ``solve()``."""
         f32 = np.dtype(dtype) == np.float32
         ftype = np.float32 if f32 else np.float64
         fptr = (lambda a: a.ctypes.data_as(C.POINTER(C.c_float))) if f32 else _ffi.dptr
@@ -512,13 +545,15 @@ class DGSQP(AbstractSolver):
         out = self._records((B,), ftype)
         tm = _ffi.TimingT()
         t0 = time.time()
-        rc = getattr(self._lib, what)(self._h, B, fptr(x0), fptr(u_ws), *_record_ptrs(out, fptr), C.byref(tm))
+        with self._u_prev_set(u_prev, B):
+            rc = getattr(self._lib, what)(self._h, B, fptr(x0), fptr(u_ws), *_record_ptrs(out, fptr), C.byref(tm))
         if rc != 0:
             raise RuntimeError(f'{what} failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
         return self._finish(out, t0, tm)
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
-                   keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False, drivers=None) -> dict:
+                   keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False, drivers=None,
+                   u_prev=None) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -547,6 +582,12 @@ class DGSQP(AbstractSolver):
         The solves and the warm-start chain do not change.  The result gains u_cmd [B, T, n_u], the commands the plants received (NaN
         where a step never ran); u_applied stays stage 0 of the prediction.
 
+        ``u_prev`` (needs no plant), for this call only: ``True`` or an array [B, n_u] carries the command that entered each agent's plant at
+        step t into solve t + 1 as the input before its stage 0 (``dgsqp_set_closed_loop_u_prev``; host mirror
+        ``closed_loop.next_u_prev``), starting from zeros or from the array: the stage-0 rate rows and rate cost then limit the change of the
+        command ACROSS control steps.  ``None``: every solve is measured against zeros, the reference's ``solve()``.  The result gains u_prev
+        [B, T, n_u], what each solve ran with (NaN after a chain's end).
+
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
         steps_done [B], time, kernel_ms; with ``keep_predictions`` also x [B, T, N+1, n_q] and l [B, T, n_c]."""
@@ -572,7 +613,10 @@ class DGSQP(AbstractSolver):
             raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
         if plant is None and (estimate_noise is not None or monitor):
             raise ValueError('estimate_noise and monitor need a plant (PlantModel() is the identity plant)')
-        noise = pt = ensemble = drv = None
+        noise = pt = ensemble = drv = up0 = None
+        carry = u_prev is not None and u_prev is not False
+        if carry and u_prev is not True:
+            up0 = coerce_u_prev(u_prev, B, self.n_u)
         if estimate_noise is not None:
             noise = np.asarray(estimate_noise, dtype=np.float64)
             if noise.shape != (B, T, self.n_q):
@@ -591,7 +635,8 @@ class DGSQP(AbstractSolver):
                     _Setting('estimate_noise', noise is not None and (T, B, dptr(noise)), (0, 0, None), 'q_est', dict(q_est=(self.n_q,))),
                     _Setting('monitor', bool(monitor) and (2 if monitor == 'stop' else 1,), (0,), 'monitor', dict(clearance=(), box_excess=()), ('hit_step',), sized=False),
                     _Setting('drivers', drv is not None and (C.byref(drv[0]), T, B, iptr(drv[1]), dptr(drv[2]), dptr(drv[3])), (None, 0, 0, None, None, None),
-                             'u_cmd', dict(u_cmd=(self.n_u,)))]
+                             'u_cmd', dict(u_cmd=(self.n_u,))),
+                    _Setting('closed_loop_u_prev', carry and (1, B if up0 is not None else 0, dptr(up0)), (0, 0, None), 'u_prev', dict(u_prev=(self.n_u,)))]
         on = [st for st in settings if st.on]
         chains = {k: np.empty(B, np.int32) for st in on for k in st.chains}
         sm.update({k: np.empty((T, B) + tail) for st in on for k, tail in st.steps.items()})
@@ -611,8 +656,8 @@ class DGSQP(AbstractSolver):
                     if getattr(self._lib, 'dgsqp_fetch_' + st.fetch)(self._h, *into) != 0:
                         raise RuntimeError(f'dgsqp_fetch_{st.fetch} failed: ' + last_error())
         finally:
-            if plant is not None:
-                for st in reversed(settings):
+            for st in reversed(settings):
+                if st.on or plant is not None:
                     getattr(self._lib, 'dgsqp_set_' + st.name)(self._h, *st.off)
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
         out.update(chains, steps_done=steps_done)
@@ -696,8 +741,8 @@ class DGSQP(AbstractSolver):
         return out
 
     # ---- test hooks ----------------------------------------------------------------------------
-    def evaluate_batch(self, x0, u, l=None):
-        """One ``_evaluate(u, l, x0, up=0, hessian=True)`` per row (DGSQP.py:509-533) + dual init."""
+    def evaluate_batch(self, x0, u, l=None, u_prev=None):
+        """One ``_evaluate(u, l, x0, up, hessian=True)`` per row (DGSQP.py:509-533) + dual init; ``up`` = ``u_prev`` [B, n_u], or zeros."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         u = np.ascontiguousarray(u, dtype=np.float64)
         B = x0.shape[0]
@@ -705,24 +750,27 @@ class DGSQP(AbstractSolver):
         n, nc = self.n, self.n_c_total
         out = dict(q=np.empty((B, n)), g=np.empty((B, nc)), G=np.empty((B, nc, n)), Q=np.empty((B, n, n)),
                    x=np.empty((B, self.N + 1, self.n_q)), l0=np.empty((B, nc)))
-        rc = self._lib.dgsqp_evaluate_batch(self._h, B, _ffi.dptr(x0), _ffi.dptr(u), _ffi.dptr(l), _ffi.dptr(out['q']),
-                                            _ffi.dptr(out['g']), _ffi.dptr(out['G']), _ffi.dptr(out['Q']), _ffi.dptr(out['x']),
-                                            _ffi.dptr(out['l0']))
+        with self._u_prev_set(u_prev, B):
+            rc = self._lib.dgsqp_evaluate_batch(self._h, B, _ffi.dptr(x0), _ffi.dptr(u), _ffi.dptr(l), _ffi.dptr(out['q']),
+                                                _ffi.dptr(out['g']), _ffi.dptr(out['G']), _ffi.dptr(out['Q']), _ffi.dptr(out['x']),
+                                                _ffi.dptr(out['l0']))
         if rc != 0:
             raise RuntimeError(f'dgsqp_evaluate_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
         return out
 
-    def qp_batch(self, x0, u, l, want_Qpd=True):
+    def qp_batch(self, x0, u, l, want_Qpd=True, u_prev=None):
         """One ``_solve_qp`` (DGSQP.py:232-266) per row at the linearisation point (u, l).  ``want_Qpd=False`` leaves the projected
-        Hessian on the device -- the path the solve itself takes (the certified ``_nearestPD`` shortcut only runs then)."""
+        Hessian on the device -- the path the solve itself takes (the certified ``_nearestPD`` shortcut only runs then).  ``u_prev`` as
+        ``solve_batch`` takes it."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         u = np.ascontiguousarray(u, dtype=np.float64)
         l = np.ascontiguousarray(l, dtype=np.float64)
         B = x0.shape[0]
         out = dict(du=np.empty((B, self.n)), lhat=np.empty((B, self.n_c_total)), Qpd=np.empty((B, self.n, self.n)) if want_Qpd else None,
                    flag=np.empty(B, np.int32), info=np.zeros((B, 8)))
-        rc = self._lib.dgsqp_qp_batch_info(self._h, B, _ffi.dptr(x0), _ffi.dptr(u), _ffi.dptr(l), _ffi.dptr(out['du']),
-                                           _ffi.dptr(out['lhat']), _ffi.dptr(out['Qpd']), _ffi.iptr(out['flag']), _ffi.dptr(out['info']))
+        with self._u_prev_set(u_prev, B):
+            rc = self._lib.dgsqp_qp_batch_info(self._h, B, _ffi.dptr(x0), _ffi.dptr(u), _ffi.dptr(l), _ffi.dptr(out['du']),
+                                               _ffi.dptr(out['lhat']), _ffi.dptr(out['Qpd']), _ffi.iptr(out['flag']), _ffi.dptr(out['info']))
         if rc != 0:
             raise RuntimeError(f'dgsqp_qp_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
         return out           # info: OSQP's diagnostics with qp_method='osqp' (include/dgsqp.h: dgsqp_qp_batch_info), zeros otherwise
@@ -785,7 +833,8 @@ class DGSQP(AbstractSolver):
     # ---- reference single-scenario surface -----------------------------------------------------
     def solve(self, states: List[VehicleState], parameters: np.ndarray = np.array([])) -> dict:
         solve_start = time.time()
-        self.u_prev = np.zeros(self.n_u)
+        if not self.carry_u_prev:
+            self.u_prev = np.zeros(self.n_u)
         x0 = self.joint_dynamics.state2q(states)
         u_init = copy.copy(self.u_ws)
         self.print_method(self.solver_name)
@@ -795,7 +844,7 @@ class DGSQP(AbstractSolver):
             self.set_trace((iters + 1) * (16 + 6 * int(self._cparams.line_search_iters)))
         self.set_iterate_log(iters + 2)
         try:
-            res = self.solve_batch(x0[None, :], u_init[None, :])
+            res = self.solve_batch(x0[None, :], u_init[None, :], u_prev=np.asarray(self.u_prev)[None, :] if self.carry_u_prev else None)
             events = self.fetch_trace(1)[0] if want_iters else None
             u_log, l_log = self.fetch_iterate_log(1)[0]
         finally:

@@ -8,8 +8,15 @@ mean box excess (how far the worst state entry is from its bound, negative: insi
 the game's solution -- an opponent that does not play the equilibrium the ego assumes -- and prints clearance and hit statistics next to the
 self-play ones.
 
+The last columns are the actuator's view: per input channel (u_a, u_steer) the largest jump of the command that entered a plant between two
+control steps, |cmd[t] - cmd[t-1]| / (dt rate_ub) with cmd[-1] = 0, over every agent and chain, and the share of control steps with a jump
+beyond the game's own rate limit.  Without ``--carry-u-prev`` every solve measures its stage-0 rate rows against zero, so the limit holds
+inside a prediction and not between two of them; with it the command of step t is the next solve's input before stage 0
+(``step_batch(..., u_prev=True)``) and the limit holds along the chain wherever the solve converged.
+
     python examples/closed_loop_robustness.py --batch 1024 --steps 20 --spreads 0 0.05 0.1 0.2
     python examples/closed_loop_robustness.py --opponent pid
+    python examples/closed_loop_robustness.py --carry-u-prev
 """
 import argparse
 import copy
@@ -24,6 +31,20 @@ from dgsqp_amd.montecarlo import kinematic_racing_game                          
 from dgsqp_amd.solver import DGSQP                                                # noqa: E402
 
 
+def command_jumps(r, lim):
+    """(largest jump per channel [2], share of steps that ran with a jump over the limit) of the commands the plants received: u_cmd with
+    drivers, else stage 0 of the solution; in units of ``lim`` [n_u] = dt rate_ub.  NaN for a game without rate rows (``lim`` None): there is
+    no limit to measure against."""
+    if lim is None:
+        return np.full(2, np.nan), np.nan
+    cmd = r['u_cmd'] if 'u_cmd' in r else r['u_applied']
+    prev = np.concatenate([np.zeros_like(cmd[:, :1]), cmd[:, :-1]], axis=1)
+    jump = np.abs(cmd - prev) / lim                                 # NaN where a step never ran
+    ran = np.isfinite(jump).all(axis=-1)
+    worst = np.nanmax(jump.reshape(-1, lim.size // 2, 2), axis=(0, 1)) if ran.any() else np.full(2, np.nan)
+    return worst, float((jump[ran].max(axis=-1) > 1.0 + 1e-9).mean()) if ran.any() else np.nan
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=1024, help='chains per launch')
@@ -34,6 +55,7 @@ def main():
     ap.add_argument('--sim-steps', type=int, default=4, help='simulation steps of the plant per control step')
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--opponent', choices=('game', 'pid'), default='game', help="who drives car 2: its part of the game's solution, or the PID lane follower")
+    ap.add_argument('--carry-u-prev', action='store_true', help="carry each step's command into the next solve as the input before its stage 0")
     args = ap.parse_args()
 
     game = kinematic_racing_game('curve', N=args.N)
@@ -42,16 +64,22 @@ def main():
     smp = s.sample_batch(game, B, seed=args.seed)
     nominal = [copy.deepcopy(m.model_config) for m in game.joint_model.dynamics_models]
     noise = args.noise * np.random.default_rng(args.seed).standard_normal((B, T, s.n_q))
-    print(f'{B} chains x {T} steps, estimate noise {args.noise:g}, plant: rk4, {args.sim_steps} simulation steps per control step')
+    P = s._problem
+    has_rate = all(P.agents[a].has_rate for a in range(s.M))          # (a game without rate rows stores rate_ub = 0)
+    lim = np.array([P.dt * P.agents[a].rate_ub[j] for a in range(s.M) for j in range(2)]) if has_rate else None
+    print(f'{B} chains x {T} steps, estimate noise {args.noise:g}, plant: rk4, {args.sim_steps} simulation steps per control step, '
+          f'u_prev {"carried" if args.carry_u_prev else "zero in every solve"}')
     opponents = [('self-play', None)] + ([('pid', Drivers(kinds=['game', 'pid']))] if args.opponent == 'pid' else [])
-    print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]')
+    print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]   max jump / (dt rate_ub): u_a, u_steer   steps over the limit')
     for spread in args.spreads:
         ens = perturbed_configs(nominal, dict(mass=spread, drag_coefficient=spread, slip_coefficient=spread), B, args.seed)
         plant = PlantModel(per_chain_configs=ens, method='rk4', M=2, sim_steps=args.sim_steps)
         for name, drivers in opponents:
-            r = s.step_batch(smp['x0'], smp['u_ws'], T, plant=plant, estimate_noise=noise, monitor='stop', drivers=drivers)
+            r = s.step_batch(smp['x0'], smp['u_ws'], T, plant=plant, estimate_noise=noise, monitor='stop', drivers=drivers,
+                             u_prev=True if args.carry_u_prev else None)
+            worst, share = command_jumps(r, lim)
             print(f'{spread:6.3f}   {name:9s}   {np.mean(r["hit_step"] >= 0):21.4f}   {np.nanmin(r["clearance"]):13.4f}   {np.nanmean(r["clearance"]):14.4f}   '
-                  f'{np.nanmean(r["box_excess"]):15.4f}   {r["steps_done"].mean():14.2f}   {r["kernel_ms"]:11.1f}')
+                  f'{np.nanmean(r["box_excess"]):15.4f}   {r["steps_done"].mean():14.2f}   {r["kernel_ms"]:11.1f}   {worst[0]:27.3f}, {worst[1]:7.3f}   {share:20.4f}')
 
 
 if __name__ == '__main__':

@@ -452,6 +452,31 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
 int dgsqp_fetch_u_cmd(dgsqp_handle_t h, double* out /* [T][B][n_u] */, int64_t capacity_doubles);
 
 /*
+ * The input before stage 0.  The stage-0 rate rows  -/+ (u_0 - u_prev) <= dt rate  and the stage-0 rate cost  1/2 w_rate (u_0 - u_prev)^2
+ * of a solve are measured against u_prev, the joint input applied before the scenario's first stage: n_u doubles in the order of
+ * u_pred[0] (agent a's two inputs at 2 a).  Without a setting u_prev = 0, the reference's solve() (DGSQP.py:305-308).
+ *
+ * dgsqp_set_u_prev: sticky, like dgsqp_set_plant; the array is copied.  It applies to the handle's SUBSEQUENT dgsqp_solve_batch,
+ * dgsqp_solve_batch_f32, dgsqp_stage_inputs (captured when staging: a later set does not reach a batch that is already staged, and every
+ * handle of a pipeline or a grouped launch keeps its own), dgsqp_evaluate_batch and dgsqp_qp_batch(_info) of exactly B scenarios; such a
+ * call with another B returns DGSQP_E_ARG (message starting "u_prev: ").  A batch staged by dgsqp_sample_batch runs from zeros.
+ * u_prev = NULL with B = 0: off.  An entry that is not finite is refused (DGSQP_E_ARG).  Closed-loop launches ignore it.
+ *
+ * dgsqp_set_closed_loop_u_prev, mode 1 (carry): solve t of chain b of the handle's SUBSEQUENT closed-loop launches runs with
+ * u_prev[t][b], where u_prev[0][b] = u_prev0[b] (NULL: zeros; otherwise the launch must have exactly B chains) and u_prev[t+1][b] is,
+ * per agent, the command that entered that agent's plant at step t: stage 0 of u[t][b] as returned -- also after 'diverged' and
+ * 'qp_fail', the feedback applies it then as well --, or with drivers u_cmd[t][b]; with delay lines the value appended to the line, not
+ * the delayed one the plant integrated under.  Mode 0: off.  It needs no plant.  dgsqp_solve_batch ignores it.  DGSQP_E_ARG, message
+ * starting "closed-loop u_prev: ": another mode, B < 0, an entry of u_prev0 that is not finite; and, from dgsqp_closed_loop_batch, a
+ * launch whose B differs from a u_prev0's.
+ * dgsqp_fetch_u_prev: u_prev of the last launch that carried, [T][B][n_u]; NaN where it was never written (the steps after a chain's
+ * end).  capacity_doubles = what out can hold (DGSQP_E_ARG when it is too small or when no such launch has run).
+ */
+int dgsqp_set_u_prev(dgsqp_handle_t h, int64_t B, const double* u_prev /* [B][n_u], or NULL with B = 0: off */);
+int dgsqp_set_closed_loop_u_prev(dgsqp_handle_t h, int mode /* 0 off, 1 carry */, int64_t B, const double* u_prev0 /* [B][n_u] or NULL = zeros */);
+int dgsqp_fetch_u_prev(dgsqp_handle_t h, double* out /* [T][B][n_u] */, int64_t capacity_doubles);
+
+/*
  * Device-resident variant used by bench.py: inputs are staged once with
  * dgsqp_stage_inputs(); dgsqp_solve_staged() runs only the solve kernel on
  * the handle's stream; dgsqp_fetch_results() copies results back.

@@ -20,7 +20,9 @@ asserts that both produce identical status, num_iters and q.
 delay per chain), ``estimates`` (that plant, solves from q + 1e-3 N(0, 1)), and the last two with the monitor recording
 (``ensemble+monitor``, ``estimates+monitor``); and two launches with drivers (``closed_loop.Drivers``) on that plant: ``pid`` (car 2 on the
 PID lane follower with its default gains, references from x0) and ``replay`` (car 2 replays the commands the game gave it in the ``plant``
-launch: the same chains as ``plant``, bit for bit, through the drivers' kernel).  ``--kinds`` restricts the list (a library without the newer entry points can still time
+launch: the same chains as ``plant``, bit for bit, through the drivers' kernel).  ``--carry-u-prev`` adds ``carry-u-prev``: ``plain`` with the command of step t carried into solve t + 1 as the input
+before its stage 0 (``step_batch(..., u_prev=True)``) -- other solves, so other chains: its time stands next to the others, not against them.
+``--kinds`` restricts the list (a library without the newer entry points can still time
 ``plain,plant``), ``--label`` names the build in the output, ``--append`` adds to ``--out`` instead of replacing it.
 
     python tools/closed_loop_bench.py --ensemble --repeats 5 --out profiles/closed_loop_ensemble_dyn_curve_N25.txt
@@ -62,6 +64,7 @@ def host_loop(s, x0, u_am, T):
 
 
 KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor', 'pid', 'replay')
+CARRY = 'carry-u-prev'          # added by --carry-u-prev (or named in --kinds): 'plain' with step_batch(..., u_prev=True)
 
 
 def ensemble_bench(args, g, s, x0, u_am):
@@ -70,11 +73,15 @@ def ensemble_bench(args, g, s, x0, u_am):
     from dgsqp_amd import closed_loop
     B, T = args.batch, args.steps
     kinds = [k for k in args.kinds.split(',') if k]
-    unknown = [k for k in kinds if k not in KINDS]
+    if args.carry_u_prev and CARRY not in kinds:
+        kinds.append(CARRY)
+    unknown = [k for k in kinds if k not in KINDS + (CARRY,)]
     if unknown:
-        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS}')
+        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS + (CARRY,)}')
     base = dict(method='rk4', M=10, sim_steps=2)
     calls = {'plain': lambda: s.step_batch(x0, u_am, T)}
+    if CARRY in kinds:
+        calls[CARRY] = lambda: s.step_batch(x0, u_am, T, u_prev=True)
     plant = closed_loop.PlantModel(delay_steps=[[0, 1], [0, 0]], **base)
     calls['plant'] = lambda: s.step_batch(x0, u_am, T, plant=plant)
     if 'pid' in kinds:
@@ -87,7 +94,7 @@ def ensemble_bench(args, g, s, x0, u_am):
         again = calls['replay']()
         for key in ('status', 'num_iters', 'q', 'u_plant'):
             assert np.array_equal(again[key], own[key], equal_nan=True), f'{key}: the replay of the plant launch\'s own commands differs from it'
-    if any(k not in ('plain', 'plant', 'pid', 'replay') for k in kinds):
+    if any(k not in ('plain', 'plant', 'pid', 'replay', CARRY) for k in kinds):
         cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
         spread = dict(mass=0.1, drag_coefficient=0.1, pacejka_d_front=0.1, pacejka_d_rear=0.1)
         delays = np.random.default_rng(args.seed).integers(0, 3, size=(B, len(cfgs), 2))
@@ -128,6 +135,7 @@ def main():
     ap.add_argument('--plant', action='store_true', help='also time step_batch with a plant of its own (c)')
     ap.add_argument('--ensemble', action='store_true', help='time the launch kinds of a robustness study instead (see the module docstring)')
     ap.add_argument('--kinds', default=','.join(KINDS), help='with --ensemble: comma-separated subset of ' + ', '.join(KINDS))
+    ap.add_argument('--carry-u-prev', action='store_true', help='with --ensemble: also time the plain launch with the command carried into the next solve (kind ' + CARRY + ')')
     ap.add_argument('--label', default='this build', help='with --ensemble: names the build in the report')
     ap.add_argument('--append', action='store_true', help='with --ensemble: add to --out instead of replacing it')
     ap.add_argument('--out', default=str(ROOT / 'profiles' / 'closed_loop_dyn_curve_N25.txt'))

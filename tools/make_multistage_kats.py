@@ -19,7 +19,8 @@ adjoints, no A/B/E/F/G tensors: nothing is shared with oracle/ or dgsqp_amd/csrc
     racing costs          DGSQP_ALGAMES_monte_carlo_chicane.py:47, :223-277; comparison_study_barc/exact_dynamic_game_dynamic.py:140-168
     merge costs / lanes   DGSQP_merge_monte_carlo.py:66-74, :253-261, :316-342
     rows, their order     DGSQP.py:730-821 (shared rows first, then per agent: function rows, input ub, input lb, state ub, state lb;
-                          state boxes from k = 1), u_{-1} = 0
+                          state boxes from k = 1); u_{-1} = 0, or the scenario's u_prev in the *_uprev cases (the `up` that
+                          DGSQP.py:509-533, :656-670 carry through every stage function)
 
 The numbers the reference computes in double precision before it builds its expressions (track tables, h = dt / M, dt * rate) are
 computed in double precision here too and enter the 60-digit arithmetic exactly.  Vehicle parameters are the defaults of the
@@ -238,15 +239,21 @@ def stage_state_cost(spec, a, xs, mg):
     return J
 
 
-def costs(spec, traj, ua, mg):
-    """J^a = sum_k stage(x_k, u_k, u_{k-1}) + terminal(x_N), u_{-1} = 0 (DGSQP.py:656-670).  traj[a][k] the states, ua[a][k] the inputs."""
+def zero_up(M):
+    return [[mp.mpf(0), mp.mpf(0)] for _ in range(M)]
+
+
+def costs(spec, traj, ua, mg, up=None):
+    """J^a = sum_k stage(x_k, u_k, u_{k-1}) + terminal(x_N), u_{-1} = up[a] (None: 0) (DGSQP.py:656-670).  traj[a][k] the states, ua[a][k]
+    the inputs."""
+    up = zero_up(spec['M']) if up is None else up
     N, M = spec['N'], spec['M']
     out = []
     for a in range(M):
         c = spec['agents'][a]['cost']
         J = mp.mpf(0)
         for k in range(N):
-            um = ua[a][k - 1] if k > 0 else [mp.mpf(0), mp.mpf(0)]
+            um = ua[a][k - 1] if k > 0 else up[a]
             for j in range(2):
                 J += F(c['input_weight'][j]) * ua[a][k][j] ** 2 / 2 + F(c['input_rate_weight'][j]) * (ua[a][k][j] - um[j]) ** 2 / 2
             J += stage_state_cost(spec, a, [traj[b][k] for b in range(M)], mg)
@@ -264,8 +271,9 @@ def costs(spec, traj, ua, mg):
     return out
 
 
-def rows(spec, traj, ua, mg):
-    """C(u), DGSQP.py:730-821."""
+def rows(spec, traj, ua, mg, up=None):
+    """C(u), DGSQP.py:730-821; the rate rows of stage 0 are measured against up[a] (None: 0)."""
+    up = zero_up(spec['M']) if up is None else up
     N, M = spec['N'], spec['M']
     dt = spec['dt']
     C = []
@@ -278,7 +286,7 @@ def rows(spec, traj, ua, mg):
         for a in range(M):
             ag = spec['agents'][a]
             if k < N and ag['rate'] is not None:                  # chicane.py:282-285
-                um = ua[a][k - 1] if k > 0 else [mp.mpf(0), mp.mpf(0)]
+                um = ua[a][k - 1] if k > 0 else up[a]
                 for j in range(2):
                     C.append((ua[a][k][j] - um[j]) - F(dt * ag['rate'][0][j]))
                     C.append(F(dt * ag['rate'][1][j]) - (ua[a][k][j] - um[j]))
@@ -300,9 +308,10 @@ def rows(spec, traj, ua, mg):
 class GameMP:
     """J^a and C at u + h (sum_i c_i e_i + c_v v), the agents' rollouts cached by the part of the perturbation that reaches them
     (the dynamics are decoupled: dynamics_models.py:2521-2528)."""
-    def __init__(self, spec, x0, u, l, h, v=None):
+    def __init__(self, spec, x0, u, l, h, v=None, up=None):
         self.spec, self.h = spec, h
         M, N = spec['M'], spec['N']
+        self.up = zero_up(M) if up is None else [[mp.mpf(e) for e in up[2 * a:2 * a + 2]] for a in range(M)]      # joint order: agent a's inputs at 2 a
         self.n = 2 * M * N
         self.u = [mp.mpf(e) for e in u]
         self.v = None if v is None else [F(e) for e in v]
@@ -336,7 +345,7 @@ class GameMP:
         if key not in self.points:
             both = [self.agent(a, pert, cv) for a in range(self.spec['M'])]
             traj, ua = [b[0] for b in both], [b[1] for b in both]
-            J, C = costs(self.spec, traj, ua, self.mg), rows(self.spec, traj, ua, self.mg)
+            J, C = costs(self.spec, traj, ua, self.mg, self.up), rows(self.spec, traj, ua, self.mg, self.up)
             lC = mp.fsum(li * ci for li, ci in zip(self.l, C) if li != 0)
             self.points[key] = (J, C, [j + lC for j in J])
         return self.points[key]
@@ -351,15 +360,15 @@ def split(nested):
     return hi, lo
 
 
-def answers(spec, x0, u, l, dps, h_exp, vs=(), full=True):
+def answers(spec, x0, u, l, dps, h_exp, vs=(), full=True, up=None):
     """x, g, J, q and G, Q (``full``) and/or G v, Q v for the directions ``vs``, each as (float64 array, float64 array of what the
-    rounding to float64 left over); plus the breakpoint margin."""
+    rounding to float64 left over); plus the breakpoint margin.  ``up`` [n_u]: the joint input before stage 0 (None: zeros)."""
     mp.mp.dps = dps
     h = mp.mpf(10) ** (-h_exp)
     M, N = spec['M'], spec['N']
     n = 2 * M * N
     own = lambda i: i // (2 * N)
-    gm = GameMP(spec, x0, u, l, h)
+    gm = GameMP(spec, x0, u, l, h, up=up)
     J0, C0, L0 = gm.at()
     nc = len(C0)
     assert nc == len(l), (nc, len(l))
@@ -389,7 +398,7 @@ def answers(spec, x0, u, l, dps, h_exp, vs=(), full=True):
     margin = (gm.mg.m, gm.mg.what)
     Gv, Qv = [], []
     for v in vs:
-        gv = GameMP(spec, x0, u, l, h, v=v)
+        gv = GameMP(spec, x0, u, l, h, v=v, up=up)
         gv.cache.update({k: val for k, val in gm.cache.items()})          # (rollouts without a v part are the same)
         Cp, Cm = gv.at((), 1)[1], gv.at((), -1)[1]
         Gv.append([(cp - cm) / (2 * h) for cp, cm in zip(Cp, Cm)])
@@ -412,26 +421,29 @@ def relerr(a, b):
 
 
 def _run(job):
-    spec, x0, u, l, dps, h_exp, vs, full = job
-    return answers(spec, x0, u, l, dps, h_exp, vs, full)
+    spec, x0, u, l, dps, h_exp, vs, full, up = job
+    return answers(spec, x0, u, l, dps, h_exp, vs, full, up)
 
 
 KEYS = ('x', 'g', 'q', 'G', 'Q', 'Gv', 'Qv')
 
 
-def solve_case(spec, x0, u, l, vs=(), full=True, pool=None, n_sens=8, seed=0, dps=60):
-    """All scenarios of a case: the answers at ``dps`` digits, their accuracy record against 90 digits, their sensitivity."""
+def solve_case(spec, x0, u, l, vs=(), full=True, pool=None, n_sens=8, seed=0, dps=60, up=None):
+    """All scenarios of a case: the answers at ``dps`` digits, their accuracy record against 90 digits, their sensitivity.  ``up`` [B, n_u]:
+    u_prev per scenario (None: zeros); it is perturbed with x0 and u for the sensitivity (after them: a case without one draws what it drew)."""
     rng = np.random.default_rng(seed)
     mp.mp.dps = 60
     jobs, tags = [], []
     for b in range(len(x0)):
-        jobs += [(spec, x0[b], u[b], l[b], dps, 20, vs, full), (spec, x0[b], u[b], l[b], 90, 30, vs, full)]
+        upb = None if up is None else up[b]
+        jobs += [(spec, x0[b], u[b], l[b], dps, 20, vs, full, upb), (spec, x0[b], u[b], l[b], 90, 30, vs, full, upb)]
         tags += [(b, 'ans'), (b, 'chk')]
         for _ in range(n_sens):
             # 2^-53 relative, as exact 60-digit numbers (a double times 1 + 2^-53 is no double)
             px = [mp.mpf(float(e)) * (1 + mp.mpf(2) ** -53 * int(s)) for e, s in zip(x0[b], rng.choice((-1, 1), len(x0[b])))]
             pu = [mp.mpf(float(e)) * (1 + mp.mpf(2) ** -53 * int(s)) for e, s in zip(u[b], rng.choice((-1, 1), len(u[b])))]
-            jobs.append((spec, px, pu, l[b], dps, 20, vs, full))
+            pp = None if upb is None else [mp.mpf(float(e)) * (1 + mp.mpf(2) ** -53 * int(s)) for e, s in zip(upb, rng.choice((-1, 1), len(upb)))]
+            jobs.append((spec, px, pu, l[b], dps, 20, vs, full, pp))
             tags.append((b, 'sens'))
     res = list(pool.map(_run, jobs)) if pool is not None else [_run(j) for j in jobs]
     out = {}
@@ -480,6 +492,29 @@ def flatten_spec(spec):
             out[pre + k] = np.asarray(ag[k], float)
         out[pre + 'radius'] = float(ag['radius'])
     return out
+
+
+def unflatten_spec(kat):
+    """The inverse of ``flatten_spec``: the game of a fixture from its ``p_*`` entries alone (what a test needs to run this generator on a
+    committed case without the reference tree)."""
+    item = lambda k: kat[k].item() if kat[k].ndim == 0 else kat[k]
+    track = None
+    if int(item('p_has_track')):
+        track = {k[len('p_track_'):]: (float(kat[k]) if kat[k].ndim == 0 else [float(e) for e in kat[k]]) for k in kat.files if k.startswith('p_track_')}
+    agents = []
+    for a in range(int(item('p_M'))):
+        pre = f'p_a{a}_'
+        take = lambda group: {k[len(pre + group):]: item(k) for k in kat.files if k.startswith(pre + group)}
+        cost = {k: (v if isinstance(v, str) else (float(v) if np.ndim(v) == 0 else tuple(float(e) for e in v))) for k, v in take('cost_').items()}
+        lanes = []
+        for j in range(int(item(pre + 'n_lane'))):
+            ln = [float(e) for e in kat[pre + f'lane{j}']]
+            lanes.append(dict(brk=ln[0], r=ln[1], n_lo=tuple(ln[2:4]), n_hi=tuple(ln[4:6]), anchor=tuple(ln[6:8])))
+        rate = tuple(tuple(float(e) for e in r) for r in kat[pre + 'rate']) if int(item(pre + 'has_rate')) else None
+        agents.append(dict(model=str(item(pre + 'model')), vehicle=take('vehicle_'), cost=cost, rate=rate, lanes=lanes,
+                           **{k: [float(e) for e in kat[pre + k]] for k in ('in_ub', 'in_lb', 'st_ub', 'st_lb')}, radius=float(item(pre + 'radius'))))
+    return dict(M=int(item('p_M')), N=int(item('p_N')), dt=float(item('p_dt')), method=str(item('p_method')), substeps=int(item('p_substeps')),
+                track=track, obstacle_rows=bool(item('p_obstacle_rows')), agents=agents)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -615,11 +650,19 @@ def slow_branch_points(x0, seg1, before=0.04):
 
 
 def case_inputs(case, defaults, shift=0):
-    """(spec, x0, u, l, directions, checks) of a case; ``checks(x)`` asserts what the points are there for, on the generator's own
+    """(spec, x0, u, l, directions, checks, u_prev [B, n_u] or None) of a case; ``checks(x)`` asserts what the points are there for, on the generator's own
     trajectory x [B, N + 1, n_q].  ``shift`` is added to the sampler's seed (main takes the first that keeps the margin)."""
     sys.path.insert(0, str(ROOT / 'tests'))
     sys.path.insert(0, str(ROOT))
     import multistage_kat as mk
+    if case.endswith(UPREV):
+        # the parent's game and scenarios, and a u_prev per scenario drawn inside the input box (its inner 90 %)
+        spec, x0, u, l, vs, checks, _ = case_inputs(case[:-len(UPREV)], defaults, shift)
+        rng = np.random.default_rng(4242 + sum(map(ord, case)))
+        lb, ub = (np.concatenate([np.asarray(ag[k], float) for ag in spec['agents']]) for k in ('in_lb', 'in_ub'))
+        assert np.isfinite(lb).all() and np.isfinite(ub).all(), 'a *_uprev case needs a finite input box'
+        mid, half = 0.5 * (lb + ub), 0.45 * (ub - lb)
+        return spec, x0, u, l, vs, checks, mid + half * rng.uniform(-1.0, 1.0, (len(x0), len(lb)))
     game = mk.build_game(case)
     vs, checks = (), (lambda x: None)
     if case == 'kin2_euler_N3':
@@ -680,14 +723,15 @@ def case_inputs(case, defaults, shift=0):
         vs = tuple(np.random.default_rng(99).standard_normal((2, 2 * 3 * N)))
     else:
         raise ValueError(case)
-    return spec, x0, u, l, vs, checks
+    return spec, x0, u, l, vs, checks, None
 
 
 # digits of the first pass where 60 are too few: the merge game's L^a is ~1e3 x the largest entry of its Q (goal costs of ~100 against
 # input weights of 0.1), and 1e-60 |L| / 4 h^2 leaves Q at 2e-18 of its largest entry -- above the 1e-18 this tool accepts
 DIGITS = {'uni3_merge_N3': 70}
+UPREV = '_uprev'      # <parent>_uprev: the parent's scenarios with a non-zero input before stage 0, stored as ``u_prev``
 CASES = ('kin2_euler_N3', 'kin2_rk4_N4', 'kin3_euler_N3', 'dyn2_rk4m3_N3', 'dyn2_rk4m10_N2', 'dyn2_rk3_N3', 'dyn2_rk2_lin_N3', 'uni3_merge_N3',
-         'kin3_N20_dir', 'kin3_N25_dir')
+         'kin3_N20_dir', 'kin3_N25_dir', 'kin2_rk4_N4' + UPREV, 'dyn2_rk4m3_N3' + UPREV)
 
 
 def main():
@@ -701,16 +745,16 @@ def main():
         for case in args.cases:
             t = time.time()
             for shift in range(50):                            # the first seed whose points keep the margin (nominal rollout, 30 digits)
-                spec, x0, u, l, vs, checks = case_inputs(case, defaults, shift)
+                spec, x0, u, l, vs, checks, up = case_inputs(case, defaults, shift)
                 mp.mp.dps = 30
-                gms = [GameMP(spec, x0[b], u[b], l[b], mp.mpf(0)) for b in range(len(x0))]
+                gms = [GameMP(spec, x0[b], u[b], l[b], mp.mpf(0), up=None if up is None else up[b]) for b in range(len(x0))]
                 if all(gm.at() and gm.mg.m > 1.1 * MARGIN for gm in gms):
                     break
                 print(f'{case}: seed shift {shift} comes within {min(gm.mg.m for gm in gms):.2e} of a breakpoint, next', flush=True)
             else:
                 raise SystemExit(f'{case}: no seed keeps the margin')
             full = not vs
-            out, acc, sens, margin = solve_case(spec, x0, u, l, vs, full, pool, dps=DIGITS.get(case, 60))
+            out, acc, sens, margin = solve_case(spec, x0, u, l, vs, full, pool, dps=DIGITS.get(case, 60), up=up)
             assert margin[0] > MARGIN, f'{case}: a state comes within {margin[0]:.2e} of a breakpoint ({margin[1]})'
             checks(out['x'].reshape(len(x0), spec['N'] + 1, -1))
             worst = max(acc.values())
@@ -722,6 +766,8 @@ def main():
             data = dict(flatten_spec(spec), x0=x0, u=u, l=l, margin=margin[0], **out)
             if vs:
                 data['v'] = np.array(vs)
+            if up is not None:
+                data['u_prev'] = up
             data.update({'acc_' + k: v for k, v in acc.items()})
             data.update({'sens_' + k: v for k, v in sens.items()})
             np.savez_compressed(GOLD / f'multistage_{case}.npz', **data)
