@@ -18,6 +18,8 @@ MAX_DELAY = 16       # DGSQP_MAX_DELAY: longest input delay line of a closed-loo
 
 STATUS_MSG = ['conv_abs_tol', 'conv_rel_tol', 'max_it', 'diverged', 'qp_fail', 'time_limit']
 NOT_RUN = -1         # DGSQP_NOT_RUN: a closed-loop step that never ran (step_batch reports it as 'not_run')
+HELD = -2            # DGSQP_HELD: a closed-loop step that followed the plan it held and did not solve ('held')
+STATUS_NAMES = {**dict(enumerate(STATUS_MSG)), NOT_RUN: 'not_run', HELD: 'held'}
 
 dbl2 = C.c_double * NUA
 
@@ -99,6 +101,14 @@ class DriversT(C.Structure):
 DRIVER_GAME, DRIVER_PID, DRIVER_REPLAY = 0, 1, 2        # DGSQP_DRIVER_*
 
 
+class HoldT(C.Structure):
+    """dgsqp_hold_t: the planning rate and the fallback of closed-loop launches that hold a plan (closed_loop.PlanHold lowers to it)."""
+    _fields_ = [('replan_every', C.c_int32), ('on_fail', C.c_int32), ('fail_mask', C.c_uint32), ('reserved', C.c_int32)]
+
+
+HOLD_REFERENCE, HOLD_HOLD = 0, 1                        # DGSQP_HOLD_*
+
+
 class StatRecordT(C.Structure):
     _fields_ = [('status', C.c_int32), ('iters', C.c_int32), ('qp_solves', C.c_int32), ('rank', C.c_int32),
                 ('p_feas', C.c_double), ('comp', C.c_double), ('stat', C.c_double), ('cost', C.c_double * MAX_AGENTS)]
@@ -142,6 +152,8 @@ SIGNATURES = {
     'dgsqp_fetch_monitor': (C.c_int, [_H, _PD, _PD, _PI]),
     'dgsqp_set_drivers': (C.c_int, [_H, C.POINTER(DriversT), C.c_int32, C.c_int64, _PI, _PD, _PD]),
     'dgsqp_fetch_u_cmd': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_set_plan_hold': (C.c_int, [_H, C.POINTER(HoldT)]),
+    'dgsqp_fetch_plan_hold': (C.c_int, [_H, _PD, _PI, C.c_int64]),
     'dgsqp_set_u_prev': (C.c_int, [_H, C.c_int64, _PD]),
     'dgsqp_set_closed_loop_u_prev': (C.c_int, [_H, C.c_int, C.c_int64, _PD]),
     'dgsqp_fetch_u_prev': (C.c_int, [_H, _PD, C.c_int64]),

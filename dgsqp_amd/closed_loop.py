@@ -20,7 +20,10 @@ A launch with a plant may also choose, per agent and per chain, who produces the
 ``dev_plant_feedback``); the command they return is what ``plant_feedback`` takes as ``u_new``.
 
 A launch may carry the command of step t into solve t + 1 as the input before its stage 0 (``step_batch(..., u_prev=True)``,
-``dgsqp_set_closed_loop_u_prev``): ``next_u_prev`` is the mirror of that rule."""
+``dgsqp_set_closed_loop_u_prev``): ``next_u_prev`` is the mirror of that rule.
+
+A launch with a plant may hold a plan across control steps (``PlanHold``, ``dgsqp_set_plan_hold``): a planning rate below the control
+rate, and the next stage of the last accepted plan as the command after a failed solve.  ``hold_step`` is the mirror of that rule."""
 from __future__ import annotations
 
 import ctypes as C
@@ -436,6 +439,83 @@ def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None)
                 raise ValueError("a 'replay' driver needs u_replay")
             u_cmd[NUA * a:NUA * a + NUA] = np.asarray(u_replay, dtype=np.float64)[NUA * a:NUA * a + NUA]
     return u_cmd, states
+
+
+REFERENCE_FAIL_MASK = (1 << DIVERGED) | (1 << QP_FAIL)      # the statuses after which step() keeps its warm start (DGSQP.py:293-295)
+CONVERGED_FAIL_MASK = 0b111100                              # every status but the two converged ones: 2 .. 5
+ON_FAIL = {'reference': _ffi.HOLD_REFERENCE, 'hold': _ffi.HOLD_HOLD}
+
+
+@dataclass
+class PlanHold:
+    """Holding a plan across control steps in ``DGSQP.step_batch(..., hold=...)`` (``dgsqp_set_plan_hold``): a chain holds a plan -- its
+    warm start -- and consumes it stage by stage until a newer one is accepted.
+
+    * ``replan_every`` R, 1 .. N: a chain solves, and once a solve is accepted follows that plan for R control steps before the next;
+    * ``on_fail``: what a chain applies after a failed solve -- 'reference': stage 0 of the failed iterate, keeping the warm start
+      unshifted (``DGSQP.step()``, the default); 'hold': the next stage of the plan it holds, and the solve is retried at the next step;
+    * ``accept``: which solves count as failed -- 'reference': 'diverged' and 'qp_fail'; 'converged': every status but the two converged
+      ones; or a mask with bit s set when status s (0 .. 5) is a failure.
+
+    The rule of one step is ``hold_step``.  The defaults are, bit for bit, the launch without ``hold``."""
+    replan_every: int = 1
+    on_fail: str = 'reference'
+    accept: object = 'reference'
+
+    def __post_init__(self):
+        if isinstance(self.replan_every, bool) or int(self.replan_every) != self.replan_every or self.replan_every < 1:
+            raise ValueError(f'replan_every must be a whole number >= 1, got {self.replan_every!r}')
+        if self.on_fail not in ON_FAIL:
+            raise ValueError(f"on_fail {self.on_fail!r} not recognized: 'reference' or 'hold'")
+        self.mask           # (validates accept)
+
+    @property
+    def mask(self) -> int:
+        """The fail mask: bit s set when status s counts as a failed solve."""
+        if isinstance(self.accept, str):
+            if self.accept not in ('reference', 'converged'):
+                raise ValueError(f"accept {self.accept!r} not recognized: 'reference', 'converged' or a mask of the statuses 0 .. 5")
+            return REFERENCE_FAIL_MASK if self.accept == 'reference' else CONVERGED_FAIL_MASK
+        if isinstance(self.accept, bool) or int(self.accept) != self.accept or not 0 <= int(self.accept) < 64:
+            raise ValueError(f'accept as a mask holds bits 0 .. 5 (one per status), got {self.accept!r}')
+        return int(self.accept)
+
+    def lower(self, problem: _ffi.ProblemT) -> _ffi.HoldT:
+        """``dgsqp_hold_t`` for the game ``problem`` (host only); ``ValueError`` for what the library would refuse."""
+        if int(self.replan_every) > int(problem.N):
+            raise ValueError(f'replan_every must be 1 .. N = {int(problem.N)}, got {self.replan_every}')
+        ht = _ffi.HoldT()
+        ht.replan_every, ht.on_fail, ht.fail_mask, ht.reserved = int(self.replan_every), ON_FAIL[self.on_fail], self.mask, 0
+        return ht
+
+
+def hold_step(status, u_t, u_ws_t, age: int, due: bool, hold: PlanHold, N: int, num_ua_d):
+    """One control step of one chain that holds a plan -- the host mirror of ``dev_hold_due``, the hold overload of ``dev_plant_feedback``
+    and ``dev_hold_next`` (csrc/dgsqp_closed_loop.h; the table in include/dgsqp.h).  ``status``: the exit code of the step's solve, or
+    None on a held step (no solve: exactly when ``due`` is False); ``u_t`` [n] the solve's iterate (agent-major; not read on a held step,
+    may be None), ``u_ws_t`` [n] the warm start the chain holds; ``age``, ``due`` the chain's state before the step (0, True when it
+    starts).  Returns ``(u_game [n_u], u_ws_next [n], age, due, plan_stage)``:
+
+    * due, status not in the mask: stage 0 of ``u_t``; ``shift(u_t)``; age 1, due = (1 >= R); plan_stage 0
+    * due, failed, 'reference':    stage 0 of ``u_t``; ``u_ws_t`` unshifted; age and due unchanged; plan_stage 0
+    * due, failed, 'hold':         stage 0 of ``u_ws_t``; ``shift(u_ws_t)``; age + 1, due stays; plan_stage = age before
+    * not due (held):              stage 0 of ``u_ws_t``; ``shift(u_ws_t)``; age + 1, due = (age >= R); plan_stage = age before
+
+    Pure data movement: device and host agree bit for bit."""
+    if (status is None) == bool(due):
+        raise ValueError('a chain solves exactly when a plan is due: status is None on a held step and only there')
+    R = int(hold.replan_every)
+    u_ws_t = np.asarray(u_ws_t, dtype=np.float64)
+    first = np.cumsum([0] + [N * int(nu) for nu in num_ua_d])       # where each agent's rows start
+    stage0 = lambda u: np.concatenate([u[first[a]:first[a] + int(nu)] for a, nu in enumerate(num_ua_d)])
+    failed = status is not None and 0 <= int(status) <= 5 and bool((hold.mask >> int(status)) & 1)
+    if status is not None and not failed:
+        u_t = np.asarray(u_t, dtype=np.float64)
+        return stage0(u_t), shift_warm_start(u_t, N, num_ua_d), 1, 1 >= R, 0
+    if failed and hold.on_fail == 'reference':
+        return stage0(np.asarray(u_t, dtype=np.float64)), u_ws_t.copy(), int(age), bool(due), 0
+    new_age = int(age) + 1
+    return stage0(u_ws_t), shift_warm_start(u_ws_t, N, num_ua_d), new_age, bool(due) if failed else new_age >= R, int(age)
 
 
 def next_u_prev(u_t_stage0, u_cmd=None) -> np.ndarray:

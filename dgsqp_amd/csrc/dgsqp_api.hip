@@ -269,7 +269,7 @@ struct DgLog {
 };
 
 // The settings of closed-loop launches (dgsqp_set_plant and, on top of a plant, dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise,
-// dgsqp_set_monitor, dgsqp_set_drivers).  Every device buffer they need is one entry of DgSide, stated once here: what a setter uploads,
+// dgsqp_set_monitor, dgsqp_set_drivers, dgsqp_set_plan_hold).  Every device buffer they need is one entry of DgSide, stated once here: what a setter uploads,
 // what a launch sizes per workgroup, and the records a launch leaves behind for a dgsqp_fetch_*.  Every buffer grows exactly to what is
 // asked of it and never shrinks.
 enum DgSideBuf {
@@ -279,6 +279,7 @@ enum DgSideBuf {
   SB_MON_SCRATCH, SB_CLEARANCE, SB_BOX_EXCESS, SB_HIT_STEP,   // the monitor: [grid][S][M][3]; clearance and box_excess [T][B], hit_step [B] int32
   SB_KIND, SB_PID, SB_REF, SB_U_REPLAY,                       // the drivers: [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
   SB_U_CMD, SB_CMD, SB_PID_STATE,                             // ... u_cmd [T][B][nu]; per workgroup: [grid][n] (2 M used: read as u_t is), [grid][M][3]
+  SB_U_GAME, SB_PLAN_STAGE, SB_GCMD, SB_HOLD_STATE,           // the held plan: u_game [T][B][nu], plan_stage [T][B] int32; per workgroup: [grid][n] as SB_CMD, [grid][2] int32
   SB_U_PREV,                                                  // the carried input (dgsqp_set_closed_loop_u_prev): u_prev [T][B][nu]
   DG_SIDE_COUNT
 };
@@ -291,7 +292,7 @@ struct DgSide {
   int64_t left[DG_SIDE_COUNT] = {};   // a record: elements the last launch that filled it left behind (0: none yet)
   template <class T> T* at(int i) const { return (T*)b[i].p; }
 };
-// what is set, and for which launch shape: the plant; the further settings on top of it; the drivers
+// what is set, and for which launch shape: the plant; the further settings on top of it; the drivers; the held plan
 struct DgPlantState {
   bool set = false;
   dgsqp_plant_t host;                 // resolved: agents[] hold the game's records when the plant uses the game's parameters
@@ -309,6 +310,10 @@ struct DgDriversState {
   int32_t T = 0;                      // the launch shape the arrays were given for
   int64_t B = 0;
   bool has_ref = false, has_replay = false;
+};
+struct DgHoldState {
+  bool set = false;
+  dgsqp_hold_t host;
 };
 
 // u_{-1}, the input applied before stage 0 (Ctx.up).  dgsqp_set_u_prev keeps a host copy; staging a batch captures it in a device buffer of
@@ -349,6 +354,7 @@ struct dgsqp_solver {
   DgPlantState plant;                      // closed-loop settings ...
   DgEnsembleState ens;
   DgDriversState drv;
+  DgHoldState hold;
   DgSide side;                             // ... and their device buffers
   DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
@@ -764,6 +770,9 @@ static int drivers_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
     return refuse(h, "drivers: ", "launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the drivers were set for T = " + std::to_string(R.T) + ", B = " + std::to_string(R.B));
   return DGSQP_OK;
 }
+static int hold_check_launch(dgsqp_solver* h) {
+  return !h->hold.set || h->plant.set ? DGSQP_OK : refuse(h, "plan hold: ", "no plant set for this launch");
+}
 static int further_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
   const DgEnsembleState& E = h->ens;
   if (E.B > 0 && E.B != B) return refuse(h, "plant ensemble: ", "launch of B = " + std::to_string(B) + " chains, the ensemble holds " + std::to_string(E.B));
@@ -809,11 +818,20 @@ static int further_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, c
   *out = ex;
   return DGSQP_OK;
 }
-// the drivers, on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes before it reads them) and the u_cmd record
-static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgEnsembleDev& ex, DgPlantDriversDev* out) {
-  const DgDriversState& R = h->drv;
+// the drivers, on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes before it reads them) and the u_cmd record.
+// A launch that holds a plan and has no drivers of the caller's runs with every agent of every chain on DGSQP_DRIVER_GAME: the kinds
+// are built here (all-GAME is the launch without drivers, bit for bit); gains, references and replay are never read then.
+static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, const DgEnsembleDev& ex, DgPlantDriversDev* out) {
+  DgDriversState& R = h->drv;
   DgSide& S = h->side;
   S.left[SB_U_CMD] = 0;
+  if (!R.set) {
+    static_assert(DGSQP_DRIVER_GAME == 0, "all-GAME kinds are a buffer of zero bytes");
+    R.has_ref = R.has_replay = false;
+    { const int rc = side_reserve(h, SB_KIND, sizeof(int32_t) * (size_t)B * h->hp.M); if (rc) return rc; }
+    { const int rc = side_reserve(h, SB_PID, sizeof(dgsqp_pid_t) * DGSQP_MAX_AGENTS); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(S.b[SB_KIND].p, 0, sizeof(int32_t) * (size_t)B * h->hp.M, h->stream));
+  }
   { const int rc = side_reserve(h, SB_CMD, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }
   { const int rc = side_reserve(h, SB_PID_STATE, sizeof(double) * (size_t)grid * h->hp.M * 3); if (rc) return rc; }
   { const int rc = side_record(h, SB_U_CMD, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
@@ -823,6 +841,22 @@ static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgEns
   dd.ref = R.has_ref ? S.at<const double>(SB_REF) : nullptr; dd.u_replay = R.has_replay ? S.at<const double>(SB_U_REPLAY) : nullptr;
   dd.u_cmd = S.at<double>(SB_U_CMD); dd.cmd = S.at<double>(SB_CMD); dd.pid_state = S.at<double>(SB_PID_STATE);
   *out = dd;
+  return DGSQP_OK;
+}
+// the held plan, on top of `dd`: the per-workgroup command and (age, due) buffers (the kernel writes before it reads them) and the u_game
+// and plan_stage records
+static int hold_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgPlantDriversDev& dd, DgPlantDriversHoldDev* out) {
+  DgSide& S = h->side;
+  S.left[SB_U_GAME] = S.left[SB_PLAN_STAGE] = 0;      // one record in two arrays: none of it while either can fail
+  { const int rc = side_reserve(h, SB_GCMD, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }
+  { const int rc = side_reserve(h, SB_HOLD_STATE, sizeof(int32_t) * (size_t)grid * 2); if (rc) return rc; }
+  { const int rc = side_record(h, SB_U_GAME, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
+  { const int rc = side_record(h, SB_PLAN_STAGE, TB, sizeof(int32_t)); if (rc) return rc; }
+  DgPlantDriversHoldDev hd{};
+  hd.dd = dd;
+  hd.replan_every = h->hold.host.replan_every; hd.on_fail = h->hold.host.on_fail; hd.fail_mask = h->hold.host.fail_mask;
+  hd.u_game = S.at<double>(SB_U_GAME); hd.plan_stage = S.at<int32_t>(SB_PLAN_STAGE); hd.gcmd = S.at<double>(SB_GCMD); hd.state = S.at<int32_t>(SB_HOLD_STATE);
+  *out = hd;
   return DGSQP_OK;
 }
 // the one launch of dg_closed_loop_kernel, instantiated for the argument pack the settings call for (none: no plant)
@@ -925,7 +959,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
   const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
                            (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>};
+                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>, (const void*)dg_closed_loop_kernel<DgPlantDriversHoldDev>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -1418,9 +1452,30 @@ int dgsqp_fetch_u_cmd(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
   return h ? side_fetch(h, {{SB_U_CMD, out, sizeof(double)}}, none, none, "u_cmd", capacity_doubles) : DGSQP_E_ARG;
 }
 
+int dgsqp_set_plan_hold(dgsqp_handle_t h, const dgsqp_hold_t* hold) {
+  { const int rc = setter_begin(h); if (rc) return rc; }
+  DgHoldState& S = h->hold;
+  if (!hold) { S.set = false; return DGSQP_OK; }
+  auto bad = [&](const std::string& m) { return refuse(h, "plan hold: ", m); };
+  { const int rc = need_plant(h, "plan hold: "); if (rc) return rc; }
+  const int N = h->hp.N;
+  if (hold->replan_every < 1 || hold->replan_every > N) return bad("replan_every must be 1 .. N = " + std::to_string(N) + ", got " + std::to_string(hold->replan_every));
+  if (hold->on_fail != DGSQP_HOLD_REFERENCE && hold->on_fail != DGSQP_HOLD_HOLD)
+    return bad("on_fail must be 0 (reference) or 1 (hold), got " + std::to_string(hold->on_fail));
+  if (hold->fail_mask >> 6) return bad("fail_mask has a bit above 5 set (" + std::to_string(hold->fail_mask) + "): the statuses are 0 .. 5");
+  S.host = *hold;
+  S.set = true;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_plan_hold(dgsqp_handle_t h, double* u_game, int32_t* plan_stage, int64_t capacity_doubles) {
+  if (!h) return DGSQP_E_ARG;
+  return side_fetch(h, {{SB_U_GAME, u_game, sizeof(double)}, {SB_PLAN_STAGE, plan_stage, sizeof(int32_t)}},
+                    "no closed-loop launch with a plan hold has run", "plan hold: null argument", "u_game", capacity_doubles);
+}
+
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
-// DgPlantDev argument when the handle has a plant, a DgEnsembleDev when one of the further settings is on as well, and a DgPlantDriversDev
-// when drivers are set.
+// DgPlantDev argument when the handle has a plant, a DgEnsembleDev when one of the further settings is on as well, a DgPlantDriversDev
+// when drivers are set, and a DgPlantDriversHoldDev when a plan is held.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1432,9 +1487,10 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
   }
-  const bool further = h->ens.any(), drivers = h->drv.set;
+  const bool further = h->ens.any(), hold = h->hold.set, drivers = h->drv.set || hold;
   { const int rc = further_check_plant(h); if (rc) return rc; }
   { const int rc = drivers_check_launch(h, T, B); if (rc) return rc; }
+  { const int rc = hold_check_launch(h); if (rc) return rc; }
   { const int rc = further_check_launch(h, T, B); if (rc) return rc; }
   const DgUPrevState& U = h->up;
   if (U.cl_mode && U.cl_B > 0 && U.cl_B != B)
@@ -1479,13 +1535,16 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
   DgPlantDriversDev dd{};
   if (further || drivers) { const int rc = further_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
-  if (drivers) { const int rc = drivers_for_launch(h, grid, TB, ex, &dd); if (rc) return rc; }
+  if (drivers) { const int rc = drivers_for_launch(h, grid, B, TB, ex, &dd); if (rc) return rc; }
+  DgPlantDriversHoldDev hd{};
+  if (hold) { const int rc = hold_for_launch(h, grid, TB, dd, &hd); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (drivers) launch_closed_loop(h, grid, B, cl, dd);
+    if (hold) launch_closed_loop(h, grid, B, cl, hd);
+    else if (drivers) launch_closed_loop(h, grid, B, cl, dd);
     else if (further) launch_closed_loop(h, grid, B, cl, ex);
     else if (h->plant.set) launch_closed_loop(h, grid, B, cl, pd);
     else launch_closed_loop(h, grid, B, cl);

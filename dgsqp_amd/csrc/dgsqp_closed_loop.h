@@ -63,6 +63,27 @@ struct DgPlantDriversDev {
   double* pid_state;                  // [grid][M][3] ei, previous u_a, previous u_steer: cleared when a chain starts
 };
 
+// A held plan (dgsqp_set_plan_hold; the table in include/dgsqp.h): a chain solves only when a plan is due and otherwise consumes the warm
+// start it holds, stage by stage.  The pack of the fifth instantiation of dg_closed_loop_kernel; it wraps DgPlantDriversDev (a launch
+// without drivers of the caller's runs with all-GAME kinds, which the host layer builds), so every other setting combines with it.  The
+// game's command goes to u_game[t][b] and to the workgroup's gcmd, where the drivers' feedback reads stage 0 of u_t; gcmd is written and
+// read by the same lane, like cmd.  state holds the chain's (age, due): written by lane 0, read by every lane after a fence and a barrier.
+// The NAME (see DgPlantDriversDev): the namespace makes this instantiation sort behind ALL the others in the mangled kernel names -- a
+// nested name mangles as N...E, and 'N' follows every digit and the 'E' that closes the empty pack of dg_closed_loop_kernel<> -- so every
+// one of them keeps its LDS kernel id.
+namespace dg_hold {
+struct DgPlantDriversHoldDev {
+  DgPlantDriversDev dd;
+  int32_t replan_every, on_fail;      // R; DGSQP_HOLD_*
+  uint32_t fail_mask;                 // bit s: status s is a failed solve
+  double* u_game;                     // [T][B][nu] the game's command: stage 0 of the step's solution, or of the plan it holds
+  int32_t* plan_stage;                // [T][B] how many stages of its plan the chain had consumed before u_game[t][b]
+  double* gcmd;                       // [grid][n] (2 M used: read as u_t is)
+  int32_t* state;                     // [grid][2] age, due: set to (0, 1) when a chain starts
+};
+}
+using dg_hold::DgPlantDriversHoldDev;
+
 // Agent a's monitor record of one simulation step, from its state block z: the position and the largest excess over the GAME's bounds
 // (-inf: no finite bound; NaN: an entry of z is not finite).  One lane, no cross-lane operation.
 __device__ inline void dev_monitor_store(const dgsqp_agent_t& game, int nqa, const double* z, double* rec) {
@@ -298,6 +319,68 @@ __device__ __noinline__ int dev_plant_feedback(DgPlantDriversDev dd, int t, int6
   return dev_plant_feedback(dd.ex, t, tb_b, q_t, cmd, w_t, q_next);
 }
 
+// A held plan: which row of the table (include/dgsqp.h) step t falls under, from whether it solved and the solve's status.
+enum { DG_HOLD_ACCEPT = 0, DG_HOLD_KEEP = 1, DG_HOLD_CONSUME = 2 };
+__device__ inline int dev_hold_rule(const DgPlantDriversHoldDev& hd, int solved, int status) {
+  if (!solved) return DG_HOLD_CONSUME;
+  if (status < 0 || status > 5 || !((hd.fail_mask >> status) & 1u)) return DG_HOLD_ACCEPT;
+  return hd.on_fail == DGSQP_HOLD_HOLD ? DG_HOLD_CONSUME : DG_HOLD_KEEP;
+}
+
+// Whether step t of the workgroup's chain solves.  (age, due) is reset where the delay lines and the PID state are (t == 0); afterwards it
+// is what dev_hold_next left, behind the fence and barrier that end a step.  The same value on every lane: the branch on it is uniform.
+__device__ __noinline__ int dev_hold_due(DgPlantDriversHoldDev hd, int t) {
+  int32_t* st = hd.state + (int64_t)blockIdx.x * 2;
+  if (t == 0) {
+    if (TID == 0) { st[0] = 0; st[1] = 1; }
+    __threadfence_block();
+    __syncthreads();
+  }
+  return __builtin_amdgcn_readfirstlane(st[1]);
+}
+
+// The feedback with a held plan: lane a < M stores the game's command for its agent -- stage 0 of the solution u_t, or of the warm start
+// uws_t the chain holds -- to u_game[t][b] and to the workgroup's gcmd, lane 0 plan_stage; gcmd is then handed to the drivers' feedback in
+// place of u_t.  uws_t was written one step ago behind a fence and a barrier (or by the host), age by this very lane.
+__device__ __noinline__ int dev_plant_feedback(DgPlantDriversHoldDev hd, int solved, int status, const double* uws_t, int t, int64_t tb_b,
+                                               const double* q_t, const double* u_t, const double* w_t, double* q_next) {
+  const DgProb& D = dg_prob;
+  const int a = TID;
+  double* g = hd.gcmd + (int64_t)blockIdx.x * D.n;
+  if (a < D.M) {
+    const int rule = dev_hold_rule(hd, solved, status);
+    const double* src = rule == DG_HOLD_CONSUME ? uws_t : u_t;
+    for (int j = 0; j < DGSQP_NUA; j++) {
+      const double v = src[am_col(D, a, 0, j)];
+      hd.u_game[tb_b * D.nu + a * DGSQP_NUA + j] = v;
+      g[am_col(D, a, 0, j)] = v;
+    }
+    if (a == 0) hd.plan_stage[tb_b] = rule == DG_HOLD_CONSUME ? hd.state[(int64_t)blockIdx.x * 2] : 0;
+  }
+  return dev_plant_feedback(hd.dd, t, tb_b, q_t, g, w_t, q_next);
+}
+
+// The next warm start with a held plan and the chain's (age, due) after the step; every lane of the workgroup calls it, after the barrier
+// that decided that the chain goes on (so every lane has read `due` of this step).
+__device__ __noinline__ void dev_hold_next(DgPlantDriversHoldDev hd, int solved, int status, const double* uws_t, const double* u_t, double* uws_next) {
+  const int n = dg_prob.n, N = dg_prob.N;
+  const int rule = dev_hold_rule(hd, solved, status);
+  const double* src = rule == DG_HOLD_ACCEPT ? u_t : uws_t;
+  for (int i = TID; i < n; i += NT) {
+    const int k = (i % (N * DGSQP_NUA)) / DGSQP_NUA;
+    uws_next[i] = rule == DG_HOLD_KEEP ? uws_t[i] : src[k + 1 < N ? i + DGSQP_NUA : i];
+  }
+  if (TID == 0) {
+    int32_t* st = hd.state + (int64_t)blockIdx.x * 2;
+    if (rule == DG_HOLD_ACCEPT) { st[0] = 1; st[1] = 1 >= hd.replan_every; }
+    else if (rule == DG_HOLD_CONSUME) {
+      const int age = st[0] + 1;
+      st[0] = age;
+      if (!solved) st[1] = age >= hd.replan_every;
+    }
+  }
+}
+
 // The state solve t of chain b starts from.  With estimates: the lanes write q_est[t][b] = q[t][b] + v[t][b], and the slice is handed to
 // the solve through memory (fence + barrier) like every other state; returns non-zero when it is not finite (the chain ends before
 // the solve).  Out of line, as the feedback.
@@ -320,6 +403,9 @@ __device__ __noinline__ int dev_estimate(DgEnsembleDev ex, int64_t tb_b, const d
 __device__ __noinline__ int dev_estimate(DgPlantDriversDev dd, int64_t tb_b, const double* q_t, const double** x0) {
   return dev_estimate(dd.ex, tb_b, q_t, x0);
 }
+__device__ __noinline__ int dev_estimate(DgPlantDriversHoldDev hd, int64_t tb_b, const double* q_t, const double** x0) {
+  return dev_estimate(hd.dd.ex, tb_b, q_t, x0);
+}
 
 // Per ticket b, for t = 0 .. T-1: solve from (q[t][b], uws[t][b]) exactly as dg_solve_kernel would, then
 //   q[t+1][b]   = x_t[b][1] (+ w[t][b])                          the game's own discrete model is the plant
@@ -332,19 +418,26 @@ __device__ __noinline__ int dev_estimate(DgPlantDriversDev dd, int64_t tb_b, con
 // (status DGSQP_NOT_RUN, zero counts, NaN).
 // No cooperative line search, no deferral, no event or iterate log: a chain's next solve depends on its last one.
 // A non-finite q_est[t][b] (DgEnsembleDev with estimates) ends the chain BEFORE solve t: steps_done[b] = t.
-// PLANT is empty, one DgPlantDev, one DgEnsembleDev, or one DgPlantDriversDev: the instantiation without a plant has the argument list it always
-// had and holds nothing of the plant, the one with a DgPlantDev nothing of the further settings, the one with a DgEnsembleDev nothing of
-// the drivers.
+// PLANT is empty, one DgPlantDev, one DgEnsembleDev, one DgPlantDriversDev, or one DgPlantDriversHoldDev: the instantiation without a plant has
+// the argument list it always had and holds nothing of the plant, the one with a DgPlantDev nothing of the further settings, the one with a
+// DgEnsembleDev nothing of the drivers, the one with a DgPlantDriversDev nothing of the held plan.
+// With a HELD PLAN (DgPlantDriversHoldDev; the table in include/dgsqp.h) step t solves only when a plan is due (dev_hold_due); a held step
+// writes status DGSQP_HELD and zero counts, forms no estimate, and feeds stage 0 of the warm start it holds to the plant; the next warm
+// start is dev_hold_next's.
 // Channel j of the command that entered agent a's plant at the step whose records start tb_b scenarios in: stage 0 of the solution u_t,
 // or with drivers what dev_plant_feedback stored in u_cmd.
 __device__ inline double dev_command(int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
 __device__ inline double dev_command(const DgPlantDev&, int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
 __device__ inline double dev_command(const DgEnsembleDev&, int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
 __device__ inline double dev_command(const DgPlantDriversDev& dd, int64_t tb_b, int a, int j, const double*) { return dd.u_cmd[tb_b * dg_prob.nu + a * DGSQP_NUA + j]; }
+__device__ inline double dev_command(const DgPlantDriversHoldDev& hd, int64_t tb_b, int a, int j, const double*) { return hd.dd.u_cmd[tb_b * dg_prob.nu + a * DGSQP_NUA + j]; }
 
 template <class... PLANT> struct DgHasEstimates { static constexpr bool value = false; };
 template <> struct DgHasEstimates<DgEnsembleDev> { static constexpr bool value = true; };
 template <> struct DgHasEstimates<DgPlantDriversDev> { static constexpr bool value = true; };
+template <> struct DgHasEstimates<DgPlantDriversHoldDev> { static constexpr bool value = true; };
+template <class... PLANT> struct DgHoldsPlan { static constexpr bool value = false; };
+template <> struct DgHoldsPlan<DgPlantDriversHoldDev> { static constexpr bool value = true; };
 template <class... PLANT>
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket, PLANT... pd) {
@@ -372,6 +465,22 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
       SolveOutPtrs O = cl.O;
       O.u += tb * n; if (O.l) O.l += tb * nc; O.x += (int64_t)t * cl.x_step; O.cond += tb * 3; O.cost += tb * dg_prob.M;
       O.status += tb; O.iters += tb; O.qp_solves += tb;
+      if constexpr (DgHoldsPlan<PLANT...>::value)
+        if (!dev_hold_due(pd..., t)) {
+          // a HELD step: no estimate and no solve; the plan the chain holds feeds the plant, and the step ends as every step does below
+          if (TID == 0) { O.status[b] = DGSQP_HELD; O.iters[b] = 0; O.qp_solves[b] = 0; }
+          int bad = dev_plant_feedback(pd..., 0, DGSQP_HELD, uws_t, t, tb + b, cl.q + (tb + b) * nq, uws_t, cl.w ? cl.w + (tb + b) * nq : nullptr,
+                                       cl.q + (tb + B + b) * nq);
+          t++;
+          if (__syncthreads_or(bad)) break;
+          dev_hold_next(pd..., 0, DGSQP_HELD, uws_t, uws_t, cl.uws + (tb + B + b) * n);
+          if (cl.up && t < cl.T && TID < dg_prob.M)
+            for (int j = 0; j < DGSQP_NUA; j++)
+              cl.up[(tb + B + b) * dg_prob.nu + TID * DGSQP_NUA + j] = dev_command(pd..., tb + b, TID, j, uws_t);
+          __threadfence_block();
+          __syncthreads();
+          continue;
+        }
       if constexpr (DgHasEstimates<PLANT...>::value) {
         const double* x0 = nullptr;
         if (dev_estimate(pd..., tb + b, cl.q + (tb + b) * nq, &x0)) break;
@@ -392,7 +501,8 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
       double* q_next = cl.q + (tb + B + b) * nq;
       double* uws_next = cl.uws + (tb + B + b) * n;
       int bad = 0;
-      if constexpr (sizeof...(PLANT) != 0) bad = dev_plant_feedback(pd..., t, tb + b, cl.q + (tb + b) * nq, u_t, w_t, q_next);
+      if constexpr (DgHoldsPlan<PLANT...>::value) bad = dev_plant_feedback(pd..., 1, status, uws_t, t, tb + b, cl.q + (tb + b) * nq, u_t, w_t, q_next);
+      else if constexpr (sizeof...(PLANT) != 0) bad = dev_plant_feedback(pd..., t, tb + b, cl.q + (tb + b) * nq, u_t, w_t, q_next);
       else
         for (int i = TID; i < nq; i += NT) {
           double v = x1[i];
@@ -402,10 +512,12 @@ dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, u
         }
       t++;
       if (__syncthreads_or(bad)) break;                     // the chain ends: q[t] shows why, its warm start is never written
-      for (int i = TID; i < n; i += NT) {
-        const int k = (i % (N * DGSQP_NUA)) / DGSQP_NUA;    // agent-major: agent a holds rows k = 0 .. N-1 of DGSQP_NUA inputs
-        uws_next[i] = keep ? uws_t[i] : u_t[k + 1 < N ? i + DGSQP_NUA : i];
-      }
+      if constexpr (DgHoldsPlan<PLANT...>::value) dev_hold_next(pd..., 1, status, uws_t, u_t, uws_next);
+      else
+        for (int i = TID; i < n; i += NT) {
+          const int k = (i % (N * DGSQP_NUA)) / DGSQP_NUA;    // agent-major: agent a holds rows k = 0 .. N-1 of DGSQP_NUA inputs
+          uws_next[i] = keep ? uws_t[i] : u_t[k + 1 < N ? i + DGSQP_NUA : i];
+        }
       // carry: the command that entered each agent's plant at this step is the next solve's u_{-1} -- stage 0 of u_t as returned (also after
       // 'diverged' / 'qp_fail': the feedback applied it), or with drivers u_cmd[t][b], read back by the lane that stored it.  With delay
       // lines it is the value appended to the line, not the delayed one the plant integrated under.

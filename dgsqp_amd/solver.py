@@ -314,6 +314,7 @@ class _Setting(NamedTuple):
     steps: dict = {}
     chains: tuple = ()
     sized: bool = True
+    steps_i32: tuple = ()
 
 
 def solve_batches(solvers, batches) -> list:
@@ -520,7 +521,7 @@ class DGSQP(AbstractSolver):
 
     def _finish(self, out: dict, t0: float, tm: _ffi.TimingT) -> dict:
         """What every result dictionary ends with, from its ``status`` [B] or [B, T] and ``u``."""
-        name = lambda s: 'not_run' if s == _ffi.NOT_RUN else _ffi.STATUS_MSG[s]
+        name = lambda s: _ffi.STATUS_NAMES[int(s)]
         st = out['status']
         out['time'] = time.time() - t0
         out['kernel_ms'] = tm.kernel_ms
@@ -553,7 +554,7 @@ class DGSQP(AbstractSolver):
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
                    keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False, drivers=None,
-                   u_prev=None) -> dict:
+                   u_prev=None, hold=None) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -588,12 +589,27 @@ class DGSQP(AbstractSolver):
         command ACROSS control steps.  ``None``: every solve is measured against zeros, the reference's ``solve()``.  The result gains u_prev
         [B, T, n_u], what each solve ran with (NaN after a chain's end).
 
+        ``hold`` (``closed_loop.PlanHold``; with ``plant=None`` the identity plant ``PlantModel()`` is used), for this call only: a chain holds
+        a plan -- its warm start -- and consumes it stage by stage until a newer one is accepted (``dgsqp_set_plan_hold``; host mirror
+        ``closed_loop.hold_step``).  ``replan_every=R``: after an accepted solve the chain follows that plan for R control steps and solves
+        again at the R-th; the steps in between run no solve and report status -2 / 'held', zero counts and NaN (``converged`` False), and
+        with ``estimate_noise`` form no estimate (q_est stays NaN there).  ``on_fail='hold'``: after a failed solve (``accept``: which
+        statuses fail) the chain applies the next stage of the plan it holds instead of stage 0 of the failed iterate, and retries at the
+        next step.  Drivers, delay lines, monitor and the ``u_prev`` carry see the game's command in place of stage 0 of the solution.  The
+        result gains u_game [B, T, n_u], the game's command (NaN where a step never ran), and plan_stage [B, T], how many stages of its plan
+        the chain had consumed before it (0 on an accepted solve, -1 where a step never ran); u_applied is u_game.  The defaults
+        ``PlanHold()`` give, bit for bit, the launch without ``hold``.
+
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
         steps_done [B], time, kernel_ms; with ``keep_predictions`` also x [B, T, N+1, n_q] and l [B, T, n_c]."""
         T = int(steps)
         if T < 1:
             raise ValueError(f'steps must be at least 1, got {steps}')
+        if hold is not None:
+            from .closed_loop import PlanHold
+            if not isinstance(hold, PlanHold):
+                raise TypeError(f'hold must be a closed_loop.PlanHold, got {type(hold).__name__}')
         x0, u_ws = self._inputs(x0, u_ws)
         B = x0.shape[0]
         w = None
@@ -606,14 +622,14 @@ class DGSQP(AbstractSolver):
         steps_done = np.empty(B, np.int32)
         tm = _ffi.TimingT()
         dptr, iptr = _ffi.dptr, _ffi.iptr
-        if drivers is not None and plant is None:
+        if (drivers is not None or hold is not None) and plant is None:
             from .closed_loop import PlantModel
             plant = PlantModel()
         if monitor not in (False, None, True, 'stop'):
             raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
         if plant is None and (estimate_noise is not None or monitor):
             raise ValueError('estimate_noise and monitor need a plant (PlantModel() is the identity plant)')
-        noise = pt = ensemble = drv = up0 = None
+        noise = pt = ensemble = drv = up0 = ht = None
         carry = u_prev is not None and u_prev is not False
         if carry and u_prev is not True:
             up0 = coerce_u_prev(u_prev, B, self.n_u)
@@ -627,19 +643,23 @@ class DGSQP(AbstractSolver):
             ensemble = plant.lower_ensemble(self._problem, B) if plant.per_chain else None
         if drivers is not None:
             drv = drivers.lower(self._problem, B, T)
+        if hold is not None:
+            ht = hold.lower(self._problem)
         # Every setting once, in the order they are set: dgsqp_set_<name>(*on) when it is asked for and, afterwards, (*off);
         # dgsqp_fetch_<fetch> fills the records it adds to the result -- ``steps`` step-major [T, B, ...] doubles, ``chains`` [B] int32 --
-        # and takes their size when ``sized``.
+        # and takes their size when ``sized``; ``steps_i32`` are further step-major records [T, B] of int32, fetched behind the doubles.
         settings = [_Setting('plant', pt is not None and (C.byref(pt),), (None,), 'u_plant', dict(u_plant=(getattr(pt, 'sim_steps', 0), self.n_u))),
                     _Setting('plant_ensemble', ensemble is not None and (B, ensemble[0], iptr(ensemble[1])), (0, None, None)),
                     _Setting('estimate_noise', noise is not None and (T, B, dptr(noise)), (0, 0, None), 'q_est', dict(q_est=(self.n_q,))),
                     _Setting('monitor', bool(monitor) and (2 if monitor == 'stop' else 1,), (0,), 'monitor', dict(clearance=(), box_excess=()), ('hit_step',), sized=False),
                     _Setting('drivers', drv is not None and (C.byref(drv[0]), T, B, iptr(drv[1]), dptr(drv[2]), dptr(drv[3])), (None, 0, 0, None, None, None),
                              'u_cmd', dict(u_cmd=(self.n_u,))),
+                    _Setting('plan_hold', ht is not None and (C.byref(ht),), (None,), 'plan_hold', dict(u_game=(self.n_u,)), steps_i32=('plan_stage',)),
                     _Setting('closed_loop_u_prev', carry and (1, B if up0 is not None else 0, dptr(up0)), (0, 0, None), 'u_prev', dict(u_prev=(self.n_u,)))]
         on = [st for st in settings if st.on]
         chains = {k: np.empty(B, np.int32) for st in on for k in st.chains}
         sm.update({k: np.empty((T, B) + tail) for st in on for k, tail in st.steps.items()})
+        sm.update({k: np.empty((T, B), np.int32) for st in on for k in st.steps_i32})
         last_error = lambda: self._lib.dgsqp_last_error(self._h).decode()
         t0 = time.time()
         try:
@@ -652,7 +672,8 @@ class DGSQP(AbstractSolver):
                 raise RuntimeError(f'dgsqp_closed_loop_batch failed ({rc}): ' + last_error())
             for st in on:
                 if st.fetch and B > 0:
-                    into = [dptr(sm[k]) for k in st.steps] + [iptr(chains[k]) for k in st.chains] + [sm[k].size for k in st.steps if st.sized]
+                    into = ([dptr(sm[k]) for k in st.steps] + [iptr(sm[k]) for k in st.steps_i32] + [iptr(chains[k]) for k in st.chains]
+                            + [sm[k].size for k in st.steps if st.sized])
                     if getattr(self._lib, 'dgsqp_fetch_' + st.fetch)(self._h, *into) != 0:
                         raise RuntimeError(f'dgsqp_fetch_{st.fetch} failed: ' + last_error())
         finally:
@@ -662,7 +683,7 @@ class DGSQP(AbstractSolver):
         out = {k: np.ascontiguousarray(np.swapaxes(v, 0, 1)) for k, v in sm.items() if v is not None}
         out.update(chains, steps_done=steps_done)
         self._finish(out, t0, tm)
-        out['u_applied'] = np.ascontiguousarray(out['u_pred'][:, :, 0])
+        out['u_applied'] = out['u_game'] if 'u_game' in out else np.ascontiguousarray(out['u_pred'][:, :, 0])
         return out
 
     def set_trace(self, pairs_per_scenario: int):

@@ -14,9 +14,15 @@ beyond the game's own rate limit.  Without ``--carry-u-prev`` every solve measur
 inside a prediction and not between two of them; with it the command of step t is the next solve's input before stage 0
 (``step_batch(..., u_prev=True)``) and the limit holds along the chain wherever the solve converged.
 
+``--replan-every R`` plans at every R-th control step only and follows the last accepted plan in between, ``--on-fail hold`` applies the next
+stage of that plan after a failed solve ('diverged', 'qp_fail') instead of stage 0 of the failed iterate (``closed_loop.PlanHold``,
+``step_batch(..., hold=...)``).  Two more columns then report the share of the steps that ran which were held (no solve) and which fell back
+on the held plan or, with ``--on-fail reference``, applied a failed iterate.
+
     python examples/closed_loop_robustness.py --batch 1024 --steps 20 --spreads 0 0.05 0.1 0.2
     python examples/closed_loop_robustness.py --opponent pid
     python examples/closed_loop_robustness.py --carry-u-prev
+    python examples/closed_loop_robustness.py --replan-every 3 --on-fail hold
 """
 import argparse
 import copy
@@ -26,7 +32,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-from dgsqp_amd.closed_loop import Drivers, PlantModel, perturbed_configs          # noqa: E402
+from dgsqp_amd.closed_loop import Drivers, PlanHold, PlantModel, perturbed_configs          # noqa: E402
 from dgsqp_amd.montecarlo import kinematic_racing_game                            # noqa: E402
 from dgsqp_amd.solver import DGSQP                                                # noqa: E402
 
@@ -45,6 +51,17 @@ def command_jumps(r, lim):
     return worst, float((jump[ran].max(axis=-1) > 1.0 + 1e-9).mean()) if ran.any() else np.nan
 
 
+def held_and_fallback(r, hold) -> str:
+    """The two columns of a launch with a held plan: of the steps that ran, the share that was held (no solve) and the share whose solve
+    failed -- the chain then applied the next stage of its plan ('hold') or stage 0 of the failed iterate ('reference')."""
+    if hold is None:
+        return ''
+    st = r['status']
+    ran = st != -1
+    failed = (st >= 0) & (((hold.mask >> np.clip(st, 0, 5)) & 1) == 1)
+    return f'   {(st == -2).sum() / max(1, ran.sum()):10.4f}   {failed.sum() / max(1, ran.sum()):14.4f}'
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=1024, help='chains per launch')
@@ -56,6 +73,9 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--opponent', choices=('game', 'pid'), default='game', help="who drives car 2: its part of the game's solution, or the PID lane follower")
     ap.add_argument('--carry-u-prev', action='store_true', help="carry each step's command into the next solve as the input before its stage 0")
+    ap.add_argument('--replan-every', type=int, default=1, help='solve at every R-th control step and follow the accepted plan in between')
+    ap.add_argument('--on-fail', choices=('reference', 'hold'), default='reference',
+                    help="after a failed solve: stage 0 of the failed iterate (the reference's step()), or the next stage of the plan the chain holds")
     args = ap.parse_args()
 
     game = kinematic_racing_game('curve', N=args.N)
@@ -69,17 +89,21 @@ def main():
     lim = np.array([P.dt * P.agents[a].rate_ub[j] for a in range(s.M) for j in range(2)]) if has_rate else None
     print(f'{B} chains x {T} steps, estimate noise {args.noise:g}, plant: rk4, {args.sim_steps} simulation steps per control step, '
           f'u_prev {"carried" if args.carry_u_prev else "zero in every solve"}')
+    hold = PlanHold(replan_every=args.replan_every, on_fail=args.on_fail) if (args.replan_every, args.on_fail) != (1, 'reference') else None
+    if hold is not None:
+        print(f'a plan every {args.replan_every} control step(s), after a failed solve: {args.on_fail}')
     opponents = [('self-play', None)] + ([('pid', Drivers(kinds=['game', 'pid']))] if args.opponent == 'pid' else [])
-    print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]   max jump / (dt rate_ub): u_a, u_steer   steps over the limit')
+    print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]   max jump / (dt rate_ub): u_a, u_steer   steps over the limit'
+          + ('   held steps   fallback steps' if hold is not None else ''))
     for spread in args.spreads:
         ens = perturbed_configs(nominal, dict(mass=spread, drag_coefficient=spread, slip_coefficient=spread), B, args.seed)
         plant = PlantModel(per_chain_configs=ens, method='rk4', M=2, sim_steps=args.sim_steps)
         for name, drivers in opponents:
             r = s.step_batch(smp['x0'], smp['u_ws'], T, plant=plant, estimate_noise=noise, monitor='stop', drivers=drivers,
-                             u_prev=True if args.carry_u_prev else None)
+                             u_prev=True if args.carry_u_prev else None, hold=hold)
             worst, share = command_jumps(r, lim)
             print(f'{spread:6.3f}   {name:9s}   {np.mean(r["hit_step"] >= 0):21.4f}   {np.nanmin(r["clearance"]):13.4f}   {np.nanmean(r["clearance"]):14.4f}   '
-                  f'{np.nanmean(r["box_excess"]):15.4f}   {r["steps_done"].mean():14.2f}   {r["kernel_ms"]:11.1f}   {worst[0]:27.3f}, {worst[1]:7.3f}   {share:20.4f}')
+                  f'{np.nanmean(r["box_excess"]):15.4f}   {r["steps_done"].mean():14.2f}   {r["kernel_ms"]:11.1f}   {worst[0]:27.3f}, {worst[1]:7.3f}   {share:20.4f}' + held_and_fallback(r, hold))
 
 
 if __name__ == '__main__':

@@ -477,6 +477,49 @@ int dgsqp_set_closed_loop_u_prev(dgsqp_handle_t h, int mode /* 0 off, 1 carry */
 int dgsqp_fetch_u_prev(dgsqp_handle_t h, double* out /* [T][B][n_u] */, int64_t capacity_doubles);
 
 /*
+ * Holding a plan across control steps (closed-loop launches WITH A PLANT SET): a planning rate below the control rate, and a defined
+ * command when a solve fails (the reference's closed-loop script solves once and follows that solution for many control steps:
+ * scripts/race/race_main.py:495-578).  A chain holds a plan and consumes it stage by stage until a newer one is accepted.  The held plan
+ * is the warm-start chain itself: stage 0 of u_ws[t][b] is the next unconsumed stage of the last accepted plan, one more shift consumes it.
+ *
+ * replan_every = R (1 <= R <= N), on_fail (DGSQP_HOLD_REFERENCE, DGSQP_HOLD_HOLD) and fail_mask: bit s set when status s counts as a
+ * failed solve (bits 0 .. 5 only; the reference's list is (1 << DGSQP_DIVERGED) | (1 << DGSQP_QP_FAIL)).  Per chain: age (int) and due
+ * (bool), age = 0 and due = true at t = 0.  Step t, with ws = u_ws[t][b] and u_t the solve's iterate:
+ *
+ *   case                                  u_game[t][b]   u_ws[t+1][b]     age, due after                  records of step t
+ *   due, status not in fail_mask          stage 0 of u_t shift(u_t)       age = 1, due = (1 >= R)         the solve's; plan_stage = 0
+ *   due, failed, DGSQP_HOLD_REFERENCE     stage 0 of u_t ws (unshifted)   unchanged (due stays)           the solve's; plan_stage = 0
+ *   due, failed, DGSQP_HOLD_HOLD          stage 0 of ws  shift(ws)        age += 1 (due stays)            the solve's; plan_stage = age before
+ *   not due (held step, no solve)         stage 0 of ws  shift(ws)        age += 1, due = (age >= R)      status DGSQP_HELD, iters = qp_solves = 0,
+ *                                                                                                         every double NaN; plan_stage = age before
+ *
+ * shift is the per-agent shift with the last row repeated, so a plan older than N stages repeats its last row.  u_game takes the place of
+ * stage 0 of u_t in everything downstream, which is unchanged: drivers (a GAME agent receives u_game; PID and REPLAY agents are
+ * untouched), delay lines, simulation steps, u_plant, monitor, disturbance, the end-of-chain rules and the u_prev carry (u_prev takes
+ * the command that entered the plant).  With estimates q_est[t][b] is formed and checked only on steps that solve: on a held step the
+ * noise is not read, q_est[t][b] stays NaN and a non-finite entry there does not end the chain.  Steps that never ran keep
+ * DGSQP_NOT_RUN and plan_stage = -1.  R = 1 with DGSQP_HOLD_REFERENCE and the reference's mask is, record for record and bit for bit,
+ * the launch without the setting.
+ */
+#define DGSQP_HELD (-2)
+#define DGSQP_HOLD_REFERENCE 0
+#define DGSQP_HOLD_HOLD 1
+typedef struct {
+  int32_t replan_every;   /* R: 1 .. N */
+  int32_t on_fail;        /* DGSQP_HOLD_* */
+  uint32_t fail_mask;     /* bit s: status s is a failed solve; bits 0 .. 5 */
+  int32_t reserved;
+} dgsqp_hold_t;
+/* The setting of the handle's SUBSEQUENT closed-loop launches (copied); NULL: off.  DGSQP_E_ARG, message starting "plan hold: ": no
+   plant set, replan_every outside 1 .. N, an unknown on_fail, a mask bit above 5; and, from dgsqp_closed_loop_batch, a launch without a
+   plant.  dgsqp_solve_batch and launches without the setting are not affected.
+   dgsqp_fetch_plan_hold: u_game [T][B][n_u] (NaN where a step never ran) and plan_stage [T][B] (-1 there) of the last launch with the
+   setting; capacity_doubles = what u_game can hold (DGSQP_E_ARG when it is too small, when a pointer is NULL or when no such launch has
+   run). */
+int dgsqp_set_plan_hold(dgsqp_handle_t h, const dgsqp_hold_t* hold);
+int dgsqp_fetch_plan_hold(dgsqp_handle_t h, double* u_game /* [T][B][n_u] */, int32_t* plan_stage /* [T][B] */, int64_t capacity_doubles);
+
+/*
  * Device-resident variant used by bench.py: inputs are staged once with
  * dgsqp_stage_inputs(); dgsqp_solve_staged() runs only the solve kernel on
  * the handle's stream; dgsqp_fetch_results() copies results back.

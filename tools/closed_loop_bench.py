@@ -22,6 +22,9 @@ delay per chain), ``estimates`` (that plant, solves from q + 1e-3 N(0, 1)), and 
 PID lane follower with its default gains, references from x0) and ``replay`` (car 2 replays the commands the game gave it in the ``plant``
 launch: the same chains as ``plant``, bit for bit, through the drivers' kernel).  ``--carry-u-prev`` adds ``carry-u-prev``: ``plain`` with the command of step t carried into solve t + 1 as the input
 before its stage 0 (``step_batch(..., u_prev=True)``) -- other solves, so other chains: its time stands next to the others, not against them.
+``--kinds ...,hold`` adds ``hold`` (named in ``--kinds`` only): the ``plant`` launch with a held plan (``closed_loop.PlanHold``, on_fail 'reference'), once per value of
+``--replan-every`` (default 1).  R = 1 is the ``plant`` launch's own chains through the held-plan kernel (asserted), so its time stands against ``plant``'s; R > 1 follows each
+accepted plan for R control steps -- other chains -- and the report counts the solves actually run and the held steps.
 ``--kinds`` restricts the list (a library without the newer entry points can still time
 ``plain,plant``), ``--label`` names the build in the output, ``--append`` adds to ``--out`` instead of replacing it.
 
@@ -65,6 +68,7 @@ def host_loop(s, x0, u_am, T):
 
 KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor', 'pid', 'replay')
 CARRY = 'carry-u-prev'          # added by --carry-u-prev (or named in --kinds): 'plain' with step_batch(..., u_prev=True)
+HOLD = 'hold'                   # named in --kinds: 'plant' with step_batch(..., hold=PlanHold(replan_every=R)) for every R of --replan-every
 
 
 def ensemble_bench(args, g, s, x0, u_am):
@@ -75,9 +79,9 @@ def ensemble_bench(args, g, s, x0, u_am):
     kinds = [k for k in args.kinds.split(',') if k]
     if args.carry_u_prev and CARRY not in kinds:
         kinds.append(CARRY)
-    unknown = [k for k in kinds if k not in KINDS + (CARRY,)]
+    unknown = [k for k in kinds if k not in KINDS + (CARRY, HOLD)]
     if unknown:
-        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS + (CARRY,)}')
+        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS + (CARRY, HOLD)}')
     base = dict(method='rk4', M=10, sim_steps=2)
     calls = {'plain': lambda: s.step_batch(x0, u_am, T)}
     if CARRY in kinds:
@@ -94,7 +98,16 @@ def ensemble_bench(args, g, s, x0, u_am):
         again = calls['replay']()
         for key in ('status', 'num_iters', 'q', 'u_plant'):
             assert np.array_equal(again[key], own[key], equal_nan=True), f'{key}: the replay of the plant launch\'s own commands differs from it'
-    if any(k not in ('plain', 'plant', 'pid', 'replay', CARRY) for k in kinds):
+    if HOLD in kinds:
+        at = kinds.index(HOLD)
+        kinds[at:at + 1] = [f'{HOLD} R={R}' for R in args.replan_every]
+        for R in args.replan_every:
+            calls[f'{HOLD} R={R}'] = lambda R=R: s.step_batch(x0, u_am, T, plant=plant, hold=closed_loop.PlanHold(replan_every=R))
+        if 1 in args.replan_every:
+            own, held = calls['plant'](), calls[f'{HOLD} R=1']()
+            for key in ('status', 'num_iters', 'q', 'u_plant'):
+                assert np.array_equal(held[key], own[key], equal_nan=True), f'{key}: the held-plan launch with R = 1 differs from the plant launch'
+    if any(k not in ('plain', 'plant', 'pid', 'replay', CARRY) and not k.startswith(HOLD) for k in kinds):
         cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
         spread = dict(mass=0.1, drag_coefficient=0.1, pacejka_d_front=0.1, pacejka_d_rear=0.1)
         delays = np.random.default_rng(args.seed).integers(0, 3, size=(B, len(cfgs), 2))
@@ -120,6 +133,8 @@ def ensemble_bench(args, g, s, x0, u_am):
     for k in kinds:
         r = last[k]
         note = f'steps run {int((r["status"] >= 0).sum())} of {B * T}, iterations per chain: mean {r["num_iters"].sum(axis=1).mean():.1f}'
+        if 'plan_stage' in r:
+            note = f'solves run {int((r["status"] >= 0).sum())} and held steps {int((r["status"] == -2).sum())} of {B * T}' + note[note.index(','):]
         if 'hit_step' in r:
             note += f'; chains with a contact {int((r["hit_step"] >= 0).sum())}, mean box_excess {np.nanmean(r["box_excess"]):.4f}'
         lines.append(f'[{args.label}] {k:18s} kernel {ms(kern[k])}; wall {ms(wall[k])}; kernel times {", ".join(f"{v * 1e3:.1f}" for v in kern[k])} ms; {note}')
@@ -134,8 +149,9 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--plant', action='store_true', help='also time step_batch with a plant of its own (c)')
     ap.add_argument('--ensemble', action='store_true', help='time the launch kinds of a robustness study instead (see the module docstring)')
-    ap.add_argument('--kinds', default=','.join(KINDS), help='with --ensemble: comma-separated subset of ' + ', '.join(KINDS))
+    ap.add_argument('--kinds', default=','.join(KINDS), help='with --ensemble: comma-separated subset of ' + ', '.join(KINDS + (CARRY, HOLD)))
     ap.add_argument('--carry-u-prev', action='store_true', help='with --ensemble: also time the plain launch with the command carried into the next solve (kind ' + CARRY + ')')
+    ap.add_argument('--replan-every', type=int, nargs='+', default=[1], help='with --ensemble and the kind ' + HOLD + ': one launch kind per value R')
     ap.add_argument('--label', default='this build', help='with --ensemble: names the build in the report')
     ap.add_argument('--append', action='store_true', help='with --ensemble: add to --out instead of replacing it')
     ap.add_argument('--out', default=str(ROOT / 'profiles' / 'closed_loop_dyn_curve_N25.txt'))
