@@ -7,7 +7,7 @@ from .game import (RacingCost, InputRateLimits, CollisionAvoidance, GoalTracking
                    LaneHalfPlane)
 from .dynamics import (KinematicBicycleConfig, DynamicBicycleConfig, UnicycleConfig, MultiAgentModelConfig,  # noqa: F401
                        CasadiKinematicBicycleCombined, CasadiDynamicBicycleCombined, CasadiKinematicUnicycle,
-                       CasadiDecoupledMultiAgentDynamicsModel)
+                       CasadiKinematicUnicycleCombined, CasadiDecoupledMultiAgentDynamicsModel)
 from .tracks import CurveTrack, ChicaneTrack, StraightTrack, RadiusArclengthTrack, get_track  # noqa: F401
 
 

@@ -14,6 +14,8 @@ MAX_SEGS = 16
 MAX_NQA = 8
 MAX_LANES = 2
 NUA = 2
+# DGSQP_MODEL_*: vehicle model ids (include/dgsqp.h)
+MODEL_KIN_BICYCLE, MODEL_DYN_BICYCLE, MODEL_UNICYCLE, MODEL_UNICYCLE_COMBINED = 0, 1, 2, 3
 MAX_DELAY = 16       # DGSQP_MAX_DELAY: longest input delay line of a closed-loop plant, in simulation steps
 
 STATUS_MSG = ['conv_abs_tol', 'conv_rel_tol', 'max_it', 'diverged', 'qp_fail', 'time_limit']

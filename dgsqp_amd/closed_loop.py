@@ -74,12 +74,16 @@ def feedback(x_pred: np.ndarray, u_am: np.ndarray, status, u_ws_prev: np.ndarray
     return q_next, u_ws_next, np.isfinite(q_next).all(axis=-1)
 
 
-def config_model_id(config) -> int:
+def config_model_id(config, game_model: Optional[int] = None) -> int:
     """Model class (DGSQP_MODEL_*) a dynamics config belongs to: the bicycle configs name theirs, every other ``DynamicsConfig`` is what
-    the unicycle is built from (dynamics.CasadiKinematicUnicycle)."""
+    the two unicycles are built from (dynamics.CasadiKinematicUnicycle, class 2, and the Frenet point mass
+    dynamics.CasadiKinematicUnicycleCombined, class 3).  Such a config does not say which; ``game_model``, the class of the game's
+    agent it is a plant for, decides between the two, and it is class 2 where that is a bicycle (which then refuses it) or not given."""
     if isinstance(config, DynamicBicycleConfig):
         return 1
-    return 0 if isinstance(config, KinematicBicycleConfig) else 2
+    if isinstance(config, KinematicBicycleConfig):
+        return 0
+    return 3 if game_model == 3 else 2
 
 
 @dataclass
@@ -145,10 +149,11 @@ class PlantModel:
                 raise ValueError(f'per_chain_configs must be [B][M] = [{B}][{n_agents}] configs')
             for b, row in enumerate(self.per_chain_configs):
                 for a, cfg in enumerate(row):
-                    if config_model_id(cfg) != problem.agents[a].model:
-                        raise ValueError(f'per-chain plant config [{b}][{a}] is of model class {config_model_id(cfg)}, the game\'s agent is of '
+                    mid = config_model_id(cfg, problem.agents[a].model)
+                    if mid != problem.agents[a].model:
+                        raise ValueError(f'per-chain plant config [{b}][{a}] is of model class {mid}, the game\'s agent is of '
                                          f'class {problem.agents[a].model}: a plant keeps the game\'s model class and state layout')
-                    fill_vehicle(vehicles[b * n_agents + a], config_model_id(cfg), cfg)
+                    fill_vehicle(vehicles[b * n_agents + a], mid, cfg)
         else:                       # per-chain delays alone: every chain has the shared plant's vehicles
             base = self.lower(problem)
             src = problem.agents if base.use_game_agents else base.agents
@@ -190,10 +195,11 @@ class PlantModel:
             if len(self.dynamics_configs) != n_agents:
                 raise ValueError(f'Number of agents: {n_agents}, but {len(self.dynamics_configs)} plant configs were provided')
             for a, cfg in enumerate(self.dynamics_configs):
-                if config_model_id(cfg) != problem.agents[a].model:
-                    raise ValueError(f'plant config {a} is of model class {config_model_id(cfg)}, the game\'s agent is of class '
+                mid = config_model_id(cfg, problem.agents[a].model)
+                if mid != problem.agents[a].model:
+                    raise ValueError(f'plant config {a} is of model class {mid}, the game\'s agent is of class '
                                      f'{problem.agents[a].model}: a plant keeps the game\'s model class and state layout')
-                fill_vehicle(pt.agents[a], config_model_id(cfg), cfg)
+                fill_vehicle(pt.agents[a], mid, cfg)
         return pt
 
 

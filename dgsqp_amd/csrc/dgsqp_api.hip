@@ -1725,7 +1725,7 @@ int dgsqp_pid_warm_start_batch(dgsqp_handle_t h, int64_t B, const double* q0, co
   HIPCHK(h, hipSetDevice(h->device));
   const DgProb& D = h->hp;
   for (int a = 0; a < D.M; a++)
-    if (D.nqa[a] == 4) { h->err = "the PID lane follower needs a Frenet-frame model (the merge script starts from zero inputs)"; return DGSQP_E_ARG; }
+    if (D.mdl[a] == DG_UNI) { h->err = "the PID lane follower needs a Frenet-frame model (the merge script starts from zero inputs)"; return DGSQP_E_ARG; }
   TmpBuf tb;
   const size_t nx = (size_t)(D.N + 1) * D.nq;
   double* dq0 = tb.alloc<double>(B * D.nq); double* du = tb.alloc<double>(B * D.n);
@@ -1760,7 +1760,7 @@ int dgsqp_sample_batch(dgsqp_handle_t h, int64_t B, const dgsqp_sampler_t* spec,
   if (!merge && (!pid || pid->substeps < 1 || spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1)) { h->err = "bad sampler description"; return DGSQP_E_ARG; }
   if (spec->kind == DGSQP_SAMPLER_FIRST_SEGMENT && D.M != 2) { h->err = "the first-segment sampler places two cars"; return DGSQP_E_ARG; }
   for (int a = 0; a < D.M; a++)
-    if ((D.nqa[a] == 4) != merge) { h->err = "sampler and vehicle model do not fit (merge: unicycles; the others: Frenet-frame models)"; return DGSQP_E_ARG; }
+    if ((D.mdl[a] == DG_UNI) != merge) { h->err = "sampler and vehicle model do not fit (merge: unicycles; the others: Frenet-frame models)"; return DGSQP_E_ARG; }
   if (candidates) *candidates = 0;
   if (B == 0) return DGSQP_OK;
   { const int rc = stage_begin(h, B); if (rc) return rc; }

@@ -102,13 +102,14 @@ __device__ inline void dev_monitor_store(const dgsqp_agent_t& game, int nqa, con
 // length d: read [0], append); d = 0 integrates under u_new.  One plant step is dev_fd_t's arithmetic on f_c with the plant's agent
 // record, step length and sub-step count (euler: one step per simulation step, as the game's model).
 // MON with a non-null `mon` ([S][M][3], the workgroup's): the agent's monitor record after every simulation step (dev_monitor_store).
-template <int NQA, bool SPL, bool MON = false>
+template <int MDL, bool SPL, bool MON = false>
 __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_plant_t& pl, int a, int64_t count, const double* u_new,
                                        double* line, double* u_rec, int nu, double* qa, double* mon = nullptr) {
   typedef Ty<0> T;
   const dgsqp_agent_t& ag = pl.agents[a];
   const int S = pl.sim_steps, integ = pl.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : pl.substeps;
   const double hs = P.dt / S, h = hs / nsub;
+  constexpr int NQA = dg_model_nq(MDL);
   T x[NQA], k1[NQA], k2[NQA], t[NQA], u[DGSQP_NUA];
 #pragma unroll
   for (int i = 0; i < NQA; i++) x[i].c[0] = qa[i];
@@ -125,37 +126,35 @@ __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_pla
       u_rec[(int64_t)j * nu + ch] = v;
     }
     FcPre<0> pre;
-    if constexpr (NQA == 8) dev_fc_pre_dyn<0>(ag, u, pre);
-    else if constexpr (NQA == 4) { pre.im = 1.0 / ag.mass; pre.iz = 0.0; pre.ilr = 0.0; }
-    else dev_fc_pre_kin<0>(ag, u, pre);
+    dev_fc_pre<0, MDL>(ag, u, pre);
     for (int m = 0; m < nsub; m++) {
-      dev_fc<0, NQA, SPL>(P, ag, x, u, pre, k1);
+      dev_fc<0, MDL, SPL>(P, ag, x, u, pre, k1);
       if (integ == DGSQP_INT_RK4) {
 #pragma unroll
         for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * (h / 2);
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
         for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * (h / 2); k1[i] = k1[i] + k2[i] * 2.0; }
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
         for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * h; k1[i] = k1[i] + k2[i] * 2.0; }
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
         for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 6.0);
       } else if (integ == DGSQP_INT_RK3) {
 #pragma unroll
         for (int i = 0; i < NQA; i++) { k1[i] = k1[i] * h; t[i] = x[i] + k1[i] * 0.5; }
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
         for (int i = 0; i < NQA; i++) { k2[i] = k2[i] * h; t[i] = x[i] - k1[i] + k2[i] * 2.0; }
         T k3[NQA];
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k3);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k3);
 #pragma unroll
         for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
       } else if (integ == DGSQP_INT_RK2) {
 #pragma unroll
         for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * h;
-        dev_fc<0, NQA, SPL>(P, ag, t, u, pre, k2);
+        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
         for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 2);
       } else {
@@ -192,13 +191,15 @@ __device__ inline int dev_plant_step(const dgsqp_plant_t& pl, double* lines, dou
   for (int i = 0; i < DGSQP_MAX_NQA; i++) qa[i] = i < nqa ? q_t[qo + i] : 0.0;
   double* u_rec = u_plant + tb_b * S * D.nu + a * DGSQP_NUA;
   const int64_t count = (int64_t)t * S;
-  if (nqa == 4) dev_plant_agent<4, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+  const int mdl = D.mdl[a];      // the plant's agent is of the game's model class (dgsqp_set_plant refuses any other)
+  if (mdl == DG_UNI) dev_plant_agent<DG_UNI, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+  else if (mdl == DG_PM) dev_plant_agent<DG_PM, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   else if (D.P.track_kind == DGSQP_TRACK_SPLINE) {
-    if (nqa == 8) dev_plant_agent<8, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
-    else dev_plant_agent<6, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+    if (mdl == DG_DYN) dev_plant_agent<DG_DYN, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+    else dev_plant_agent<DG_KIN, true, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   }
-  else if (nqa == 8) dev_plant_agent<8, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
-  else dev_plant_agent<6, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+  else if (mdl == DG_DYN) dev_plant_agent<DG_DYN, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
+  else dev_plant_agent<DG_KIN, false, MON>(D.P, pl, a, count, u_new, line, u_rec, D.nu, qa, mon);
   int bad = 0;
   for (int i = 0; i < DGSQP_MAX_NQA; i++)
     if (i < nqa) {

@@ -638,27 +638,55 @@ __device__ inline void dev_fc_uni(const Ty<DEG>* q, const Ty<DEG>* u, const FcPr
   dq[3] = u[1];
 }
 
-template <int DEG, int NQA, bool SPL = false>
+// point mass in the track's Frenet frame (dynamics_models.py:536-541); q = [x, y, v, e_psi, s, x_tran], u = [Fx, wz].  Reads mass
+// and c_da only; no elementary function of the input, so pre.im is all its FcPre carries.
+template <int DEG>
+__device__ inline void dev_fc_pm(const dgsqp_problem_t& P, const dgsqp_agent_t& ag, const Ty<DEG>* q, const Ty<DEG>* u, const FcPre<DEG>& pre, Ty<DEG>* dq) {
+  typedef Ty<DEG> T;
+  double c;
+  T psit;
+  dev_track(P, q[4], c, psit);
+  T s1, c1, s2, c2;
+  ty_sincos(psit + q[3], s1, c1);
+  ty_sincos(q[3], s2, c2);
+  const T vlon = q[2] * c2 * ty_recip(1.0 - q[5] * c);
+  dq[0] = q[2] * c1;
+  dq[1] = q[2] * s1;
+  dq[2] = (u[0] - q[2] * ag.c_da) * pre.im;
+  dq[3] = u[1] - vlon * c;
+  dq[4] = vlon;
+  dq[5] = q[2] * s2;
+}
+
+// MDL: the model tag (DGSQP_MODEL_*), a template parameter for the reason SPL is one; NQA = dg_model_nq(MDL) wherever a count is needed
+template <int DEG, int MDL, bool SPL = false>
 __device__ inline void dev_fc(const dgsqp_problem_t& P, const dgsqp_agent_t& ag, const Ty<DEG>* q, const Ty<DEG>* u, const FcPre<DEG>& pre, Ty<DEG>* dq) {
-  if constexpr (NQA == 8) dev_fc_dyn<DEG, SPL>(P, ag, q, u, pre, dq);
-  else if constexpr (NQA == 4) dev_fc_uni<DEG>(q, u, pre, dq);
+  if constexpr (MDL == DG_DYN) dev_fc_dyn<DEG, SPL>(P, ag, q, u, pre, dq);
+  else if constexpr (MDL == DG_UNI) dev_fc_uni<DEG>(q, u, pre, dq);
+  else if constexpr (MDL == DG_PM) { static_assert(!SPL, "the Frenet point mass runs on arc tracks only"); dev_fc_pm<DEG>(P, ag, q, u, pre, dq); }
   else dev_fc_kin<DEG, SPL>(P, ag, q, u, pre, dq);
+}
+// the terms of f_c that depend on the input only, once per stage
+template <int DEG, int MDL>
+__device__ inline void dev_fc_pre(const dgsqp_agent_t& ag, const Ty<DEG>* u, FcPre<DEG>& pre) {
+  if constexpr (MDL == DG_DYN) dev_fc_pre_dyn<DEG>(ag, u, pre);
+  else if constexpr (MDL == DG_UNI || MDL == DG_PM) { pre.im = 1.0 / ag.mass; pre.iz = 0.0; pre.ilr = 0.0; }
+  else dev_fc_pre_kin<DEG>(ag, u, pre);
 }
 
 // one discrete step of the joint model's integrator (dynamics_models.py:88-99, :188-219).  The integrator is a template
 // parameter so that every instantiation keeps only the stage arrays it needs in registers (rk4: x, k-accumulator, k, t).
-template <int DEG, int NQA, int INTEG, bool SPL = false>
+template <int DEG, int MDL, int INTEG, bool SPL = false>
 __device__ inline void dev_fd_t(const dgsqp_problem_t& P, const dgsqp_agent_t& ag, const Ty<DEG>* q, const Ty<DEG>* u, Ty<DEG>* qn) {
   typedef Ty<DEG> T;
+  constexpr int NQA = dg_model_nq(MDL);
   T x[NQA], k1[NQA], k2[NQA], t[NQA];
   FcPre<DEG> pre;
-  if constexpr (NQA == 8) dev_fc_pre_dyn<DEG>(ag, u, pre);
-  else if constexpr (NQA == 4) { pre.im = 1.0 / ag.mass; pre.iz = 0.0; pre.ilr = 0.0; }
-  else dev_fc_pre_kin<DEG>(ag, u, pre);
+  dev_fc_pre<DEG, MDL>(ag, u, pre);
 #pragma unroll
   for (int i = 0; i < NQA; i++) x[i] = q[i];
   if constexpr (INTEG == DGSQP_INT_EULER) {
-    dev_fc<DEG, NQA, SPL>(P, ag, x, u, pre, k1);
+    dev_fc<DEG, MDL, SPL>(P, ag, x, u, pre, k1);
 #pragma unroll
     for (int i = 0; i < NQA; i++) qn[i] = x[i] + k1[i] * P.dt;
     return;
@@ -666,34 +694,34 @@ __device__ inline void dev_fd_t(const dgsqp_problem_t& P, const dgsqp_agent_t& a
   const double h = P.dt / P.substeps;
   for (int m = 0; m < P.substeps; m++) {
     if constexpr (INTEG == DGSQP_INT_RK4) {
-      dev_fc<DEG, NQA, SPL>(P, ag, x, u, pre, k1);
+      dev_fc<DEG, MDL, SPL>(P, ag, x, u, pre, k1);
 #pragma unroll
       for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * (h / 2);
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k2);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
       for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * (h / 2); k1[i] = k1[i] + k2[i] * 2.0; }
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k2);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
       for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * h; k1[i] = k1[i] + k2[i] * 2.0; }
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k2);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
       for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 6.0);
     } else if constexpr (INTEG == DGSQP_INT_RK3) {
       T k3[NQA];
-      dev_fc<DEG, NQA, SPL>(P, ag, x, u, pre, k1);
+      dev_fc<DEG, MDL, SPL>(P, ag, x, u, pre, k1);
 #pragma unroll
       for (int i = 0; i < NQA; i++) { k1[i] = k1[i] * h; t[i] = x[i] + k1[i] * 0.5; }
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k2);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
       for (int i = 0; i < NQA; i++) { k2[i] = k2[i] * h; t[i] = x[i] - k1[i] + k2[i] * 2.0; }
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k3);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k3);
 #pragma unroll
       for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
     } else {
-      dev_fc<DEG, NQA, SPL>(P, ag, x, u, pre, k1);
+      dev_fc<DEG, MDL, SPL>(P, ag, x, u, pre, k1);
 #pragma unroll
       for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * h;
-      dev_fc<DEG, NQA, SPL>(P, ag, t, u, pre, k2);
+      dev_fc<DEG, MDL, SPL>(P, ag, t, u, pre, k2);
 #pragma unroll
       for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 2);
     }
@@ -701,13 +729,13 @@ __device__ inline void dev_fd_t(const dgsqp_problem_t& P, const dgsqp_agent_t& a
 #pragma unroll
   for (int i = 0; i < NQA; i++) qn[i] = x[i];
 }
-template <int DEG, int NQA, bool SPL = false>
+template <int DEG, int MDL, bool SPL = false>
 __device__ inline void dev_fd(const dgsqp_problem_t& P, const dgsqp_agent_t& ag, const Ty<DEG>* q, const Ty<DEG>* u, Ty<DEG>* qn) {
   switch (P.integrator) {   // uniform
-    case DGSQP_INT_EULER: dev_fd_t<DEG, NQA, DGSQP_INT_EULER, SPL>(P, ag, q, u, qn); break;
-    case DGSQP_INT_RK4: dev_fd_t<DEG, NQA, DGSQP_INT_RK4, SPL>(P, ag, q, u, qn); break;
-    case DGSQP_INT_RK3: dev_fd_t<DEG, NQA, DGSQP_INT_RK3, SPL>(P, ag, q, u, qn); break;
-    default: dev_fd_t<DEG, NQA, DGSQP_INT_RK2, SPL>(P, ag, q, u, qn); break;
+    case DGSQP_INT_EULER: dev_fd_t<DEG, MDL, DGSQP_INT_EULER, SPL>(P, ag, q, u, qn); break;
+    case DGSQP_INT_RK4: dev_fd_t<DEG, MDL, DGSQP_INT_RK4, SPL>(P, ag, q, u, qn); break;
+    case DGSQP_INT_RK3: dev_fd_t<DEG, MDL, DGSQP_INT_RK3, SPL>(P, ag, q, u, qn); break;
+    default: dev_fd_t<DEG, MDL, DGSQP_INT_RK2, SPL>(P, ag, q, u, qn); break;
   }
 }
 

@@ -84,9 +84,10 @@ __device__ inline double dev_state_cost(const DgProb& D, int a, XP xk, bool term
 // ------------------------------------------------------------------------------------------------
 // trial input u + alpha du, written the same way everywhere so that equal points give bit-identical trajectories
 __device__ inline double step_u(double u, double alpha, double du) { return __builtin_fma(alpha, du, u); }
-template <int NQA, bool SPL = false>
+template <int MDL, bool SPL = false>
 __device__ inline void dev_rollout_agent(const DgProb& D, int a, clptr ub, clptr du, double alpha, lptr x) {
   typedef Ty<0> T;
+  constexpr int NQA = dg_model_nq(MDL);
   const int nq = D.nq, qo = D.qoff[a];
   T q[NQA], u[2], qn[NQA];
   for (int i = 0; i < NQA; i++) q[i].c[0] = x[qo + i];
@@ -94,7 +95,7 @@ __device__ inline void dev_rollout_agent(const DgProb& D, int a, clptr ub, clptr
     const int i0 = am_col(D, a, k, 0);
     u[0].c[0] = du ? step_u(ub[i0], alpha, du[i0]) : ub[i0];
     u[1].c[0] = du ? step_u(ub[i0 + 1], alpha, du[i0 + 1]) : ub[i0 + 1];
-    dev_fd<0, NQA, SPL>(D.P, D.P.agents[a], q, u, qn);
+    dev_fd<0, MDL, SPL>(D.P, D.P.agents[a], q, u, qn);
     for (int i = 0; i < NQA; i++) { q[i] = qn[i]; x[(k + 1) * nq + qo + i] = qn[i].c[0]; }
   }
 }
@@ -403,12 +404,13 @@ __device__ __noinline__ void dev_rollout_multi(const Ctx& c, clptr ub, clptr du,
     lptr x = j < K1 ? xs + j * xstride : xs2 + (j - K1) * xstride;
     if (split) dev_rollout_dyn<DYN_VEL>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
     else if (all_dyn) dev_rollout_dyn<DYN_BOTH>(D, w >> 1, w & 1, R, ub, du, alpha, x, nullptr);
-    else if (D.P.track_kind == DGSQP_TRACK_SPLINE && D.nqa[w] != 4) {
-      if (D.nqa[w] == 8) dev_rollout_agent<8, true>(D, w, ub, du, alpha, x); else dev_rollout_agent<6, true>(D, w, ub, du, alpha, x);
+    else if (D.P.track_kind == DGSQP_TRACK_SPLINE && D.mdl[w] != DG_UNI) {      // (no point mass here: dg_build refuses it on a spline track)
+      if (D.mdl[w] == DG_DYN) dev_rollout_agent<DG_DYN, true>(D, w, ub, du, alpha, x); else dev_rollout_agent<DG_KIN, true>(D, w, ub, du, alpha, x);
     }
-    else if (D.nqa[w] == 8) dev_rollout_agent<8>(D, w, ub, du, alpha, x);
-    else if (D.nqa[w] == 4) dev_rollout_agent<4>(D, w, ub, du, alpha, x);
-    else dev_rollout_agent<6>(D, w, ub, du, alpha, x);
+    else if (D.mdl[w] == DG_DYN) dev_rollout_agent<DG_DYN>(D, w, ub, du, alpha, x);
+    else if (D.mdl[w] == DG_UNI) dev_rollout_agent<DG_UNI>(D, w, ub, du, alpha, x);
+    else if (D.mdl[w] == DG_PM) dev_rollout_agent<DG_PM>(D, w, ub, du, alpha, x);
+    else dev_rollout_agent<DG_KIN>(D, w, ub, du, alpha, x);
   }
   __syncthreads();
 }
@@ -425,11 +427,12 @@ __device__ inline void dir_pair(int neff, int dir, int& i, int& j) {
   while (p >= neff - 1 - i) { p -= neff - 1 - i; i++; }
   j = i + 1 + p;
 }
-template <int DEG, int NQA, int INTEG, bool SPL = false>
+template <int DEG, int MDL, int INTEG, bool SPL = false>
 __device__ __forceinline__ void dev_taylor_item_impl(const Ctx& c, int a, int k, int dir, clptr ue) {
   const DgProb& D = dg_prob;
   const DgLds& L = D.L;
   typedef Ty<DEG> T;
+  constexpr int NQA = dg_model_nq(MDL);
   clptr x = LP(L.e_x + k * D.nq + D.qoff[a]);
   T q[NQA], u[2], out[NQA];
   for (int i = 0; i < NQA; i++) q[i] = ty_const<DEG>(x[i]);
@@ -445,7 +448,7 @@ __device__ __forceinline__ void dev_taylor_item_impl(const Ctx& c, int a, int k,
 #pragma unroll
     for (int i = 0; i < 2; i++) u[i].c[1] = (NQA + i == zi || NQA + i == zj) ? 1.0 : 0.0;
   }
-  dev_fd_t<DEG, NQA, INTEG, SPL>(D.P, D.P.agents[a], q, u, out);
+  dev_fd_t<DEG, MDL, INTEG, SPL>(D.P, D.P.agents[a], q, u, out);
   if (dir < D.neff[a]) {
     const int z = D.effvar[a][dir];
     if (z < NQA) {
@@ -464,20 +467,22 @@ __device__ __forceinline__ void dev_taylor_item_impl(const Ctx& c, int a, int k,
 }
 // First-derivative items are compiled out of line, one instantiation per (model, integrator), which keeps their register
 // allocation tight (no spills for euler); the second-order items are inlined into their caller.
-template <int DEG, int NQA, int INTEG, bool SPL = false>
-__device__ __noinline__ void dev_taylor_item_ool(const Ctx& c, int a, int k, int dir, clptr ue) { dev_taylor_item_impl<DEG, NQA, INTEG, SPL>(c, a, k, dir, ue); }
-template <int DEG, int NQA, int INTEG>
+template <int DEG, int MDL, int INTEG, bool SPL = false>
+__device__ __noinline__ void dev_taylor_item_ool(const Ctx& c, int a, int k, int dir, clptr ue) { dev_taylor_item_impl<DEG, MDL, INTEG, SPL>(c, a, k, dir, ue); }
+template <int DEG, int MDL, int INTEG>
 __device__ __forceinline__ void dev_taylor_item(const Ctx& c, int a, int k, int dir, clptr ue) {
   // games on a spline track: their own out-of-line instantiations (the arc-track ones keep their register allocation)
-  if (NQA != 4 && dg_prob.P.track_kind == DGSQP_TRACK_SPLINE) { dev_taylor_item_ool<DEG, NQA, INTEG, true>(c, a, k, dir, ue); return; }
-  if constexpr (DEG >= 2 && NQA == 8 && INTEG != DGSQP_INT_EULER) dev_taylor_item_impl<DEG, NQA, INTEG>(c, a, k, dir, ue);
-  else dev_taylor_item_ool<DEG, NQA, INTEG>(c, a, k, dir, ue);
+  if constexpr (MDL == DG_KIN || MDL == DG_DYN)
+    if (dg_prob.P.track_kind == DGSQP_TRACK_SPLINE) { dev_taylor_item_ool<DEG, MDL, INTEG, true>(c, a, k, dir, ue); return; }
+  if constexpr (DEG >= 2 && MDL == DG_DYN && INTEG != DGSQP_INT_EULER) dev_taylor_item_impl<DEG, MDL, INTEG>(c, a, k, dir, ue);
+  else dev_taylor_item_ool<DEG, MDL, INTEG>(c, a, k, dir, ue);
 }
 template <int DEG, int INTEG>
-__device__ __forceinline__ void dev_taylor_item_nqa(const Ctx& c, int nqa, int a, int k, int dir, clptr ue) {
-  if (nqa == 8) dev_taylor_item<DEG, 8, INTEG>(c, a, k, dir, ue);
-  else if (nqa == 4) dev_taylor_item<DEG, 4, INTEG>(c, a, k, dir, ue);
-  else dev_taylor_item<DEG, 6, INTEG>(c, a, k, dir, ue);
+__device__ __forceinline__ void dev_taylor_item_mdl(const Ctx& c, int mdl, int a, int k, int dir, clptr ue) {
+  if (mdl == DG_DYN) dev_taylor_item<DEG, DG_DYN, INTEG>(c, a, k, dir, ue);
+  else if (mdl == DG_UNI) dev_taylor_item<DEG, DG_UNI, INTEG>(c, a, k, dir, ue);
+  else if (mdl == DG_PM) dev_taylor_item<DEG, DG_PM, INTEG>(c, a, k, dir, ue);
+  else dev_taylor_item<DEG, DG_KIN, INTEG>(c, a, k, dir, ue);
 }
 template <int DEG>
 __device__ __noinline__ void dev_dyn_derivs(const Ctx& c, clptr ue) {
@@ -505,10 +510,10 @@ __device__ __noinline__ void dev_dyn_derivs(const Ctx& c, clptr ue) {
       for (int it = TID; it < D.N * nd; it += NT) {
         const int k = it / nd, dir = it % nd;
         switch (D.P.integrator) {
-          case DGSQP_INT_EULER: dev_taylor_item_nqa<DEG, DGSQP_INT_EULER>(c, D.nqa[a], a, k, dir, ue); break;
-          case DGSQP_INT_RK4: dev_taylor_item_nqa<DEG, DGSQP_INT_RK4>(c, D.nqa[a], a, k, dir, ue); break;
-          case DGSQP_INT_RK3: dev_taylor_item_nqa<DEG, DGSQP_INT_RK3>(c, D.nqa[a], a, k, dir, ue); break;
-          default: dev_taylor_item_nqa<DEG, DGSQP_INT_RK2>(c, D.nqa[a], a, k, dir, ue); break;
+          case DGSQP_INT_EULER: dev_taylor_item_mdl<DEG, DGSQP_INT_EULER>(c, D.mdl[a], a, k, dir, ue); break;
+          case DGSQP_INT_RK4: dev_taylor_item_mdl<DEG, DGSQP_INT_RK4>(c, D.mdl[a], a, k, dir, ue); break;
+          case DGSQP_INT_RK3: dev_taylor_item_mdl<DEG, DGSQP_INT_RK3>(c, D.mdl[a], a, k, dir, ue); break;
+          default: dev_taylor_item_mdl<DEG, DGSQP_INT_RK2>(c, D.mdl[a], a, k, dir, ue); break;
         }
       }
     }
@@ -528,10 +533,10 @@ __device__ __noinline__ void dev_dyn_derivs(const Ctx& c, clptr ue) {
       if (it < D.N * nd) {
         const int k = it / nd, dir = it % nd;
         switch (D.P.integrator) {   // one out-of-line instantiation per (model, integrator): registers are allocated per variant
-          case DGSQP_INT_EULER: dev_taylor_item_nqa<DEG, DGSQP_INT_EULER>(c, D.nqa[a], a, k, dir, ue); break;
-          case DGSQP_INT_RK4: dev_taylor_item_nqa<DEG, DGSQP_INT_RK4>(c, D.nqa[a], a, k, dir, ue); break;
-          case DGSQP_INT_RK3: dev_taylor_item_nqa<DEG, DGSQP_INT_RK3>(c, D.nqa[a], a, k, dir, ue); break;
-          default: dev_taylor_item_nqa<DEG, DGSQP_INT_RK2>(c, D.nqa[a], a, k, dir, ue); break;
+          case DGSQP_INT_EULER: dev_taylor_item_mdl<DEG, DGSQP_INT_EULER>(c, D.mdl[a], a, k, dir, ue); break;
+          case DGSQP_INT_RK4: dev_taylor_item_mdl<DEG, DGSQP_INT_RK4>(c, D.mdl[a], a, k, dir, ue); break;
+          case DGSQP_INT_RK3: dev_taylor_item_mdl<DEG, DGSQP_INT_RK3>(c, D.mdl[a], a, k, dir, ue); break;
+          default: dev_taylor_item_mdl<DEG, DGSQP_INT_RK2>(c, D.mdl[a], a, k, dir, ue); break;
         }
       }
     }
@@ -596,9 +601,9 @@ __device__ __noinline__ void dev_rollout_with_derivs(const Ctx& c, clptr ue, lpt
     if (it < D.N * nd) {
       const int k = it / nd, dir = it % nd;
       switch (D.P.integrator) {
-        case DGSQP_INT_RK4: dev_taylor_item_nqa<2, DGSQP_INT_RK4>(c, 8, a, k, dir, ue); break;
-        case DGSQP_INT_RK3: dev_taylor_item_nqa<2, DGSQP_INT_RK3>(c, 8, a, k, dir, ue); break;
-        default: dev_taylor_item_nqa<2, DGSQP_INT_RK2>(c, 8, a, k, dir, ue); break;
+        case DGSQP_INT_RK4: dev_taylor_item_mdl<2, DGSQP_INT_RK4>(c, DG_DYN, a, k, dir, ue); break;
+        case DGSQP_INT_RK3: dev_taylor_item_mdl<2, DGSQP_INT_RK3>(c, DG_DYN, a, k, dir, ue); break;
+        default: dev_taylor_item_mdl<2, DGSQP_INT_RK2>(c, DG_DYN, a, k, dir, ue); break;
       }
     }
   }

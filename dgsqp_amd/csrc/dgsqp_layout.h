@@ -25,6 +25,14 @@
 #define DG_NH (DG_BLOCK / 128)  // row-groups of the register-resident matrix slices (thread = column x row-group)
 #define DG_LDS_LIMIT ((163840 - 512) / DG_WG_PER_CU)   // 160 KB per CU minus the kernel's static LDS (256 B per workgroup)
 
+// The vehicle model of a device template is its DGSQP_MODEL_* id (MDL), chosen at compile time like SPL; the state count follows
+// from it, not the other way round: the kinematic bicycle and the Frenet point mass both have six states, in the same order.
+__host__ __device__ constexpr int dg_model_nq(int mdl) { return mdl == DGSQP_MODEL_DYN_BICYCLE ? 8 : (mdl == DGSQP_MODEL_UNICYCLE ? 4 : 6); }
+#define DG_KIN DGSQP_MODEL_KIN_BICYCLE
+#define DG_DYN DGSQP_MODEL_DYN_BICYCLE
+#define DG_UNI DGSQP_MODEL_UNICYCLE
+#define DG_PM DGSQP_MODEL_UNICYCLE_COMBINED
+
 enum { DG_R_OBS = 0, DG_R_RATE_UB, DG_R_RATE_LB, DG_R_IN_UB, DG_R_IN_LB, DG_R_ST_UB, DG_R_ST_LB, DG_R_LANE };
 
 struct DgRow {      // one inequality row
@@ -98,6 +106,7 @@ struct DgProb {
   dgsqp_params_t par;
   int M, N, nq, nu, n, nc, npairs, ndense, ngd, ntask;
   int nqa[DGSQP_MAX_AGENTS], qoff[DGSQP_MAX_AGENTS], sidx[DGSQP_MAX_AGENTS], eyidx[DGSQP_MAX_AGENTS];
+  int mdl[DGSQP_MAX_AGENTS];   // the agent's model tag (DGSQP_MODEL_*): what the kernels dispatch f_c on; nqa[a] = dg_model_nq(mdl[a])
   double inv_track_L;
   double eig_floor;    // value given to negative eigenvalues by _nearestPD (par.eig_floor, 1e-10 when not set)
   int uniform_nqa;
@@ -434,10 +443,13 @@ static inline std::string dg_build(const dgsqp_problem_t& P, const dgsqp_params_
   for (int a = 0; a < P.M; a++) {
     if (P.agents[a].model != P.agents[0].model) D.uniform_nqa = 0;
     const int mdl = P.agents[a].model;
-    if (mdl != DGSQP_MODEL_KIN_BICYCLE && mdl != DGSQP_MODEL_DYN_BICYCLE && mdl != DGSQP_MODEL_UNICYCLE) return "unsupported vehicle model";
-    D.nqa[a] = mdl == DGSQP_MODEL_DYN_BICYCLE ? 8 : (mdl == DGSQP_MODEL_UNICYCLE ? 4 : 6);
+    if (mdl != DGSQP_MODEL_KIN_BICYCLE && mdl != DGSQP_MODEL_DYN_BICYCLE && mdl != DGSQP_MODEL_UNICYCLE && mdl != DGSQP_MODEL_UNICYCLE_COMBINED)
+      return "unsupported vehicle model";
+    if (mdl == DGSQP_MODEL_UNICYCLE_COMBINED && P.track_kind != DGSQP_TRACK_ARCS) return "the Frenet point mass (model 3) runs on arc tracks only";
+    D.mdl[a] = mdl;
+    D.nqa[a] = dg_model_nq(mdl);
     D.qoff[a] = D.nq; D.nq += D.nqa[a];
-    // Frenet states s, e_y are the last two of both bicycles.  The unicycle has none: its slots (v, psi) only ever meet
+    // Frenet states s, e_y (x_tran) are the last two of both bicycles and of the point mass.  The unicycle has none: its slots (v, psi) only ever meet
     // zero progress / competition / blocking weights, and carry the goal-tracking curvature of the last two states.
     D.sidx[a] = D.nqa[a] - 2; D.eyidx[a] = D.nqa[a] - 1;
     if (mdl == DGSQP_MODEL_UNICYCLE && (P.agents[a].w_prog != 0.0 || P.agents[a].w_comp != 0.0 || P.agents[a].w_block != 0.0))

@@ -131,7 +131,7 @@ __global__ void dg_sample_zero_rollout_kernel(int64_t n, const double* __restric
     u[0].c[0] = 0.0; u[1].c[0] = 0.0;
     for (int i = 0; i < nqa && i < 4; i++) out[i] = q[i].c[0];
     for (int k = 0; k < D.N; k++) {
-      dev_fd<0, 4>(D.P, D.P.agents[a], q, u, qn);
+      dev_fd<0, DG_UNI>(D.P, D.P.agents[a], q, u, qn);
       for (int i = 0; i < 4; i++) q[i] = qn[i];
       for (int i = 0; i < nqa && i < 4; i++) out[(int64_t)(k + 1) * D.nq + i] = q[i].c[0];
     }

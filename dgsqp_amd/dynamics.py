@@ -12,6 +12,8 @@ signatures and the state/input layout follow the reference:
   state ``[x, y, v, e_psi, s, e_y]``, input ``[a, delta]``,
 * ``CasadiDynamicBicycleCombined`` (dynamics_models.py:1945-2179),
   state ``[x, y, v_x, v_y, psidot, e_psi, s, e_y]``,
+* ``CasadiKinematicUnicycleCombined`` (dynamics_models.py:491-608), a point mass in the track's Frenet frame,
+  state ``[x, y, v, e_psi, s, x_tran]``, input ``[Fx, wz]``,
 * ``CasadiDecoupledMultiAgentDynamicsModel`` (dynamics_models.py:2482-2632).
 
 The only arithmetic kept on the host is a numpy ``fc`` used by the PID
@@ -136,6 +138,7 @@ class MultiAgentModelConfig(DynamicsConfig):
 MODEL_KIN_BICYCLE = 0
 MODEL_DYN_BICYCLE = 1
 MODEL_UNICYCLE = 2
+MODEL_UNICYCLE_COMBINED = 3
 INTEGRATORS = {'euler': 0, 'rk4': 1, 'rk3': 2, 'rk2': 3}
 
 
@@ -190,7 +193,7 @@ class CasadiKinematicBicycleCombined(_FrenetBicycle):
     """Frenet-frame kinematic bicycle (dynamics_models.py:997-1150)."""
     model_id = MODEL_KIN_BICYCLE
     n_q = 6
-    s_idx, ey_idx = 4, 5
+    epsi_idx, s_idx, ey_idx = 3, 4, 5
 
     def __init__(self, t0: float, model_config: KinematicBicycleConfig = None, track=None):
         super().__init__(t0, model_config or KinematicBicycleConfig(), track)
@@ -252,7 +255,7 @@ class CasadiDynamicBicycleCombined(_FrenetBicycle):
     """Frenet-frame dynamic bicycle with Pacejka / linear tyres (dynamics_models.py:1945-2179)."""
     model_id = MODEL_DYN_BICYCLE
     n_q = 8
-    s_idx, ey_idx = 6, 7
+    epsi_idx, s_idx, ey_idx = 5, 6, 7
 
     def __init__(self, t0: float, model_config: DynamicBicycleConfig = None, track=None):
         super().__init__(t0, model_config or DynamicBicycleConfig(), track)
@@ -379,6 +382,57 @@ class CasadiKinematicUnicycle(_FrenetBicycle):
                 a1 = self.fc(q, u); a2 = self.fc(q + h * a1, u)
                 q = q + h * (a1 + a2) / 2
         return q
+
+
+class CasadiKinematicUnicycleCombined(_FrenetBicycle):
+    """Point mass in the track's Frenet frame (dynamics_models.py:491-608): state [x, y, v, e_psi, s, x_tran], input [Fx, wz].
+    Six states in the kinematic bicycle's order.  Of ``UnicycleConfig`` the dynamics read ``mass`` and ``damping_coefficient`` only
+    (:536-541); drag and rolling resistance are stored by the reference's constructor and never used."""
+    model_id = MODEL_UNICYCLE_COMBINED
+    n_q = 6
+    epsi_idx, s_idx, ey_idx = 3, 4, 5
+
+    def __init__(self, t0: float, model_config: UnicycleConfig = None, track=None):
+        super().__init__(t0, model_config or UnicycleConfig(), track=track)
+        c = self.model_config
+        self.m, self.c_da = c.mass, c.damping_coefficient
+        self.c_dr, self.c_r, self.p_r = c.drag_coefficient, c.rolling_resistance, c.rolling_resistance_exponent
+
+    def fc(self, q, u) -> np.ndarray:
+        """Continuous dynamics (dynamics_models.py:536-541)."""
+        _, _, v, epsi, s, xtran = q
+        Fx, wz = u
+        c = self.track.get_curvature(s)
+        psi_t = self.track.get_tangent_angle(s)
+        ds = v * np.cos(epsi) / (1 - xtran * c)
+        return np.array([v * np.cos(psi_t + epsi), v * np.sin(psi_t + epsi), (Fx - self.c_da * v) / self.m,
+                         wz - c * (v * np.cos(epsi)) / (1 - xtran * c), ds, v * np.sin(epsi)])
+
+    fd = CasadiKinematicUnicycle.fd
+
+    def state2q(self, state: VehicleState) -> np.ndarray:
+        return np.array([state.x.x, state.x.y, state.v.v_long, state.p.e_psi, state.p.s, state.p.x_tran])
+
+    def q2state(self, state: VehicleState, q):
+        state.x.x, state.x.y, state.v.v_long, state.p.e_psi, state.p.s, state.p.x_tran = (float(v) for v in q[:6])
+
+    def qu2state(self, state: VehicleState, q=None, u=None):
+        if q is not None:
+            self.q2state(state, q)
+        if u is not None:
+            state.u.u_a, state.u.u_steer = float(u[0]), float(u[1])
+
+    def qu2prediction(self, prediction: VehiclePrediction, q=None, u=None):
+        import array
+        if prediction is None:
+            prediction = VehiclePrediction()
+        if q is not None:
+            for name, col in (('x', 0), ('y', 1), ('v_long', 2), ('e_psi', 3), ('s', 4), ('x_tran', 5)):
+                setattr(prediction, name, array.array('d', q[:, col]))
+        if u is not None:
+            prediction.u_a = array.array('d', u[:, 0])
+            prediction.u_steer = array.array('d', u[:, 1])
+        return prediction
 
 
 class CasadiDecoupledMultiAgentDynamicsModel:

@@ -18,7 +18,7 @@ from typing import List
 import numpy as np
 
 from .dynamics import (CasadiDecoupledMultiAgentDynamicsModel, CasadiDynamicBicycleCombined,
-                       CasadiKinematicBicycleCombined, CasadiKinematicUnicycle, DynamicBicycleConfig,
+                       CasadiKinematicBicycleCombined, CasadiKinematicUnicycle, CasadiKinematicUnicycleCombined, DynamicBicycleConfig,
                        KinematicBicycleConfig, MultiAgentModelConfig, UnicycleConfig)
 from .game import (CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, LaneHalfPlane, RacingCost)
 from .solver_types import DGSQPParams, DGSQPV2Params
@@ -198,6 +198,32 @@ def barc_racing_game(N=15, M=2, reg=0.0) -> Game:
                 name=f'kb_barc_M{M}_N{N}', sampler='circuit')
 
 
+def point_mass_racing_game(track_kind='barc', N=20, M=2, theta_deg=45) -> Game:
+    """The planning game of the race demo, scripts/race/game_setup_unicycle.py: Frenet point masses
+    (``CasadiKinematicUnicycleCombined``; euler, dt 0.1, one sub-step, drag / damping / rolling resistance 0, :34-64), inputs within
+    +-2 and x_tran within +-(H - 0.1) with no other state bound (:66-94), no rate rows (:213, :229), stage cost 1/2 0.1 (Fx^2 + wz^2)
+    (:154-155, :163), terminal cost -1 s + 5 atan(s_other - s) (:159-166), radii 0.21 (:106-107), collision rows at stages 1..N
+    (:246-252), solver parameters with reg = 0 (:112-128).  ``'barc'`` is the script's L_track_barc circuit; ``'curve'`` and
+    ``'chicane'`` put the same game on the Monte-Carlo tracks (half width 1)."""
+    dt, r = 0.1, 0.21
+    if track_kind == 'barc':
+        track = get_track('L_track_barc')
+        H = track.half_width
+    else:
+        H = 1.0
+        track = _track(track_kind, theta_deg, H)
+    cfg = lambda i: UnicycleConfig(dt=dt, model_name=f'car{i + 1}_pm', noise=False, discretization_method='euler', drag_coefficient=0,
+                                   damping_coefficient=0, rolling_resistance=0, code_gen=False, M=1)
+    models = [CasadiKinematicUnicycleCombined(0, cfg(i), track=track) for i in range(M)]
+    joint = CasadiDecoupledMultiAgentDynamicsModel(0, models, MultiAgentModelConfig(
+        dt=dt, discretization_method='euler', use_mx=False, code_gen=False, verbose=True, compute_hessians=True, M=1))
+    params = DGSQPParams(solver_name='DGSQP', dt=dt, N=N, merit_function='stat_l1', nonmono_ls=True, line_search_iters=50, sqp_iters=50,
+                         p_tol=1e-3, d_tol=1e-3, reg=0.0, beta=0.01, tau=0.5, verbose=False)
+    cost = lambda: RacingCost(input_weight=(0.1, 0.1), input_rate_weight=(0.0, 0.0), comp_weights=(1.0, 5.0), comp_type='atan')
+    return Game(joint, [cost() for _ in range(M)], [None] * M, CollisionAvoidance([r] * M), _bounds(H - 0.1, M, u_a=2.0, u_steer=2.0),
+                params, track, H - 0.1, 2 * r, name=f'pm_{track_kind}_M{M}_N{N}', sampler='circuit' if track_kind == 'barc' else 'first_segment')
+
+
 def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10) -> Game:
     """BASELINE.json config 4: head-to-head race on the F1 track (``f1_austin_tenth_scale``, a ``CasadiBSplineTrack`` in the
     reference: track_lib.get_track :112-113, scripts/comparison_study_f1), long horizon N = 50.  Costs, rate limits, radii and
@@ -278,6 +304,12 @@ def _fc_batch(model, q, u):
     c = model.model_config
     ua, us = u[:, 0], u[:, 1]
     absv = lambda x: np.where(x > 0, x, -x)
+    if model.model_id == 3:         # Frenet point mass (dynamics_models.py:536-541)
+        v, epsi, s, xtran = q[:, 2], q[:, 3], q[:, 4], q[:, 5]
+        curv, psi_t = _track_lookup(model.track, s)
+        den = 1 - xtran * curv
+        return np.stack([v * np.cos(psi_t + epsi), v * np.sin(psi_t + epsi), (ua - model.c_da * v) / model.m,
+                         us - curv * (v * np.cos(epsi)) / den, v * np.cos(epsi) / den, v * np.sin(epsi)], axis=1)
     if model.model_id == 0:
         v, epsi, s, ey = q[:, 2], q[:, 3], q[:, 4], q[:, 5]
         beta = np.arctan2(np.tan(us) * model.L_r, model.L_f + model.L_r)
@@ -322,7 +354,7 @@ def pid_warm_start(model, q0, N, dt, u_max=(2.1, 0.436), du=(10.0, 4.5)):
     Gains: speed Kp=1; steer Kp=1, Ki=0.005 on 5*(e_y - e_y0) + e_psi; du/u saturation as the script passes them."""
     B = q0.shape[0]
     v_idx = 2
-    epsi_idx, ey_idx = (3, 5) if model.model_id == 0 else (5, 7)
+    epsi_idx, ey_idx = model.epsi_idx, model.ey_idx
     v_ref, lat_ref = q0[:, v_idx].copy(), q0[:, ey_idx].copy()
     ei = np.zeros(B)
     u_prev = np.zeros((B, 2))
@@ -479,7 +511,7 @@ def _sample_scenarios_circuit(game: Game, B: int, seed: int, max_rounds: int):
             xy = np.array([track.local_to_global((si, ei_, pi_))[:2] for si, ei_, pi_ in zip(s_, ey, ep)]).reshape(-1, 2)
             q = np.zeros((n, mdl.n_q))
             q[:, 0], q[:, 1], q[:, 2] = xy[:, 0], xy[:, 1], v
-            q[:, mdl.s_idx], q[:, mdl.ey_idx], q[:, 3 if mdl.model_id == 0 else 5] = s_, ey, ep      # e_psi: state 3 (kinematic) / 5 (dynamic)
+            q[:, mdl.s_idx], q[:, mdl.ey_idx], q[:, mdl.epsi_idx] = s_, ey, ep      # e_psi: state 3 (kinematic, point mass) / 5 (dynamic)
             qw, uw = pid_warm_start(mdl, q, N, dt, du=du)
             q0.append(q); q_ws.append(qw); u_ws.append(uw)
         keep = np.ones(n, bool)

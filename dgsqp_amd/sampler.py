@@ -115,7 +115,7 @@ def place(game, seed: int, cand):
         xy = np.array([track.local_to_global((si, ei, 0.0))[:2] for si, ei in zip(s, ey)]).reshape(-1, 2)
         q = np.zeros((n, mdl.n_q))
         q[:, 0], q[:, 1], q[:, 2] = xy[:, 0], xy[:, 1], v
-        q[:, 3 if mdl.model_id == 0 else 5] = epsi
+        q[:, mdl.epsi_idx] = epsi
         q[:, mdl.s_idx], q[:, mdl.ey_idx] = s, ey
         return q
     if kind == FIRST_SEGMENT:

@@ -49,6 +49,13 @@ def fill_vehicle(A: _ffi.AgentT, model_id: int, c) -> None:
     """The vehicle fields of one ``dgsqp_agent_t`` (model .. lin_Br) from a model class and its config: what ``build_problem`` writes for
     every agent of the game and ``closed_loop.PlantModel`` for every agent of a plant."""
     A.model = model_id
+    if model_id == 3:       # Frenet point mass: f_c reads mass and c_da (dynamics_models.py:536-541); the rest is defined and unread
+        A.L_f = A.L_r = 0.13
+        A.mass, A.I_z, A.gravity = float(c.mass), 1.0, 9.81
+        A.c_da = float(c.damping_coefficient)
+        A.c_dr = A.c_s = A.c_r = 0.0
+        A.p_r = 0.5
+        return
     if model_id != 2:
         A.L_f, A.L_r, A.mass = c.wheel_dist_front, c.wheel_dist_rear, c.mass
         A.c_dr, A.c_da = c.drag_coefficient, c.damping_coefficient
@@ -377,7 +384,7 @@ def plan(P: _ffi.ProblemT, par: _ffi.ParamsT) -> dict:
 def problem_dims(P: _ffi.ProblemT):
     """(n_q, n_u, n, n_c) from the constraint-assembly rules DGSQP.py:732-821."""
     M, N = P.M, P.N
-    nqa = [{0: 6, 1: 8, 2: 4}[P.agents[a].model] for a in range(M)]
+    nqa = [{0: 6, 1: 8, 2: 4, 3: 6}[P.agents[a].model] for a in range(M)]
     n_q, n_u = sum(nqa), 2 * M
     n_c = 0
     pairs = M * (M - 1) // 2 if P.obstacle_rows else 0

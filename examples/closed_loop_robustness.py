@@ -23,6 +23,7 @@ on the held plan or, with ``--on-fail reference``, applied a failed iterate.
     python examples/closed_loop_robustness.py --opponent pid
     python examples/closed_loop_robustness.py --carry-u-prev
     python examples/closed_loop_robustness.py --replan-every 3 --on-fail hold
+    python examples/closed_loop_robustness.py --model point-mass
 """
 import argparse
 import copy
@@ -33,7 +34,7 @@ import numpy as np
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 from dgsqp_amd.closed_loop import Drivers, PlanHold, PlantModel, perturbed_configs          # noqa: E402
-from dgsqp_amd.montecarlo import kinematic_racing_game                            # noqa: E402
+from dgsqp_amd.montecarlo import kinematic_racing_game, point_mass_racing_game    # noqa: E402
 from dgsqp_amd.solver import DGSQP                                                # noqa: E402
 
 
@@ -76,9 +77,11 @@ def main():
     ap.add_argument('--replan-every', type=int, default=1, help='solve at every R-th control step and follow the accepted plan in between')
     ap.add_argument('--on-fail', choices=('reference', 'hold'), default='reference',
                     help="after a failed solve: stage 0 of the failed iterate (the reference's step()), or the next stage of the plan the chain holds")
+    ap.add_argument('--model', choices=('kinematic', 'point-mass'), default='kinematic',
+                    help="the vehicles: kinematic bicycles, or the race demo's Frenet point masses (mass and damping perturbed; that game has no rate rows)")
     args = ap.parse_args()
 
-    game = kinematic_racing_game('curve', N=args.N)
+    game = point_mass_racing_game('curve', N=args.N) if args.model == 'point-mass' else kinematic_racing_game('curve', N=args.N)
     s = DGSQP(*game.solver_args(), print_method=None)
     B, T = args.batch, args.steps
     smp = s.sample_batch(game, B, seed=args.seed)
@@ -96,7 +99,8 @@ def main():
     print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]   max jump / (dt rate_ub): u_a, u_steer   steps over the limit'
           + ('   held steps   fallback steps' if hold is not None else ''))
     for spread in args.spreads:
-        ens = perturbed_configs(nominal, dict(mass=spread, drag_coefficient=spread, slip_coefficient=spread), B, args.seed)
+        fields = ('mass', 'damping_coefficient') if args.model == 'point-mass' else ('mass', 'drag_coefficient', 'slip_coefficient')
+        ens = perturbed_configs(nominal, {f: spread for f in fields}, B, args.seed)
         plant = PlantModel(per_chain_configs=ens, method='rk4', M=2, sim_steps=args.sim_steps)
         for name, drivers in opponents:
             r = s.step_batch(smp['x0'], smp['u_ws'], T, plant=plant, estimate_noise=noise, monitor='stop', drivers=drivers,

@@ -38,6 +38,9 @@ enum {
   DGSQP_MODEL_KIN_BICYCLE = 0, /* CasadiKinematicBicycleCombined :997  */
   DGSQP_MODEL_DYN_BICYCLE = 1, /* CasadiDynamicBicycleCombined   :1945 */
   DGSQP_MODEL_UNICYCLE = 2,    /* CasadiKinematicUnicycle        :306 : state [x, y, v, psi], input [F, omega] */
+  /* CasadiKinematicUnicycleCombined :491 : a point mass in the track's Frenet frame, state [x, y, v, e_psi, s, x_tran], input
+     [Fx, wz].  Reads mass and c_da only (:536-541).  Arc tracks only.  Six states in the kinematic bicycle's order. */
+  DGSQP_MODEL_UNICYCLE_COMBINED = 3,
 };
 #define DGSQP_MAX_LANES 2 /* lane half-plane rows per agent and stage */
 /* discretisation (dynamics_models.py:88-125, :188-219) */

@@ -154,11 +154,18 @@ def main():
     ap.add_argument('--replan-every', type=int, nargs='+', default=[1], help='with --ensemble and the kind ' + HOLD + ': one launch kind per value R')
     ap.add_argument('--label', default='this build', help='with --ensemble: names the build in the report')
     ap.add_argument('--append', action='store_true', help='with --ensemble: add to --out instead of replacing it')
-    ap.add_argument('--out', default=str(ROOT / 'profiles' / 'closed_loop_dyn_curve_N25.txt'))
+    ap.add_argument('--model', choices=('dynamic', 'point-mass'), default='dynamic',
+                    help="the game: BASELINE configs[1] (dynamic bicycles, N = 25), or the race demo's point-mass game on its circuit (N = 20)")
+    ap.add_argument('--out', default=None, help='default: profiles/closed_loop_<game>.txt')
     args = ap.parse_args()
-    from dgsqp_amd.montecarlo import dynamic_racing_game
+    from dgsqp_amd.montecarlo import dynamic_racing_game, point_mass_racing_game
     from dgsqp_amd.solver import DGSQP
-    g = dynamic_racing_game(N=25, rk4_substeps=10)               # BASELINE configs[1]
+    if args.model == 'point-mass':
+        g, game_name = point_mass_racing_game('barc', N=20), 'pm_barc_N20 (scripts/race/game_setup_unicycle.py)'
+    else:
+        g, game_name = dynamic_racing_game(N=25, rk4_substeps=10), 'dyn_curve_N25 (BASELINE configs[1])'
+    if args.out is None:
+        args.out = str(ROOT / 'profiles' / f'closed_loop_{game_name.split()[0]}.txt')
     s = DGSQP(*g.solver_args(), print_method=None, qp_method='active_set')
     B, T = args.batch, args.steps
     smp = s.sample_batch(g, B, seed=args.seed)
@@ -196,7 +203,7 @@ def main():
             dt, c = timed(run_c); tc.append(dt); kc.append(c['kernel_ms'] / 1e3)
     st = b['status']
     fmt = lambda v: f'median {np.median(v) * 1e3:.1f} ms (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f})'
-    lines = [f'closed loop, dyn_curve_N25 (BASELINE configs[1]), B = {B} chains x T = {T} steps, no disturbance, device-sampled inputs (seed {args.seed}); {args.repeats} alternated repeats after one warm-up each',
+    lines = [f'closed loop, {game_name}, B = {B} chains x T = {T} steps, no disturbance, device-sampled inputs (seed {args.seed}); {args.repeats} alternated repeats after one warm-up each',
              f'(a) host loop: {T} x solve_batch (cooperative line search + deferral) + numpy feedback + re-upload: wall {fmt(ta)}; kernels alone {fmt(ka)}',
              f'(b) step_batch: one launch of dg_closed_loop_kernel:                                               wall {fmt(tb)}; kernel alone {fmt(kb)}',
              f'(b) / (a), medians of the wall times: {np.median(tb) / np.median(ta):.3f}   ((a) / (b) = {np.median(ta) / np.median(tb):.3f})',

@@ -11,7 +11,7 @@ the rollout.  This tool writes the rollout, the costs and the rows as plain mpma
 with 60 digits and h = 1e-20 (first derivatives good to ~1e-40, second to ~1e-20).  No dynamic programming, no Taylor arithmetic, no
 adjoints, no A/B/E/F/G tensors: nothing is shared with oracle/ or dgsqp_amd/csrc except the reference's text --
 
-    continuous dynamics   dynamics_models.py:331-339 (unicycle), :1046-1070 (kinematic bicycle), :2013-2062 (dynamic bicycle; Pacejka
+    continuous dynamics   dynamics_models.py:331-339 (unicycle), :536-541 (Frenet point mass), :1046-1070 (kinematic bicycle), :2013-2062 (dynamic bicycle; Pacejka
                           and linear tyres, simple slip angle, rear-wheel drive), ca_abs :228-234, ca_sign :236-238
     discretisation        :88-99 euler, :188-219 rk4 / rk3 / rk2 with M substeps of h = dt / M
     track                 radius_arclength_track.py:361-408 (key points), :199-225 (curvature pw_const, tangent pw_lin) as a true
@@ -129,6 +129,19 @@ def fc_uni(p, tr, q, u, mg):            # dynamics_models.py:331-339
     return [v * mp.cos(psi), v * mp.sin(psi), u[0] / F(p['mass']), u[1]]
 
 
+def fc_pm(p, tr, q, u, mg):             # dynamics_models.py:536-541 (mass and damping_coefficient: all the class reads there)
+    x, y, v, epsi, s, xtran = q
+    Fx, wz = u
+    c, psi_t = track_fn(tr, s, mg)
+    dx = v * mp.cos(psi_t + epsi)
+    dy = v * mp.sin(psi_t + epsi)
+    dv = (Fx - F(p['damping_coefficient']) * v) / F(p['mass'])
+    depsi = wz - c * (v * mp.cos(epsi)) / (1 - xtran * c)
+    ds = v * mp.cos(epsi) / (1 - xtran * c)
+    dxtran = v * mp.sin(epsi)
+    return [dx, dy, dv, depsi, ds, dxtran]
+
+
 def fc_kin(p, tr, q, u, mg):            # dynamics_models.py:1046-1070
     x, y, v, epsi, s, xtran = q
     a, gamma = u
@@ -179,11 +192,12 @@ def fc_dyn(p, tr, q, u, mg):            # dynamics_models.py:2013-2062
             ax + psidot * vy, ay - psidot * vx, alphaz, psidot - c * vlon / den, vlon / den, vx * mp.sin(epsi) + vy * mp.cos(epsi)]
 
 
-FC = {'uni': fc_uni, 'kin': fc_kin, 'dyn': fc_dyn}
-NQ = {'uni': 4, 'kin': 6, 'dyn': 8}
-S_IDX = {'kin': 4, 'dyn': 6}            # s; e_y is the state after it
+FC = {'uni': fc_uni, 'kin': fc_kin, 'dyn': fc_dyn, 'pm': fc_pm}
+NQ = {'uni': 4, 'kin': 6, 'dyn': 8, 'pm': 6}
+S_IDX = {'kin': 4, 'dyn': 6, 'pm': 4}   # s; e_y (x_tran) is the state after it
 VEHICLE_KEYS = {
     'uni': ['mass'],
+    'pm': ['mass', 'damping_coefficient'],
     'kin': ['wheel_dist_front', 'wheel_dist_rear', 'mass', 'drag_coefficient', 'damping_coefficient', 'slip_coefficient', 'rolling_resistance',
             'rolling_resistance_exponent'],
     'dyn': ['wheel_dist_front', 'wheel_dist_rear', 'mass', 'yaw_inertia', 'gravity', 'drag_coefficient', 'damping_coefficient', 'rolling_resistance',
@@ -529,7 +543,7 @@ def reference_defaults(ref_dir):
     try:
         from DGSQP.dynamics.model_types import DynamicBicycleConfig, KinematicBicycleConfig, UnicycleConfig
         assert pathlib.Path(sys.modules['DGSQP.dynamics.model_types'].__file__).resolve().is_relative_to(pathlib.Path(ref_dir).resolve())
-        cfgs = {'kin': KinematicBicycleConfig, 'dyn': DynamicBicycleConfig, 'uni': UnicycleConfig}
+        cfgs = {'kin': KinematicBicycleConfig, 'dyn': DynamicBicycleConfig, 'uni': UnicycleConfig, 'pm': UnicycleConfig}
         return {kind: (lambda cls, keys: (lambda **over: {k: getattr(cls(**over), k) for k in keys}))(cfgs[kind], VEHICLE_KEYS[kind]) for kind in cfgs}
     finally:
         sys.path.remove(str(ref_dir))
@@ -567,6 +581,27 @@ def dynamic_game(defaults, N, method='rk4', substeps=10, **over):
                                             pacejka_b_front=5.0, pacejka_b_rear=5.0, pacejka_c_front=2.28, pacejka_c_rear=2.28), **over})
     return dict(M=2, N=N, dt=0.1, method=method, substeps=substeps, track=curve_track(), obstacle_rows=True,
                 agents=[bicycle_agent('dyn', veh(), racing_cost((1.0, 5.0), 'linear'), None, 0.23) for _ in range(2)])
+
+
+def point_mass_agent(vehicle, cost, rate, radius=0.21, half_width=1.0):
+    """game_setup_unicycle.py:66-94: |Fx| <= 2, |wz| <= 2, |x_tran| <= half width - 0.1, no other state bound; radii :106-107."""
+    st_ub, st_lb = [INF] * 6, [-INF] * 6
+    st_ub[5], st_lb[5] = half_width - 0.1, -(half_width - 0.1)
+    return dict(model='pm', vehicle=vehicle, cost=cost, rate=rate, lanes=[], in_ub=(2.0, 2.0), in_lb=(-2.0, -2.0), st_ub=st_ub, st_lb=st_lb,
+                radius=radius)
+
+
+def point_mass_cost(**over):            # game_setup_unicycle.py:99-104, :154-166: 1/2 0.1 |u|^2 per stage (no rate term), -1 s + 5 atan(ds) at the end
+    return {**dict(kind='racing', input_weight=(0.1, 0.1), input_rate_weight=(0.0, 0.0), comp_weights=(1.0, 5.0), comp_type='atan',
+                   blocking_weight=0.0, obs_weight=0.0, obs_r=0.3), **over}
+
+
+def point_mass_game(defaults, track, N, M=2, method='euler', substeps=1, cost=point_mass_cost, rate=None, **vehicle):
+    """game_setup_unicycle.py: vehicle :35-55 (drag, damping, rolling resistance 0), euler with dt 0.1 :21, :34, collision rows at stages
+    1..N :246-252, no rate rows :213, :229 -- on a Monte-Carlo track of half width 1."""
+    veh = lambda: defaults['pm'](**{**dict(damping_coefficient=0), **vehicle})
+    return dict(M=M, N=N, dt=0.1, method=method, substeps=substeps, track=track, obstacle_rows=True,
+                agents=[point_mass_agent(veh(), cost(), rate) for _ in range(M)])
 
 
 def merge_game_spec(defaults, N, M=3):
@@ -655,6 +690,7 @@ def case_inputs(case, defaults, shift=0):
     sys.path.insert(0, str(ROOT / 'tests'))
     sys.path.insert(0, str(ROOT))
     import multistage_kat as mk
+    import point_mass_kat as pk
     if case.endswith(UPREV):
         # the parent's game and scenarios, and a u_prev per scenario drawn inside the input box (its inner 90 %)
         spec, x0, u, l, vs, checks, _ = case_inputs(case[:-len(UPREV)], defaults, shift)
@@ -663,7 +699,7 @@ def case_inputs(case, defaults, shift=0):
         assert np.isfinite(lb).all() and np.isfinite(ub).all(), 'a *_uprev case needs a finite input box'
         mid, half = 0.5 * (lb + ub), 0.45 * (ub - lb)
         return spec, x0, u, l, vs, checks, mid + half * rng.uniform(-1.0, 1.0, (len(x0), len(lb)))
-    game = mk.build_game(case)
+    game = (pk if case in pk.CASES else mk).build_game(case)
     vs, checks = (), (lambda x: None)
     if case == 'kin2_euler_N3':
         spec = kinematic_game(defaults, curve_track(), 3)
@@ -721,6 +757,41 @@ def case_inputs(case, defaults, shift=0):
         spec = kinematic_game(defaults, curve_track(), N, M=3)
         x0, u, l = draw(case, game, 2, 16 + 100 * shift, n_rows(spec))
         vs = tuple(np.random.default_rng(99).standard_normal((2, 2 * 3 * N)))
+    elif case == 'pm2_euler_N3':
+        spec = point_mass_game(defaults, curve_track(), 3)
+        x0, u, l = draw(case, game, 3, 21 + 100 * shift, n_rows(spec))
+        x0[0, 4] = 0.9                                        # car 1 crosses the segment boundary s = 1 between stages 0 and 1
+
+        def checks(x):
+            assert x[0, 0, 4] < 1.0 < x[0, 1, 4], x[0, :2, 4]
+    elif case == 'pm2_rk4_N4':
+        cost = lambda: point_mass_cost(input_rate_weight=(0.3, 0.2), comp_type='linear', blocking_weight=0.7, obs_weight=3.0, obs_r=0.9)
+        spec = point_mass_game(defaults, chicane_track(), 4, method='rk4', substeps=2, cost=cost, rate=((10.0, 4.5), (-10.0, -4.5)),
+                               damping_coefficient=0.3, mass=1.9)
+        x0, u, l = draw(case, game, 3, 22 + 100 * shift, n_rows(spec))
+        x0[1, 4] += 4.6; x0[1, 6 + 4] += 4.6                  # scenario 1: out of curve 1 (c < 0) over the mid straight ...
+        x0[2, 4] += 5.4; x0[2, 6 + 4] += 5.4                  # scenario 2: ... into curve 2 (c > 0)
+
+        def checks(x):
+            tr = spec['track']
+            curv = lambda s: tr['seg_curv'][np.searchsorted(tr['seg_s'], s, side='right') - 1]
+            cs = curv(x[:, :, [4, 10]])
+            assert (cs < 0).any() and (cs > 0).any() and (cs == 0).any(), cs
+            d = np.linalg.norm(x[:, :, 0:2] - x[:, :, 6:8], axis=2)
+            assert (d < 1.8 - MARGIN).all(), d               # the hinge of the soft-obstacle cost is active
+    elif case == 'mix3_rk4m3_N3':
+        # agents (kinematic bicycle, point mass, dynamic bicycle), each with its own game's vehicle, boxes and cost, radii 0.2, on the curve track
+        kin = kinematic_game(defaults, curve_track(), 3, M=1)['agents'][0]
+        pm = point_mass_agent(defaults['pm'](damping_coefficient=0.2), point_mass_cost(), None, radius=0.2)
+        dyn = dynamic_game(defaults, 3)['agents'][0]
+        dyn['radius'] = 0.2
+        spec = dict(M=3, N=3, dt=0.1, method='rk4', substeps=3, track=curve_track(), obstacle_rows=True, agents=[kin, pm, dyn])
+        x0, u, l = draw(case, game, 2, 23 + 100 * shift, n_rows(spec))
+    elif case in ('pm3_N20_dir', 'pm3_N25_dir'):
+        N = {'pm3_N20_dir': 20, 'pm3_N25_dir': 25}[case]
+        spec = point_mass_game(defaults, curve_track(), N, M=3)
+        x0, u, l = draw(case, game, 2, 24 + 100 * shift, n_rows(spec))
+        vs = tuple(np.random.default_rng(98).standard_normal((2, 2 * 3 * N)))
     else:
         raise ValueError(case)
     return spec, x0, u, l, vs, checks, None
@@ -731,7 +802,8 @@ def case_inputs(case, defaults, shift=0):
 DIGITS = {'uni3_merge_N3': 70}
 UPREV = '_uprev'      # <parent>_uprev: the parent's scenarios with a non-zero input before stage 0, stored as ``u_prev``
 CASES = ('kin2_euler_N3', 'kin2_rk4_N4', 'kin3_euler_N3', 'dyn2_rk4m3_N3', 'dyn2_rk4m10_N2', 'dyn2_rk3_N3', 'dyn2_rk2_lin_N3', 'uni3_merge_N3',
-         'kin3_N20_dir', 'kin3_N25_dir', 'kin2_rk4_N4' + UPREV, 'dyn2_rk4m3_N3' + UPREV)
+         'kin3_N20_dir', 'kin3_N25_dir', 'kin2_rk4_N4' + UPREV, 'dyn2_rk4m3_N3' + UPREV,
+         'pm2_euler_N3', 'pm2_rk4_N4', 'mix3_rk4m3_N3', 'pm3_N20_dir', 'pm3_N25_dir')
 
 
 def main():
