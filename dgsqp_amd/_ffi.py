@@ -100,7 +100,7 @@ class DriversT(C.Structure):
     _fields_ = [('kind', C.c_int32 * MAX_AGENTS), ('pid', PidT * MAX_AGENTS)]
 
 
-DRIVER_GAME, DRIVER_PID, DRIVER_REPLAY = 0, 1, 2        # DGSQP_DRIVER_*
+DRIVER_GAME, DRIVER_PID, DRIVER_REPLAY, DRIVER_TRACK = 0, 1, 2, 3        # DGSQP_DRIVER_*
 
 
 class HoldT(C.Structure):
@@ -156,6 +156,9 @@ SIGNATURES = {
     'dgsqp_fetch_u_cmd': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_set_plan_hold': (C.c_int, [_H, C.POINTER(HoldT)]),
     'dgsqp_fetch_plan_hold': (C.c_int, [_H, _PD, _PI, C.c_int64]),
+    'dgsqp_set_cross_plant': (C.c_int, [_H, C.POINTER(PlantT), C.c_int64, _PD]),
+    'dgsqp_fetch_plant_state': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_fetch_track_ref': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_set_u_prev': (C.c_int, [_H, C.c_int64, _PD]),
     'dgsqp_set_closed_loop_u_prev': (C.c_int, [_H, C.c_int, C.c_int64, _PD]),
     'dgsqp_fetch_u_prev': (C.c_int, [_H, _PD, C.c_int64]),

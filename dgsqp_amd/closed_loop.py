@@ -23,7 +23,11 @@ A launch may carry the command of step t into solve t + 1 as the input before it
 ``dgsqp_set_closed_loop_u_prev``): ``next_u_prev`` is the mirror of that rule.
 
 A launch with a plant may hold a plan across control steps (``PlanHold``, ``dgsqp_set_plan_hold``): a planning rate below the control
-rate, and the next stage of the last accepted plan as the command after a failed solve.  ``hold_step`` is the mirror of that rule."""
+rate, and the next stage of the last accepted plan as the command after a failed solve.  ``hold_step`` is the mirror of that rule.
+
+A plant may be of ANOTHER model class than the game's agent (``PlantModel(own_class=True)``, ``dgsqp_set_cross_plant``): it keeps a state
+``z`` of its own and the game sees the projection ``project_state`` of it; ``lift_state`` is the default ``z0``.  A 'track' driver follows
+the game's plan on such a plant: ``track_reference`` is the reference it steers towards, ``drive`` / ``pid_driver_step`` the law."""
 from __future__ import annotations
 
 import ctypes as C
@@ -86,6 +90,62 @@ def config_model_id(config, game_model: Optional[int] = None) -> int:
     return 3 if game_model == 3 else 2
 
 
+MODEL_NQ = {0: 6, 1: 8, 2: 4, 3: 6}     # states per model class (dg_model_nq)
+SIX_OF_EIGHT = (0, 1, 2, 5, 6, 7)       # [x, y, v, e_psi, s, e_y] of [x, y, vx, vy, w, e_psi, s, e_y]
+CROSS_PAIRS = ((0, 1), (3, 0), (3, 1))  # (game class, plant class) besides the same class: the table in include/dgsqp.h
+
+
+def cross_projection(game_class: int, plant_class: int) -> tuple:
+    """Which entries of a plant agent's state block the game's agent sees; ``ValueError`` for a pair outside the table."""
+    g, p = int(game_class), int(plant_class)
+    if g not in MODEL_NQ or p not in MODEL_NQ or (g != p and (g, p) not in CROSS_PAIRS):
+        raise ValueError(f'a game agent of model class {g} on a plant of class {p} is not a supported pair (same class, 0 -> 1, 3 -> 0, 3 -> 1)')
+    return SIX_OF_EIGHT if MODEL_NQ[p] == 8 and MODEL_NQ[g] == 6 else tuple(range(MODEL_NQ[g]))
+
+
+def _blocks(classes):
+    return np.concatenate(([0], np.cumsum([MODEL_NQ[int(c)] for c in classes])))
+
+
+def project_state(game_classes, plant_classes, z) -> np.ndarray:
+    """``q = p(z)``: ``z`` [..., n_z] (the plant agents' blocks, agent after agent) -> [..., n_q] in the game's layout.  Data movement."""
+    z = np.asarray(z, dtype=np.float64)
+    zoff = _blocks(plant_classes)
+    if len(game_classes) != len(plant_classes) or z.shape[-1] != zoff[-1]:
+        raise ValueError(f'z has {z.shape[-1]} entries per chain, the plant classes {list(plant_classes)} have {zoff[-1]}')
+    return np.concatenate([z[..., [zoff[a] + i for i in cross_projection(g, p)]] for a, (g, p) in enumerate(zip(game_classes, plant_classes))], axis=-1)
+
+
+def lift_state(game_classes, plant_classes, x0) -> np.ndarray:
+    """A plant state whose projection is ``x0`` [..., n_q]: the entries the game does not see (vy, w) are zero."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    qoff, zoff = _blocks(game_classes), _blocks(plant_classes)
+    if len(game_classes) != len(plant_classes) or x0.shape[-1] != qoff[-1]:
+        raise ValueError(f'x0 has {x0.shape[-1]} entries per chain, the game classes {list(game_classes)} have {qoff[-1]}')
+    z = np.zeros(x0.shape[:-1] + (int(zoff[-1]),))
+    for a, (g, p) in enumerate(zip(game_classes, plant_classes)):
+        z[..., [zoff[a] + i for i in cross_projection(g, p)]] = x0[..., qoff[a]:qoff[a + 1]]
+    return z
+
+
+def track_reference(model, q_agent, g, method: Optional[str] = None, dt: Optional[float] = None, M: Optional[int] = None) -> np.ndarray:
+    """The state a 'track' driver steers towards: one step of the discrete model of the GAME's agent (``model``: a numpy model of
+    ``dynamics``) from ``q_agent`` -- the projection of the plant agent's true state -- under the game's command ``g``.  ``method``, ``dt``
+    and ``M`` are the joint model's (a game discretises every agent with them); by default the model's own, and the result is then
+    ``model.fd(q_agent, g)`` where the model has one.  The references are entries 2 (v), last (lateral) and e_psi of the result."""
+    from .dynamics import CasadiKinematicUnicycle
+    if method is None and dt is None and M is None:
+        return np.asarray(CasadiKinematicUnicycle.fd(model, q_agent, g), dtype=np.float64)
+    import copy
+    m = copy.copy(model)
+    m.model_config = copy.copy(model.model_config)
+    if method is not None:
+        m.model_config.discretization_method = method
+    m.dt = float(model.dt if dt is None else dt)
+    m.M = int(model.M if M is None else M)
+    return np.asarray(CasadiKinematicUnicycle.fd(m, q_agent, g), dtype=np.float64)
+
+
 @dataclass
 class PlantModel:
     """The plant of ``DGSQP.step_batch(..., plant=...)``: same model class, state layout and track as the game's agents, but its own
@@ -100,7 +160,10 @@ class PlantModel:
     A plant PER CHAIN (``dgsqp_set_plant_ensemble``; ``perturbed_configs`` draws one): ``per_chain_configs`` [B][M], chain b's vehicles,
     and ``per_chain_delay_steps`` [B][M][2] (or ``per_chain_delay`` in seconds, converted as ``delay``), chain b's delays; B must be the
     batch size of the call.  Method, ``M`` and ``sim_steps`` are shared by all chains.  With per-chain delays alone every chain keeps
-    the vehicles of ``dynamics_configs`` (or the game's)."""
+    the vehicles of ``dynamics_configs`` (or the game's).
+
+    ``own_class=True``: the configs may be of ANOTHER model class than the game's agents (``dgsqp_set_cross_plant``; the pairs of
+    ``cross_projection``): the plant then keeps a state of its own, ``step_batch`` takes ``z0`` and returns ``z``."""
     dynamics_configs: Optional[Sequence] = None
     method: Optional[str] = None
     M: Optional[int] = None
@@ -110,6 +173,14 @@ class PlantModel:
     per_chain_configs: Optional[Sequence] = None
     per_chain_delay_steps: Optional[Sequence] = None
     per_chain_delay: Optional[Sequence] = None
+    own_class: bool = False
+
+    def plant_classes(self, problem: _ffi.ProblemT) -> list:
+        """The model class of each plant agent: its config's, or the game's where there is none."""
+        game = [int(problem.agents[a].model) for a in range(int(problem.M))]
+        if self.dynamics_configs is None:
+            return game
+        return [config_model_id(c, g) for c, g in zip(self.dynamics_configs, game)]
 
     def _delay_steps(self, steps, seconds, shape: tuple, dt: float, what: str) -> np.ndarray:
         if steps is not None and seconds is not None:
@@ -144,13 +215,16 @@ class PlantModel:
         if int(self.sim_steps) != self.sim_steps or self.sim_steps < 1:
             raise ValueError(f'sim_steps must be a whole number >= 1, got {self.sim_steps}')
         vehicles = (_ffi.VehicleT * (B * n_agents))()
+        classes = self.plant_classes(problem) if self.own_class else None
         if self.per_chain_configs is not None:
             if len(self.per_chain_configs) != B or any(len(row) != n_agents for row in self.per_chain_configs):
                 raise ValueError(f'per_chain_configs must be [B][M] = [{B}][{n_agents}] configs')
             for b, row in enumerate(self.per_chain_configs):
                 for a, cfg in enumerate(row):
                     mid = config_model_id(cfg, problem.agents[a].model)
-                    if mid != problem.agents[a].model:
+                    if self.own_class and mid != classes[a]:
+                        raise ValueError(f'per-chain plant config [{b}][{a}] is of model class {mid}, the plant\'s agent is of class {classes[a]}')
+                    if not self.own_class and mid != problem.agents[a].model:
                         raise ValueError(f'per-chain plant config [{b}][{a}] is of model class {mid}, the game\'s agent is of '
                                          f'class {problem.agents[a].model}: a plant keeps the game\'s model class and state layout')
                     fill_vehicle(vehicles[b * n_agents + a], mid, cfg)
@@ -171,7 +245,8 @@ class PlantModel:
         return vehicles, delay
 
     def lower(self, problem: _ffi.ProblemT) -> _ffi.PlantT:
-        """``dgsqp_plant_t`` for the game ``problem`` (host only); ``ValueError`` for what the library would refuse."""
+        """``dgsqp_plant_t`` for the game ``problem`` (host only) -- with ``own_class`` what ``dgsqp_set_cross_plant`` takes --; ``ValueError``
+        for what the library would refuse."""
         from .solver import fill_vehicle
         n_agents = int(problem.M)
         if int(self.sim_steps) != self.sim_steps or self.sim_steps < 1:
@@ -196,7 +271,9 @@ class PlantModel:
                 raise ValueError(f'Number of agents: {n_agents}, but {len(self.dynamics_configs)} plant configs were provided')
             for a, cfg in enumerate(self.dynamics_configs):
                 mid = config_model_id(cfg, problem.agents[a].model)
-                if mid != problem.agents[a].model:
+                if self.own_class:
+                    cross_projection(problem.agents[a].model, mid)
+                elif mid != problem.agents[a].model:
                     raise ValueError(f'plant config {a} is of model class {mid}, the game\'s agent is of class '
                                      f'{problem.agents[a].model}: a plant keeps the game\'s model class and state layout')
                 fill_vehicle(pt.agents[a], mid, cfg)
@@ -299,7 +376,7 @@ def monitor(z: np.ndarray, radii, st_lb, st_ub, qoff):
     return np.where(bad, np.nan, clearance), np.where(bad, np.nan, box), first
 
 
-DRIVER_KINDS = {'game': _ffi.DRIVER_GAME, 'pid': _ffi.DRIVER_PID, 'replay': _ffi.DRIVER_REPLAY}
+DRIVER_KINDS = {'game': _ffi.DRIVER_GAME, 'pid': _ffi.DRIVER_PID, 'replay': _ffi.DRIVER_REPLAY, 'track': _ffi.DRIVER_TRACK}
 UNICYCLE = 2                    # DGSQP_MODEL_UNICYCLE: no e_y / e_psi, so no lane follower
 
 
@@ -326,10 +403,10 @@ class PidGains:
 def _kind_id(k) -> int:
     if isinstance(k, str):
         if k not in DRIVER_KINDS:
-            raise ValueError(f"driver kind {k!r} not recognized: 'game', 'pid' or 'replay'")
+            raise ValueError(f"driver kind {k!r} not recognized: 'game', 'pid', 'replay' or 'track'")
         return DRIVER_KINDS[k]
     if int(k) != k or int(k) not in DRIVER_KINDS.values():
-        raise ValueError(f'driver kind {k!r} not recognized: 0 (game), 1 (pid) or 2 (replay)')
+        raise ValueError(f'driver kind {k!r} not recognized: 0 (game), 1 (pid), 2 (replay) or 3 (track)')
     return int(k)
 
 
@@ -338,7 +415,8 @@ class Drivers:
     """Who produces the command that enters each agent's plant in ``DGSQP.step_batch(..., drivers=...)`` (``dgsqp_set_drivers``):
 
     * ``kinds`` [M]: 'game' (stage 0 of the game's solution, as without drivers), 'pid' (the lane follower ``pid`` run closed-loop on the
-      TRUE state; 6- and 8-state models only) or 'replay' (``u_replay``), or the numbers 0, 1, 2;
+      TRUE state; 6- and 8-state models only), 'replay' (``u_replay``) or 'track' (the lane follower towards ``track_reference`` of the game's
+      command; only with ``PlantModel(own_class=True)``), or the numbers 0 .. 3;
     * ``pid``: one ``PidGains`` for all agents or one per agent (default: ``PidGains()``);
     * ``per_chain_kinds`` [B][M]: the kinds of every chain, in place of ``kinds``;
     * ``refs`` [B][M][2]: (v_ref, lat_ref) of the PID agents per chain; None: (v, e_y) of the chain's x0, as the warm-start PID does;
@@ -361,8 +439,9 @@ class Drivers:
             raise ValueError(f'pid must be one PidGains or one per agent ({n_agents})')
         return list(self.pid)
 
-    def lower(self, problem: _ffi.ProblemT, B: int, T: int):
-        """``(drivers, kind, ref, u_replay)`` for ``dgsqp_set_drivers`` with a launch of ``B`` chains and ``T`` steps: a ``DriversT``, an
+    def lower(self, problem: _ffi.ProblemT, B: int, T: int, plant_classes=None):
+        """``plant_classes``: the classes of a cross plant's agents (``PlantModel.plant_classes``), None without one.
+        ``(drivers, kind, ref, u_replay)`` for ``dgsqp_set_drivers`` with a launch of ``B`` chains and ``T`` steps: a ``DriversT``, an
         int32 array [B, M] or None, a float64 array [B, M, 2] or None and a float64 array [T, B, n_u] (step-major, as the library takes
         it) or None (host only); ``ValueError`` for what the library would refuse."""
         M = int(problem.M)
@@ -383,6 +462,14 @@ class Drivers:
         for a in range(M):
             if (every[:, a] == _ffi.DRIVER_PID).any() and problem.agents[a].model == UNICYCLE:
                 raise ValueError(f'PID driver for agent {a}, a unicycle: the lane follower needs e_y and e_psi (the 6- and 8-state models)')
+            if (every[:, a] == _ffi.DRIVER_TRACK).any():
+                if plant_classes is None:
+                    raise ValueError(f"driver kind 'track' (3) of agent {a} not recognized without a plant of its own class: PlantModel(own_class=True)")
+                if problem.agents[a].model == UNICYCLE:
+                    raise ValueError(f"'track' driver for agent {a}, a unicycle: the lane follower needs e_y and e_psi (the 6- and 8-state models)")
+            if plant_classes is not None and problem.agents[a].model == 3 and plant_classes[a] != 3 and (every[1 if per_chain is not None else 0:, a] == _ffi.DRIVER_GAME).any():
+                raise ValueError(f"drivers: agent {a} is a point mass (inputs Fx, wz) on a bicycle plant (acceleration, steering): a 'game' driver "
+                                 "cannot command it; use 'track', 'pid' or 'replay'")
         ref = None
         if self.refs is not None:
             ref = np.ascontiguousarray(self.refs, dtype=np.float64)
@@ -408,15 +495,18 @@ def new_pid_state(lead=()) -> np.ndarray:
     return np.zeros(tuple(lead) + (3,))
 
 
-def pid_driver_step(pid: PidGains, q_agent, ref, state, dt: float):
+def pid_driver_step(pid: PidGains, q_agent, ref, state, dt: float, epsi_ref: float = 0.0):
     """One control step of the PID driver for one agent -- the host mirror of ``dev_pid_law``: the operations of ``pid.PID.solve`` in its
     order, with Kd = 0, symmetric limits and u_ref = 0.  ``q_agent`` [n_qa] the agent's TRUE state (6- or 8-state model: v at 2, e_psi at 3
     or 5, e_y last), ``ref`` (v_ref, lat_ref), ``state`` [3] (integrator, previous u_a, previous u_steer), ``dt`` the control step.
+    ``epsi_ref`` (a 'track' driver's): the law sees ``e_psi - epsi_ref`` in place of ``e_psi``.
     Returns ``(u [2], state [3])``; ``state`` itself is not changed."""
     q_agent = np.asarray(q_agent, dtype=np.float64)
     if q_agent.shape[-1] not in (6, 8):
         raise ValueError(f'the lane follower needs e_y and e_psi: a 6- or 8-state agent, got {q_agent.shape[-1]} states')
     v, epsi, ey = float(q_agent[2]), float(q_agent[5 if q_agent.shape[-1] == 8 else 3]), float(q_agent[-1])
+    if epsi_ref:
+        epsi = epsi - float(epsi_ref)
     ei, up0, up1 = (float(x) for x in state)
     ua = -(pid.kp_v * (v - float(ref[0])))
     e = pid.ey_gain * (ey - float(ref[1])) + epsi
@@ -427,11 +517,14 @@ def pid_driver_step(pid: PidGains, q_agent, ref, state, dt: float):
     return np.array([ua, us]), np.array([ei, ua, us])
 
 
-def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None):
+def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None, track_refs=None):
     """The commands of one control step of one chain -- the host mirror of the drivers overload of ``dev_plant_feedback``.  Per agent a:
     kind 0 takes ``u_game[2a:2a+2]`` (stage 0 of the solution), kind 1 ``pid_driver_step(gains[a], q[qoff[a]:qoff[a+1]], refs[a],
     states[a], dt)``, kind 2 ``u_replay[2a:2a+2]``.  ``kinds`` [M], ``u_game`` [n_u], ``q`` [n_q] the TRUE state, ``refs`` [M, 2],
-    ``states`` [M, 3].  Returns ``(u_cmd [n_u], states [M, 3])``; only PID agents' states change (in the returned copy)."""
+    ``states`` [M, 3].  With a cross plant ``q`` is the PLANT's state z and ``qoff`` its blocks; kind 3 ('track') is
+    ``pid_driver_step(gains[a], z_a, track_refs[a][:2], states[a], dt, epsi_ref=track_refs[a][2])`` with ``track_refs`` [M, 3] =
+    (v_ref, lat_ref, epsi_ref) from ``track_reference``.  Returns ``(u_cmd [n_u], states [M, 3])``; only PID and track agents' states
+    change (in the returned copy)."""
     u_game = np.asarray(u_game, dtype=np.float64)
     q = np.asarray(q, dtype=np.float64)
     states = np.array(states, dtype=np.float64)
@@ -440,6 +533,11 @@ def drive(kinds, u_game, q, gains, refs, states, dt: float, qoff, u_replay=None)
         k = _kind_id(k)
         if k == _ffi.DRIVER_PID:
             u_cmd[NUA * a:NUA * a + NUA], states[a] = pid_driver_step(gains[a], q[qoff[a]:qoff[a + 1]], refs[a], states[a], dt)
+        elif k == _ffi.DRIVER_TRACK:
+            if track_refs is None:
+                raise ValueError("driver kind 'track' (3) not recognized without track_refs (closed_loop.track_reference of the game's command)")
+            r = np.asarray(track_refs, dtype=np.float64)[a]
+            u_cmd[NUA * a:NUA * a + NUA], states[a] = pid_driver_step(gains[a], q[qoff[a]:qoff[a + 1]], r[:2], states[a], dt, epsi_ref=r[2])
         elif k == _ffi.DRIVER_REPLAY:
             if u_replay is None:
                 raise ValueError("a 'replay' driver needs u_replay")
@@ -524,14 +622,20 @@ def hold_step(status, u_t, u_ws_t, age: int, due: bool, hold: PlanHold, N: int, 
     return stage0(u_ws_t), shift_warm_start(u_ws_t, N, num_ua_d), new_age, bool(due) if failed else new_age >= R, int(age)
 
 
-def next_u_prev(u_t_stage0, u_cmd=None) -> np.ndarray:
+def next_u_prev(u_t_stage0, u_cmd=None, kinds=None) -> np.ndarray:
     """The input a chain's next solve takes as applied before its stage 0 (``step_batch(..., u_prev=...)``,
     ``dgsqp_set_closed_loop_u_prev``) -- the host mirror of the carry in ``dg_closed_loop_kernel``: per agent, the command that entered that
     agent's plant at this step.  ``u_t_stage0`` [..., n_u] is stage 0 of the solve's solution as returned (``u_applied``; also after
     'diverged' / 'qp_fail', the feedback applies it then as well); ``u_cmd`` [..., n_u] the commands of a launch with drivers (``drive``), which
     then take its place: a PID or replay agent's own command is what the game sees as that agent's previous input.  With delay lines this
-    is the value appended to the line, not the delayed one the plant integrated under.  Pure data movement: a copy."""
+    is the value appended to the line, not the delayed one the plant integrated under.  ``kinds`` [M] (with ``u_cmd``): a 'track' agent's command
+    is in the plant's units, so its entries take the GAME's command ``u_t_stage0`` (u_game).  Pure data movement: a copy."""
     src = np.asarray(u_t_stage0 if u_cmd is None else u_cmd, dtype=np.float64)
     if u_cmd is not None and src.shape != np.shape(u_t_stage0):
         raise ValueError(f'u_cmd has shape {src.shape}, stage 0 of the solution {np.shape(u_t_stage0)}')
-    return src.copy()
+    out = src.copy()
+    if u_cmd is not None and kinds is not None:
+        for a, k in enumerate(kinds):
+            if _kind_id(k) == _ffi.DRIVER_TRACK:
+                out[..., NUA * a:NUA * a + NUA] = np.asarray(u_t_stage0, dtype=np.float64)[..., NUA * a:NUA * a + NUA]
+    return out

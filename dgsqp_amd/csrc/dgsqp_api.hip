@@ -281,6 +281,7 @@ enum DgSideBuf {
   SB_U_CMD, SB_CMD, SB_PID_STATE,                             // ... u_cmd [T][B][nu]; per workgroup: [grid][n] (2 M used: read as u_t is), [grid][M][3]
   SB_U_GAME, SB_PLAN_STAGE, SB_GCMD, SB_HOLD_STATE,           // the held plan: u_game [T][B][nu], plan_stage [T][B] int32; per workgroup: [grid][n] as SB_CMD, [grid][2] int32
   SB_U_PREV,                                                  // the carried input (dgsqp_set_closed_loop_u_prev): u_prev [T][B][nu]
+  SB_X_GAME, SB_X_LIFT, SB_Z, SB_TRACK_REF,                   // the cross plant: the game as a dgsqp_plant_t; the game with bounds in the plant's layout; z [T+1][B][nz], track_ref [T][B][M][3]
   DG_SIDE_COUNT
 };
 struct DgBuf {
@@ -310,10 +311,19 @@ struct DgDriversState {
   int32_t T = 0;                      // the launch shape the arrays were given for
   int64_t B = 0;
   bool has_ref = false, has_replay = false;
+  std::vector<int32_t> kinds;         // [B][M] as uploaded (a cross-plant launch checks them against its pairs)
 };
 struct DgHoldState {
   bool set = false;
   dgsqp_hold_t host;
+};
+// a plant of another model class (dgsqp_set_cross_plant): plant.set holds as well while it is set, plant.host is its resolved record
+struct DgCrossState {
+  bool set = false;
+  int64_t B = 0;                      // chains z0 was given for
+  int mdl[DGSQP_MAX_AGENTS] = {}, nz[DGSQP_MAX_AGENTS] = {}, zoff[DGSQP_MAX_AGENTS] = {}, nz_all = 0;
+  int8_t proj[DGSQP_MAX_AGENTS][DGSQP_MAX_NQA] = {};
+  std::vector<double> z0;             // [B][nz_all]
 };
 
 // u_{-1}, the input applied before stage 0 (Ctx.up).  dgsqp_set_u_prev keeps a host copy; staging a batch captures it in a device buffer of
@@ -355,6 +365,7 @@ struct dgsqp_solver {
   DgEnsembleState ens;
   DgDriversState drv;
   DgHoldState hold;
+  DgCrossState cross;
   DgSide side;                             // ... and their device buffers
   DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
@@ -766,6 +777,9 @@ static int drivers_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
   const DgDriversState& R = h->drv;
   if (!R.set) return DGSQP_OK;
   if (!h->plant.set) return refuse(h, "drivers: ", "no plant set for this launch");
+  if (!h->cross.set)
+    for (const int32_t k : R.kinds)
+      if (k == DGSQP_DRIVER_TRACK) return refuse(h, "drivers: ", "a TRACK driver is set and no cross plant for this launch");
   if (R.T != T || R.B != B)
     return refuse(h, "drivers: ", "launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the drivers were set for T = " + std::to_string(R.T) + ", B = " + std::to_string(R.B));
   return DGSQP_OK;
@@ -854,9 +868,51 @@ static int hold_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgPlantD
   { const int rc = side_record(h, SB_PLAN_STAGE, TB, sizeof(int32_t)); if (rc) return rc; }
   DgPlantDriversHoldDev hd{};
   hd.dd = dd;
-  hd.replan_every = h->hold.host.replan_every; hd.on_fail = h->hold.host.on_fail; hd.fail_mask = h->hold.host.fail_mask;
+  // (a cross-plant launch without a hold of the caller's: R = 1 with the reference's rule, which is the launch without the setting)
+  const dgsqp_hold_t off{1, DGSQP_HOLD_REFERENCE, (1u << DGSQP_DIVERGED) | (1u << DGSQP_QP_FAIL), 0};
+  const dgsqp_hold_t& H = h->hold.set ? h->hold.host : off;
+  hd.replan_every = H.replan_every; hd.on_fail = H.on_fail; hd.fail_mask = H.fail_mask;
   hd.u_game = S.at<double>(SB_U_GAME); hd.plan_stage = S.at<int32_t>(SB_PLAN_STAGE); hd.gcmd = S.at<double>(SB_GCMD); hd.state = S.at<int32_t>(SB_HOLD_STATE);
   *out = hd;
+  return DGSQP_OK;
+}
+// The cross plant.  Before the launch: its shape, x0 = p(z0) bit for bit, no disturbance, and a GAME driver only where the game's inputs
+// mean what the plant's do.  For the launch, on top of `hd`: the z record with z0 in slice 0, and track_ref.
+static int cross_check_launch(dgsqp_solver* h, int64_t B, const double* x0, const double* w) {
+  const DgCrossState& X = h->cross;
+  const DgProb& D = h->hp;
+  if (!X.set) return DGSQP_OK;
+  if (w) return refuse(h, "cross plant: ", "a disturbance w is in the game's layout and has no place in the plant's state z: pass NULL");
+  if (B != X.B) return refuse(h, "cross plant: ", "launch of B = " + std::to_string(B) + " chains, z0 was set for " + std::to_string(X.B));
+  for (int64_t b = 0; b < B; b++)
+    for (int a = 0; a < D.M; a++)
+      for (int i = 0; i < D.nqa[a]; i++)
+        if (memcmp(&x0[b * D.nq + D.qoff[a] + i], &X.z0[b * X.nz_all + X.zoff[a] + X.proj[a][i]], sizeof(double)) != 0)
+          return refuse(h, "cross plant: ", "x0 of chain " + std::to_string(b) + ", agent " + std::to_string(a) + ", entry " + std::to_string(i) + " is not the projection of z0 (bit for bit)");
+  for (int a = 0; a < D.M; a++) {
+    if (D.mdl[a] != DGSQP_MODEL_UNICYCLE_COMBINED || X.mdl[a] == DGSQP_MODEL_UNICYCLE_COMBINED) continue;
+    for (int64_t b = 0; b < B; b++)
+      if (!h->drv.set || h->drv.kinds[(size_t)b * D.M + a] == DGSQP_DRIVER_GAME)
+        return refuse(h, "drivers: ", "agent " + std::to_string(a) + " is a point mass (inputs Fx, wz) on a bicycle plant (acceleration, steering): a GAME driver cannot command it" +
+                      (h->drv.set ? " (chain " + std::to_string(b) + ")" : " (no drivers set: every agent is GAME)") + "; use TRACK, PID or REPLAY");
+  }
+  return DGSQP_OK;
+}
+static int cross_for_launch(dgsqp_solver* h, int64_t B, int32_t T, const DgPlantDriversHoldDev& hd, DgCrossPlantDev* out) {
+  const DgCrossState& X = h->cross;
+  DgSide& S = h->side;
+  S.left[SB_Z] = S.left[SB_TRACK_REF] = 0;
+  { const int rc = side_record(h, SB_Z, ((int64_t)T + 1) * B * X.nz_all, sizeof(double)); if (rc) return rc; }
+  { const int rc = side_record(h, SB_TRACK_REF, (int64_t)T * B * h->hp.M * 3, sizeof(double)); if (rc) return rc; }
+  HIPCHK(h, hipMemcpyAsync(S.b[SB_Z].p, X.z0.data(), sizeof(double) * X.z0.size(), hipMemcpyHostToDevice, h->stream));
+  DgCrossPlantDev xp{};
+  xp.hd = hd;
+  for (int a = 0; a < DGSQP_MAX_AGENTS; a++) { xp.mdl[a] = X.mdl[a]; xp.nz[a] = X.nz[a]; xp.zoff[a] = X.zoff[a]; }
+  xp.nz_all = X.nz_all;
+  memcpy(xp.proj, X.proj, sizeof(xp.proj));
+  xp.lift = S.at<const dgsqp_problem_t>(SB_X_LIFT); xp.game = S.at<const dgsqp_plant_t>(SB_X_GAME);
+  xp.z = S.at<double>(SB_Z); xp.track_ref = S.at<double>(SB_TRACK_REF);
+  *out = xp;
   return DGSQP_OK;
 }
 // the one launch of dg_closed_loop_kernel, instantiated for the argument pack the settings call for (none: no plant)
@@ -959,7 +1015,8 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
   const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
                            (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>, (const void*)dg_closed_loop_kernel<DgPlantDriversHoldDev>};
+                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>, (const void*)dg_closed_loop_kernel<DgPlantDriversHoldDev>,
+                           (const void*)dg_closed_loop_kernel<DgCrossPlantDev>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -1333,6 +1390,7 @@ int dgsqp_solve_batch(dgsqp_handle_t h, int64_t B, const double* x0, const doubl
 int dgsqp_set_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant) {
   { const int rc = setter_begin(h); if (rc) return rc; }
   DgPlantState& S = h->plant;
+  if (h->cross.set) { h->cross.set = false; S.set = false; }      // (a cross plant's record is not a plant of the game's class)
   if (!plant) { S.set = false; return DGSQP_OK; }
   auto bad = [&](const std::string& m) { return refuse(h, "plant: ", m); };
   const int integ = plant->integrator;
@@ -1356,6 +1414,69 @@ int dgsqp_fetch_u_plant(dgsqp_handle_t h, double* out, int64_t capacity_doubles)
   return h ? side_fetch(h, {{SB_U_PLANT, out, sizeof(double)}}, none, none, "u_plant", capacity_doubles) : DGSQP_E_ARG;
 }
 
+// the pairs (game class -> plant class) of the table in include/dgsqp.h
+static bool cross_pair_ok(int game, int plant) {
+  if (game == plant) return game >= DGSQP_MODEL_KIN_BICYCLE && game <= DGSQP_MODEL_UNICYCLE_COMBINED;
+  if (plant == DGSQP_MODEL_DYN_BICYCLE) return game == DGSQP_MODEL_KIN_BICYCLE || game == DGSQP_MODEL_UNICYCLE_COMBINED;
+  return game == DGSQP_MODEL_UNICYCLE_COMBINED && plant == DGSQP_MODEL_KIN_BICYCLE;
+}
+int dgsqp_set_cross_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant, int64_t B, const double* z0) {
+  { const int rc = setter_begin(h); if (rc) return rc; }
+  DgCrossState& X = h->cross;
+  if (!plant) { if (X.set) { X.set = false; h->plant.set = false; } return DGSQP_OK; }
+  auto bad = [&](const std::string& m) { return refuse(h, "cross plant: ", m); };
+  const int integ = plant->integrator;
+  if (integ != DGSQP_INT_EULER && integ != DGSQP_INT_RK4 && integ != DGSQP_INT_RK3 && integ != DGSQP_INT_RK2) return bad("unknown integrator " + std::to_string(integ));
+  if (plant->substeps < 1) return bad("substeps must be at least 1, got " + std::to_string(plant->substeps));
+  if (plant->sim_steps < 1) return bad("sim_steps must be at least 1, got " + std::to_string(plant->sim_steps));
+  if (B < 1 || !z0) return bad("z0 [B][n_z] is needed, with B >= 1");
+  const DgProb& D = h->hp;
+  const dgsqp_problem_t& P = D.P;
+  DgCrossState N;
+  for (int a = 0; a < P.M; a++) {
+    const std::string who = "agent " + std::to_string(a);
+    for (int j = 0; j < DGSQP_NUA; j++) { const std::string m = delay_fault(who, j, plant->delay[a][j]); if (!m.empty()) return bad(m); }
+    const int gm = P.agents[a].model, pm = plant->use_game_agents ? gm : plant->agents[a].model;
+    if (!cross_pair_ok(gm, pm))
+      return bad(who + ": a game agent of model class " + std::to_string(gm) + " on a plant of class " + std::to_string(pm) + " is not a supported pair (same class, 0 -> 1, 3 -> 0, 3 -> 1)");
+    N.mdl[a] = pm; N.nz[a] = dg_model_nq(pm); N.zoff[a] = N.nz_all; N.nz_all += N.nz[a];
+    for (int i = 0; i < D.nqa[a]; i++) N.proj[a][i] = (int8_t)(N.nz[a] == D.nqa[a] || i < 3 ? i : i + 2);      // 6 of 8: [0, 1, 2, 5, 6, 7]
+  }
+  N.B = B;
+  N.z0.assign(z0, z0 + (size_t)B * N.nz_all);
+  DgPlantState& S = h->plant;
+  S.set = false; X.set = false;
+  S.host = *plant;
+  if (plant->use_game_agents) memcpy(S.host.agents, P.agents, sizeof(P.agents));
+  { const int rc = side_upload(h, SB_PLANT, &S.host, sizeof(dgsqp_plant_t)); if (rc) return rc; }
+  // the game as a plant (the reference of a TRACK driver is one step of it), and the game with its bounds in the plant's layout
+  {
+    std::vector<dgsqp_plant_t> g(1);
+    memset(g.data(), 0, sizeof(dgsqp_plant_t));
+    g[0].integrator = P.integrator; g[0].substeps = P.substeps; g[0].sim_steps = 1; g[0].use_game_agents = 1;
+    memcpy(g[0].agents, P.agents, sizeof(P.agents));
+    { const int rc = side_upload(h, SB_X_GAME, g.data(), sizeof(dgsqp_plant_t)); if (rc) return rc; }
+    std::vector<dgsqp_problem_t> lift(1, P);
+    for (int a = 0; a < P.M; a++) {
+      dgsqp_agent_t& A = lift[0].agents[a];
+      for (int i = 0; i < DGSQP_MAX_NQA; i++) { A.st_ub[i] = INFINITY; A.st_lb[i] = -INFINITY; }
+      for (int i = 0; i < D.nqa[a]; i++) { A.st_ub[N.proj[a][i]] = P.agents[a].st_ub[i]; A.st_lb[N.proj[a][i]] = P.agents[a].st_lb[i]; }
+    }
+    { const int rc = side_upload(h, SB_X_LIFT, lift.data(), sizeof(dgsqp_problem_t)); if (rc) return rc; }
+  }
+  X = std::move(N);
+  X.set = true; S.set = true;
+  return DGSQP_OK;
+}
+int dgsqp_fetch_plant_state(dgsqp_handle_t h, double* z, int64_t capacity_doubles) {
+  const char* none = "no closed-loop launch with a cross plant has run";
+  return h ? side_fetch(h, {{SB_Z, z, sizeof(double)}}, none, none, "z", capacity_doubles) : DGSQP_E_ARG;
+}
+int dgsqp_fetch_track_ref(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  const char* none = "no closed-loop launch with a cross plant has run";
+  return h ? side_fetch(h, {{SB_TRACK_REF, out, sizeof(double)}}, none, none, "track_ref", capacity_doubles) : DGSQP_E_ARG;
+}
+
 int dgsqp_set_plant_ensemble(dgsqp_handle_t h, int64_t B, const dgsqp_vehicle_t* vehicles, const int32_t* delay) {
   { const int rc = setter_begin(h); if (rc) return rc; }
   DgEnsembleState& E = h->ens;
@@ -1367,7 +1488,11 @@ int dgsqp_set_plant_ensemble(dgsqp_handle_t h, int64_t B, const dgsqp_vehicle_t*
   for (int64_t b = 0; b < B; b++)
     for (int a = 0; a < M; a++) {
       const std::string who = "chain " + std::to_string(b) + ", agent " + std::to_string(a);
-      { const std::string m = model_fault("vehicle of " + who, vehicles[b * M + a].model, h->hp.P.agents[a].model); if (!m.empty()) return bad(m); }
+      if (h->cross.set) {
+        if (vehicles[b * M + a].model != h->cross.mdl[a])
+          return bad("vehicle of " + who + " is of model class " + std::to_string(vehicles[b * M + a].model) + ", the cross plant's agent is of class " + std::to_string(h->cross.mdl[a]));
+      }
+      else { const std::string m = model_fault("vehicle of " + who, vehicles[b * M + a].model, h->hp.P.agents[a].model); if (!m.empty()) return bad(m); }
       for (int j = 0; delay && j < DGSQP_NUA; j++) { const std::string m = delay_fault(who, j, delay[(b * M + a) * DGSQP_NUA + j]); if (!m.empty()) return bad(m); }
     }
   E.B = 0;
@@ -1420,6 +1545,12 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
   std::vector<int32_t> kinds((size_t)B * M);
   bool replay = false;
   auto check = [&](int32_t k, int a, const std::string& where) -> int {
+    if (k == DGSQP_DRIVER_TRACK && h->cross.set) {
+      if (P.agents[a].model == DGSQP_MODEL_UNICYCLE)
+        return bad("TRACK driver for " + where + ", a unicycle: the lane follower needs e_y and e_psi (the 6- and 8-state models)");
+      return DGSQP_OK;
+    }
+    if (k == DGSQP_DRIVER_TRACK) return bad("kind of " + where + " is 3 (track): a TRACK driver needs a cross plant (dgsqp_set_cross_plant; the identity cross plant will do)");
     if (k != DGSQP_DRIVER_GAME && k != DGSQP_DRIVER_PID && k != DGSQP_DRIVER_REPLAY)
       return bad("kind of " + where + " is " + std::to_string(k) + ", allowed 0 (game), 1 (PID), 2 (replay)");
     if (k == DGSQP_DRIVER_PID && P.agents[a].model == DGSQP_MODEL_UNICYCLE)
@@ -1443,6 +1574,7 @@ int dgsqp_set_drivers(dgsqp_handle_t h, const dgsqp_drivers_t* d, int32_t T, int
     if (u_replay) { const int rc = side_upload(h, SB_U_REPLAY, u_replay, sizeof(double) * (size_t)T * (size_t)B * h->hp.nu); if (rc) return rc; }
   }
   R.has_ref = ref != nullptr; R.has_replay = u_replay != nullptr;
+  R.kinds = std::move(kinds);
   R.T = T; R.B = B;
   R.set = true;
   return DGSQP_OK;
@@ -1475,7 +1607,7 @@ int dgsqp_fetch_plan_hold(dgsqp_handle_t h, double* u_game, int32_t* plan_stage,
 
 // Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
 // DgPlantDev argument when the handle has a plant, a DgEnsembleDev when one of the further settings is on as well, a DgPlantDriversDev
-// when drivers are set, and a DgPlantDriversHoldDev when a plan is held.
+// when drivers are set, a DgPlantDriversHoldDev when a plan is held, and a DgCrossPlantDev when the plant is a cross plant.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1487,11 +1619,12 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
   }
-  const bool further = h->ens.any(), hold = h->hold.set, drivers = h->drv.set || hold;
+  const bool cross = h->cross.set, further = h->ens.any(), hold = h->hold.set || cross, drivers = h->drv.set || hold;
   { const int rc = further_check_plant(h); if (rc) return rc; }
   { const int rc = drivers_check_launch(h, T, B); if (rc) return rc; }
   { const int rc = hold_check_launch(h); if (rc) return rc; }
   { const int rc = further_check_launch(h, T, B); if (rc) return rc; }
+  { const int rc = cross_check_launch(h, B, x0, w); if (rc) return rc; }
   const DgUPrevState& U = h->up;
   if (U.cl_mode && U.cl_B > 0 && U.cl_B != B)
     return refuse(h, "closed-loop u_prev: ", "launch of B = " + std::to_string(B) + " chains, u_prev0 was set for " + std::to_string(U.cl_B));
@@ -1538,12 +1671,15 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (drivers) { const int rc = drivers_for_launch(h, grid, B, TB, ex, &dd); if (rc) return rc; }
   DgPlantDriversHoldDev hd{};
   if (hold) { const int rc = hold_for_launch(h, grid, TB, dd, &hd); if (rc) return rc; }
+  DgCrossPlantDev xp{};
+  if (cross) { const int rc = cross_for_launch(h, B, T, hd, &xp); if (rc) return rc; }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (hold) launch_closed_loop(h, grid, B, cl, hd);
+    if (cross) launch_closed_loop(h, grid, B, cl, xp);
+    else if (hold) launch_closed_loop(h, grid, B, cl, hd);
     else if (drivers) launch_closed_loop(h, grid, B, cl, dd);
     else if (further) launch_closed_loop(h, grid, B, cl, ex);
     else if (h->plant.set) launch_closed_loop(h, grid, B, cl, pd);

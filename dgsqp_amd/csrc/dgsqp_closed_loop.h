@@ -84,6 +84,28 @@ struct DgPlantDriversHoldDev {
 }
 using dg_hold::DgPlantDriversHoldDev;
 
+// A plant of ANOTHER model class than the game's (dgsqp_set_cross_plant): the plant keeps a state z of its own, [T+1][B][nz], fed back
+// like q by the lane that wrote it, and the game sees the projection q = p(z) -- entry i of agent a's block of q is entry proj[a][i] of
+// its block of z.  The pack of the sixth instantiation of dg_closed_loop_kernel; it wraps DgPlantDriversHoldDev (the host layer builds
+// all-GAME kinds and the default hold when the caller gives none), so every other setting combines with it.  `lift` is the game with
+// every agent's state bounds moved to the plant's layout (+-inf on entries the game does not see): what the monitor of dev_plant_agent
+// reads when it integrates a z block; `game` is the game as a plant (its integrator and sub-steps, one simulation step, no delay): one
+// step of it from p(z) under the game's command is the reference a TRACK driver follows.
+// The NAME (see DgPlantDriversDev, dg_hold): N9dg_xplant... sorts behind N7dg_hold..., so this instantiation is the last one.
+namespace dg_xplant {
+struct DgCrossPlantDev {
+  dg_hold::DgPlantDriversHoldDev hd;
+  int32_t mdl[DGSQP_MAX_AGENTS], nz[DGSQP_MAX_AGENTS], zoff[DGSQP_MAX_AGENTS];      // the plant agents' classes, state counts, offsets in z
+  int32_t nz_all;                                                                   // their sum
+  int8_t proj[DGSQP_MAX_AGENTS][DGSQP_MAX_NQA];
+  const dgsqp_problem_t* lift;
+  const dgsqp_plant_t* game;
+  double* z;                          // [T+1][B][nz_all] slice 0 = z0, slice t + 1 = the plant's state after step t
+  double* track_ref;                  // [T][B][M][3] (v_ref, lat_ref, epsi_ref) of the TRACK agents
+};
+}
+using dg_xplant::DgCrossPlantDev;
+
 // Agent a's monitor record of one simulation step, from its state block z: the position and the largest excess over the GAME's bounds
 // (-inf: no finite bound; NaN: an entry of z is not finite).  One lane, no cross-lane operation.
 __device__ inline void dev_monitor_store(const dgsqp_agent_t& game, int nqa, const double* z, double* rec) {
@@ -408,6 +430,157 @@ __device__ __noinline__ int dev_estimate(DgPlantDriversHoldDev hd, int64_t tb_b,
   return dev_estimate(hd.dd.ex, tb_b, q_t, x0);
 }
 
+// ---- a plant of another model class (DgCrossPlantDev) ----
+// One step of the GAME's discrete model for agent a from x (in place) under g: the game as a plant has no delay (the line is never
+// touched) and one simulation step, whose input record goes to a local.
+// P is the pack's copy of the game (`lift`: step, integrator and track are the game's; the bounds are not read here).
+__device__ inline void dev_cross_game_step(const dgsqp_problem_t& P, const dgsqp_plant_t& game, int a, const double* g, double* x) {
+  double rec[DGSQP_NUA];
+  const int mdl = dg_prob.mdl[a];
+  if (mdl == DG_PM) dev_plant_agent<DG_PM, false>(P, game, a, 0, g, nullptr, rec, DGSQP_NUA, x);
+  else if (P.track_kind == DGSQP_TRACK_SPLINE) {
+    if (mdl == DG_DYN) dev_plant_agent<DG_DYN, true>(P, game, a, 0, g, nullptr, rec, DGSQP_NUA, x);
+    else dev_plant_agent<DG_KIN, true>(P, game, a, 0, g, nullptr, rec, DGSQP_NUA, x);
+  }
+  else if (mdl == DG_DYN) dev_plant_agent<DG_DYN, false>(P, game, a, 0, g, nullptr, rec, DGSQP_NUA, x);
+  else dev_plant_agent<DG_KIN, false>(P, game, a, 0, g, nullptr, rec, DGSQP_NUA, x);
+}
+
+// The feedback with a plant of another class, one lane per agent; every lane of the workgroup calls it.  Lane a < M, in this order:
+// the game's command (the hold overload's rule) to u_game[t][b]; its driver's command to u_cmd[t][b] -- PID and REPLAY read and command the
+// PLANT's agent, TRACK is dev_pid_law towards one step of the game's model from p(z_t) under the game's command (track_ref[t][b][a]);
+// the S simulation steps of its block of z with the plant's class (dev_plant_agent: delay lines, u_plant, the monitor's records against
+// `lift`); z[t+1][b] and q[t+1][b] = p(z[t+1][b]).  Returns non-zero when z[t+1] is not finite (or, from lane 0, after a hit in mode 2).
+// The chain's plant and the monitor's reduction are those of the DgEnsembleDev overload, restated: that function keeps its code.
+__device__ __noinline__ int dev_plant_feedback(DgCrossPlantDev xp, int solved, int status, const double* uws_t, int t, int64_t tb_b,
+                                               const double* q_t, const double* u_t, const double* w_t, double* q_next) {
+  const DgProb& D = dg_prob;
+  const DgPlantDriversHoldDev& hd = xp.hd;
+  const DgPlantDriversDev& dd = hd.dd;
+  const DgEnsembleDev& ex = dd.ex;
+  const dgsqp_problem_t& L = *xp.lift;      // the game, read through the pack: bounds in the plant's layout, everything else the game's
+  const int a = TID, M = D.M;
+  const int64_t b = tb_b - (int64_t)t * ex.B;
+  const dgsqp_plant_t* pl = ex.pd.P;
+  if (ex.vehicles) {
+    dgsqp_plant_t* mine = ex.wg_plant + blockIdx.x;
+    if (t == 0) {
+      if (a == 0) { mine->integrator = pl->integrator; mine->substeps = pl->substeps; mine->sim_steps = pl->sim_steps; mine->use_game_agents = 0; }
+      if (a < M) {
+        __builtin_memcpy(&mine->agents[a], &ex.vehicles[b * M + a], sizeof(dgsqp_vehicle_t));
+        for (int ch = 0; ch < DGSQP_NUA; ch++) mine->delay[a][ch] = ex.delay ? ex.delay[(b * M + a) * DGSQP_NUA + ch] : pl->delay[a][ch];
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+    pl = mine;
+  }
+  const int S = pl->sim_steps;
+  double* mon = ex.monitor ? ex.mon_scratch + (int64_t)blockIdx.x * S * M * 3 : nullptr;
+  int bad = 0;
+  if (a < M) {
+    const int nqa = D.nqa[a], nza = xp.nz[a];
+    const int8_t* pr = xp.proj[a];
+    const double* za = xp.z + tb_b * xp.nz_all + xp.zoff[a];             // written by this very lane one step ago, or by the host
+    double* zn = xp.z + (tb_b + ex.B) * xp.nz_all + xp.zoff[a];
+    // 1. the game's command, and the driver's
+    const int rule = dev_hold_rule(hd, solved, status);
+    const double* src = rule == DG_HOLD_CONSUME ? uws_t : u_t;
+    double g[DGSQP_NUA], c[DGSQP_NUA];
+    for (int j = 0; j < DGSQP_NUA; j++) {
+      g[j] = src[am_col(D, a, 0, j)];
+      hd.u_game[tb_b * D.nu + a * DGSQP_NUA + j] = g[j];
+    }
+    if (a == 0) hd.plan_stage[tb_b] = rule == DG_HOLD_CONSUME ? hd.state[(int64_t)blockIdx.x * 2] : 0;
+    const int kind = dd.kind[b * M + a];
+    double* st = dd.pid_state + ((int64_t)blockIdx.x * M + a) * 3;
+    if (t == 0) { st[0] = 0.0; st[1] = 0.0; st[2] = 0.0; }
+    if (kind == DGSQP_DRIVER_PID || kind == DGSQP_DRIVER_TRACK) {
+      const int epsi = nza == 8 ? 5 : 3, ey = nza - 1;                  // (the PLANT's layout)
+      double v_ref, lat_ref, epsi_ref = 0.0;
+      if (kind == DGSQP_DRIVER_TRACK) {
+        double xr[DGSQP_MAX_NQA];
+        for (int i = 0; i < DGSQP_MAX_NQA; i++) xr[i] = i < nqa ? za[pr[i]] : 0.0;
+        dev_cross_game_step(L, *xp.game, a, g, xr);
+        v_ref = xr[2]; lat_ref = xr[nqa - 1]; epsi_ref = xr[nqa == 8 ? 5 : 3];      // (the GAME's layout)
+        double* tr = xp.track_ref + (tb_b * M + a) * 3;
+        tr[0] = v_ref; tr[1] = lat_ref; tr[2] = epsi_ref;
+      } else {
+        const double* z0 = za - (int64_t)t * ex.B * xp.nz_all;            // the chain's z0: slice 0 of z
+        const double* ref = dd.ref ? dd.ref + (b * M + a) * 2 : nullptr;
+        v_ref = ref ? ref[0] : z0[2]; lat_ref = ref ? ref[1] : z0[ey];
+      }
+      double ei = st[0], up0 = st[1], up1 = st[2];
+      dev_pid_law(dd.pid[a], L.dt, za[2], v_ref, za[ey], lat_ref, kind == DGSQP_DRIVER_TRACK ? za[epsi] - epsi_ref : za[epsi], ei, up0, up1);
+      st[0] = ei; st[1] = up0; st[2] = up1;
+      c[0] = up0; c[1] = up1;
+    }
+    else if (kind == DGSQP_DRIVER_REPLAY)
+      for (int j = 0; j < DGSQP_NUA; j++) c[j] = dd.u_replay[tb_b * D.nu + a * DGSQP_NUA + j];
+    else
+      for (int j = 0; j < DGSQP_NUA; j++) c[j] = g[j];
+    for (int j = 0; j < DGSQP_NUA; j++) dd.u_cmd[tb_b * D.nu + a * DGSQP_NUA + j] = c[j];
+    // 2. the S simulation steps of the agent's block of z
+    double* line = ex.pd.lines + ((int64_t)blockIdx.x * DGSQP_MAX_AGENTS + a) * (DGSQP_NUA * DGSQP_MAX_DELAY);
+    if (t == 0)
+      for (int i = 0; i < DGSQP_NUA * DGSQP_MAX_DELAY; i++) line[i] = 0.0;
+    double zz[DGSQP_MAX_NQA];
+    for (int i = 0; i < DGSQP_MAX_NQA; i++) zz[i] = i < nza ? za[i] : 0.0;
+    double* u_rec = ex.pd.u_plant + tb_b * S * D.nu + a * DGSQP_NUA;
+    const int64_t count = (int64_t)t * S;
+    const int mdl = xp.mdl[a];
+    if (mdl == DG_UNI) dev_plant_agent<DG_UNI, false, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+    else if (mdl == DG_PM) dev_plant_agent<DG_PM, false, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+    else if (L.track_kind == DGSQP_TRACK_SPLINE) {
+      if (mdl == DG_DYN) dev_plant_agent<DG_DYN, true, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+      else dev_plant_agent<DG_KIN, true, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+    }
+    else if (mdl == DG_DYN) dev_plant_agent<DG_DYN, false, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+    else dev_plant_agent<DG_KIN, false, true>(L, *pl, a, count, c, line, u_rec, D.nu, zz, mon);
+    // 3. z[t+1] and its projection (the monitor's record of the last simulation step is dev_plant_agent's: nothing is added to z)
+    for (int i = 0; i < DGSQP_MAX_NQA; i++)
+      if (i < nza) { zn[i] = zz[i]; bad |= !isfinite(zz[i]); }
+    for (int i = 0; i < DGSQP_MAX_NQA; i++)
+      if (i < nqa) q_next[D.qoff[a] + i] = zz[pr[i]];
+  }
+  if (!mon) return bad;
+  __threadfence_block();
+  __syncthreads();
+  if (a == 0) {
+    double cl = INFINITY, bx = -INFINITY;
+    bool fin = true;
+    int hit = -1;
+    for (int j = 0; j < S; j++)
+      for (int i = 0; i < M; i++) {
+        const double* ri = mon + ((int64_t)j * M + i) * 3;
+        fin = fin && ri[2] == ri[2];
+        bx = fmax(bx, ri[2]);
+        for (int k = i + 1; k < M; k++) {
+          const double* rk = ri + (k - i) * 3;
+          const double dx = ri[0] - rk[0], dy = ri[1] - rk[1];
+          const double d = sqrt(dx * dx + dy * dy) - (L.agents[i].radius + L.agents[k].radius);
+          cl = fmin(cl, d);
+          if (d < 0.0 && hit < 0) hit = j;
+        }
+      }
+    ex.clearance[tb_b] = fin ? cl : NAN;
+    ex.box_excess[tb_b] = fin ? bx : NAN;
+    if (hit >= 0) {
+      if (ex.hit_step[b] < 0) ex.hit_step[b] = t * S + hit;
+      if (ex.monitor == 2) bad = 1;
+    }
+  }
+  return bad;
+}
+
+__device__ __noinline__ int dev_hold_due(DgCrossPlantDev xp, int t) { return dev_hold_due(xp.hd, t); }
+__device__ __noinline__ void dev_hold_next(DgCrossPlantDev xp, int solved, int status, const double* uws_t, const double* u_t, double* uws_next) {
+  dev_hold_next(xp.hd, solved, status, uws_t, u_t, uws_next);
+}
+__device__ __noinline__ int dev_estimate(DgCrossPlantDev xp, int64_t tb_b, const double* q_t, const double** x0) {
+  return dev_estimate(xp.hd.dd.ex, tb_b, q_t, x0);
+}
+
 // Per ticket b, for t = 0 .. T-1: solve from (q[t][b], uws[t][b]) exactly as dg_solve_kernel would, then
 //   q[t+1][b]   = x_t[b][1] (+ w[t][b])                          the game's own discrete model is the plant
 //            or = plant(q[t][b], stage 0 of u_t[b]) (+ w[t][b])  with a PLANT: dev_plant_feedback
@@ -419,7 +592,9 @@ __device__ __noinline__ int dev_estimate(DgPlantDriversHoldDev hd, int64_t tb_b,
 // (status DGSQP_NOT_RUN, zero counts, NaN).
 // No cooperative line search, no deferral, no event or iterate log: a chain's next solve depends on its last one.
 // A non-finite q_est[t][b] (DgEnsembleDev with estimates) ends the chain BEFORE solve t: steps_done[b] = t.
-// PLANT is empty, one DgPlantDev, one DgEnsembleDev, one DgPlantDriversDev, or one DgPlantDriversHoldDev: the instantiation without a plant has
+// With a plant of ANOTHER CLASS (DgCrossPlantDev) the plant's own state z is fed back next to q, q[t+1][b] = p(z[t+1][b]), and a chain
+// ends on a non-finite entry of z[t+1][b]; everything else is the held-plan instantiation's.
+// PLANT is empty, one DgPlantDev, one DgEnsembleDev, one DgPlantDriversDev, one DgPlantDriversHoldDev, or one DgCrossPlantDev: the instantiation without a plant has
 // the argument list it always had and holds nothing of the plant, the one with a DgPlantDev nothing of the further settings, the one with a
 // DgEnsembleDev nothing of the drivers, the one with a DgPlantDriversDev nothing of the held plan.
 // With a HELD PLAN (DgPlantDriversHoldDev; the table in include/dgsqp.h) step t solves only when a plan is due (dev_hold_due); a held step
@@ -432,13 +607,21 @@ __device__ inline double dev_command(const DgPlantDev&, int64_t, int a, int j, c
 __device__ inline double dev_command(const DgEnsembleDev&, int64_t, int a, int j, const double* u_t) { return u_t[am_col(dg_prob, a, 0, j)]; }
 __device__ inline double dev_command(const DgPlantDriversDev& dd, int64_t tb_b, int a, int j, const double*) { return dd.u_cmd[tb_b * dg_prob.nu + a * DGSQP_NUA + j]; }
 __device__ inline double dev_command(const DgPlantDriversHoldDev& hd, int64_t tb_b, int a, int j, const double*) { return hd.dd.u_cmd[tb_b * dg_prob.nu + a * DGSQP_NUA + j]; }
+// a TRACK agent's command is in the plant's units: the game's rate rows are measured against the GAME's command for that agent
+__device__ inline double dev_command(const DgCrossPlantDev& xp, int64_t tb_b, int a, int j, const double*) {
+  const DgPlantDriversDev& dd = xp.hd.dd;
+  const int kind = dd.kind[(tb_b % dd.ex.B) * dg_prob.M + a];
+  return (kind == DGSQP_DRIVER_TRACK ? xp.hd.u_game : dd.u_cmd)[tb_b * dg_prob.nu + a * DGSQP_NUA + j];
+}
 
 template <class... PLANT> struct DgHasEstimates { static constexpr bool value = false; };
 template <> struct DgHasEstimates<DgEnsembleDev> { static constexpr bool value = true; };
 template <> struct DgHasEstimates<DgPlantDriversDev> { static constexpr bool value = true; };
 template <> struct DgHasEstimates<DgPlantDriversHoldDev> { static constexpr bool value = true; };
+template <> struct DgHasEstimates<DgCrossPlantDev> { static constexpr bool value = true; };
 template <class... PLANT> struct DgHoldsPlan { static constexpr bool value = false; };
 template <> struct DgHoldsPlan<DgPlantDriversHoldDev> { static constexpr bool value = true; };
+template <> struct DgHoldsPlan<DgCrossPlantDev> { static constexpr bool value = true; };
 template <class... PLANT>
 __global__ void __launch_bounds__(DG_BLOCK, 2)
 dg_closed_loop_kernel(int64_t B, DgClosedLoop cl, double* __restrict__ ws_all, unsigned long long* __restrict__ ticket, PLANT... pd) {

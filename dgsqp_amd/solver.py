@@ -561,7 +561,7 @@ class DGSQP(AbstractSolver):
 
     def step_batch(self, x0: np.ndarray, u_ws: np.ndarray, steps: int, disturbance: Optional[np.ndarray] = None,
                    keep_predictions: bool = False, plant=None, estimate_noise: Optional[np.ndarray] = None, monitor=False, drivers=None,
-                   u_prev=None, hold=None) -> dict:
+                   u_prev=None, hold=None, z0: Optional[np.ndarray] = None) -> dict:
         """B closed-loop runs of ``steps`` calls of ``step()`` each, in ONE launch (``dgsqp_closed_loop_batch``): one workgroup carries
         one scenario through all its steps, nothing crosses the host in between.  ``x0`` [B, n_q]; ``u_ws`` [B, N, n_u] or [B, n] as
         ``solve_batch`` takes it; ``disturbance`` [B, steps, n_q], added to the next state -- the plant is the game's own discrete model
@@ -607,6 +607,15 @@ class DGSQP(AbstractSolver):
         the chain had consumed before it (0 on an accepted solve, -1 where a step never ran); u_applied is u_game.  The defaults
         ``PlanHold()`` give, bit for bit, the launch without ``hold``.
 
+        ``plant=PlantModel(..., own_class=True)`` (``dgsqp_set_cross_plant``), for this call only: a plant of another model class than the game's
+        agents, with a state of its own.  ``z0`` [B, n_z] is its initial state (default ``closed_loop.lift_state`` of ``x0``: vy = w = 0);
+        ``x0`` must be ``closed_loop.project_state`` of it, bit for bit.  q[:, t + 1] is the projection of z[:, t + 1], a chain ends on a
+        non-finite entry of z, and ``disturbance`` is refused (it has no place in z).  Drivers read and command the plant's agents; a
+        'track' driver follows the game's plan (``closed_loop.track_reference``), and a point-mass agent on a bicycle plant needs one (or
+        'pid' / 'replay').  The launch runs with ``Drivers()`` and ``PlanHold()`` where none are given (bit for bit the launch without), so
+        the result holds u_cmd, u_game and plan_stage, and gains z [B, T+1, n_z] and, with a 'track' agent, track_ref [B, T, M, 3] =
+        (v_ref, lat_ref, epsi_ref), NaN for other agents.
+
         Returns, scenario-major: q [B, T+1, n_q], u_applied [B, T, n_u], u [B, T, n], u_pred [B, T, N, n_u], u_ws [B, T+1, n] (slice t =
         the warm start step t started from), status / num_iters / qp_solves [B, T], cond [B, T, 3], cost [B, T, M], msg, converged,
         steps_done [B], time, kernel_ms; with ``keep_predictions`` also x [B, T, N+1, n_q] and l [B, T, n_c]."""
@@ -632,6 +641,26 @@ class DGSQP(AbstractSolver):
         if (drivers is not None or hold is not None) and plant is None:
             from .closed_loop import PlantModel
             plant = PlantModel()
+        cross = plant is not None and bool(getattr(plant, 'own_class', False))
+        if z0 is not None and not cross:
+            raise ValueError('z0 is the state of a plant of its own class: it needs plant=PlantModel(..., own_class=True)')
+        pcls = zz0 = None
+        if cross:
+            from .closed_loop import Drivers, PlanHold, lift_state, project_state
+            if disturbance is not None:
+                raise ValueError('disturbance is in the game\'s layout and has no place in the state z of a plant of its own class')
+            gcls = [int(self._problem.agents[a].model) for a in range(self.M)]
+            pcls = plant.plant_classes(self._problem)
+            if len(pcls) != self.M:
+                raise ValueError(f'Number of agents: {self.M}, but {len(pcls)} plant configs were provided')
+            n_z = lift_state(gcls, pcls, np.zeros(self.n_q)).shape[-1]      # (also refuses a pair outside the table)
+            zz0 = lift_state(gcls, pcls, x0) if z0 is None else np.ascontiguousarray(z0, dtype=np.float64)
+            if zz0.shape != (B, n_z):
+                raise ValueError(f'z0 must be [B, n_z] = {(B, n_z)}, got {zz0.shape}')
+            if not np.array_equal(project_state(gcls, pcls, zz0).view(np.uint64), x0.view(np.uint64)):
+                raise ValueError('x0 must be the projection of z0 (closed_loop.project_state), bit for bit')
+            drivers = Drivers() if drivers is None else drivers
+            hold = PlanHold() if hold is None else hold
         if monitor not in (False, None, True, 'stop'):
             raise ValueError(f"monitor must be False, True or 'stop', got {monitor!r}")
         if plant is None and (estimate_noise is not None or monitor):
@@ -649,13 +678,15 @@ class DGSQP(AbstractSolver):
             pt = plant.lower(self._problem)
             ensemble = plant.lower_ensemble(self._problem, B) if plant.per_chain else None
         if drivers is not None:
-            drv = drivers.lower(self._problem, B, T)
+            drv = drivers.lower(self._problem, B, T, plant_classes=pcls) if cross else drivers.lower(self._problem, B, T)
         if hold is not None:
             ht = hold.lower(self._problem)
         # Every setting once, in the order they are set: dgsqp_set_<name>(*on) when it is asked for and, afterwards, (*off);
         # dgsqp_fetch_<fetch> fills the records it adds to the result -- ``steps`` step-major [T, B, ...] doubles, ``chains`` [B] int32 --
         # and takes their size when ``sized``; ``steps_i32`` are further step-major records [T, B] of int32, fetched behind the doubles.
-        settings = [_Setting('plant', pt is not None and (C.byref(pt),), (None,), 'u_plant', dict(u_plant=(getattr(pt, 'sim_steps', 0), self.n_u))),
+        tracked = cross and (drv[0].kind[:self.M] + ([] if drv[1] is None else list(drv[1].reshape(-1)))).count(_ffi.DRIVER_TRACK) > 0
+        settings = [_Setting('plant', pt is not None and not cross and (C.byref(pt),), (None,), 'u_plant', dict(u_plant=(getattr(pt, 'sim_steps', 0), self.n_u))),
+                    _Setting('cross_plant', cross and (C.byref(pt), B, dptr(zz0)), (None, 0, None), 'u_plant', dict(u_plant=(getattr(pt, 'sim_steps', 0), self.n_u))),
                     _Setting('plant_ensemble', ensemble is not None and (B, ensemble[0], iptr(ensemble[1])), (0, None, None)),
                     _Setting('estimate_noise', noise is not None and (T, B, dptr(noise)), (0, 0, None), 'q_est', dict(q_est=(self.n_q,))),
                     _Setting('monitor', bool(monitor) and (2 if monitor == 'stop' else 1,), (0,), 'monitor', dict(clearance=(), box_excess=()), ('hit_step',), sized=False),
@@ -663,6 +694,7 @@ class DGSQP(AbstractSolver):
                              'u_cmd', dict(u_cmd=(self.n_u,))),
                     _Setting('plan_hold', ht is not None and (C.byref(ht),), (None,), 'plan_hold', dict(u_game=(self.n_u,)), steps_i32=('plan_stage',)),
                     _Setting('closed_loop_u_prev', carry and (1, B if up0 is not None else 0, dptr(up0)), (0, 0, None), 'u_prev', dict(u_prev=(self.n_u,)))]
+        # (the cross plant's further records, fetched behind the table's: z has T + 1 slices and is no step record)
         on = [st for st in settings if st.on]
         chains = {k: np.empty(B, np.int32) for st in on for k in st.chains}
         sm.update({k: np.empty((T, B) + tail) for st in on for k, tail in st.steps.items()})
@@ -683,6 +715,14 @@ class DGSQP(AbstractSolver):
                             + [sm[k].size for k in st.steps if st.sized])
                     if getattr(self._lib, 'dgsqp_fetch_' + st.fetch)(self._h, *into) != 0:
                         raise RuntimeError(f'dgsqp_fetch_{st.fetch} failed: ' + last_error())
+            if cross and B > 0:
+                sm['z'] = np.empty((T + 1, B, zz0.shape[1]))
+                if self._lib.dgsqp_fetch_plant_state(self._h, dptr(sm['z']), sm['z'].size) != 0:
+                    raise RuntimeError('dgsqp_fetch_plant_state failed: ' + last_error())
+                if tracked:
+                    sm['track_ref'] = np.empty((T, B, self.M, 3))
+                    if self._lib.dgsqp_fetch_track_ref(self._h, dptr(sm['track_ref']), sm['track_ref'].size) != 0:
+                        raise RuntimeError('dgsqp_fetch_track_ref failed: ' + last_error())
         finally:
             for st in reversed(settings):
                 if st.on or plant is not None:

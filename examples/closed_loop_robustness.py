@@ -24,6 +24,12 @@ on the held plan or, with ``--on-fail reference``, applied a failed iterate.
     python examples/closed_loop_robustness.py --carry-u-prev
     python examples/closed_loop_robustness.py --replan-every 3 --on-fail hold
     python examples/closed_loop_robustness.py --model point-mass
+    python examples/closed_loop_robustness.py --model point-mass --plant-class dynamic --track
+
+``--plant-class dynamic`` runs the chains on dynamic bicycles with Pacejka tyres -- a plant of ANOTHER model class than the game's, with a
+state of its own (``PlantModel(own_class=True)``; mass, drag and yaw inertia perturbed).  The kinematic game's commands mean the same on
+that plant; the point-mass game's (Fx, wz) do not, so there ``--track`` is needed: every car follows its part of the game's plan with the
+lane follower (``Drivers('track')``) -- the race demo's set-up, with the PID law in place of its tracking MPC.
 """
 import argparse
 import copy
@@ -34,7 +40,7 @@ import numpy as np
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 from dgsqp_amd.closed_loop import Drivers, PlanHold, PlantModel, perturbed_configs          # noqa: E402
-from dgsqp_amd.montecarlo import kinematic_racing_game, point_mass_racing_game    # noqa: E402
+from dgsqp_amd.montecarlo import dynamic_racing_game, kinematic_racing_game, point_mass_racing_game    # noqa: E402
 from dgsqp_amd.solver import DGSQP                                                # noqa: E402
 
 
@@ -79,13 +85,23 @@ def main():
                     help="after a failed solve: stage 0 of the failed iterate (the reference's step()), or the next stage of the plan the chain holds")
     ap.add_argument('--model', choices=('kinematic', 'point-mass'), default='kinematic',
                     help="the vehicles: kinematic bicycles, or the race demo's Frenet point masses (mass and damping perturbed; that game has no rate rows)")
+    ap.add_argument('--plant-class', choices=('game', 'dynamic'), default='game',
+                    help="the plants: the game's model class, or dynamic bicycles with Pacejka tyres (a state of their own)")
+    ap.add_argument('--track', action='store_true', help="every car follows its part of the game's plan with the lane follower (needs --plant-class dynamic)")
     args = ap.parse_args()
+    if args.track and args.plant_class != 'dynamic':
+        ap.error('--track needs --plant-class dynamic')
+    if args.plant_class == 'dynamic' and args.model == 'point-mass' and not args.track:
+        ap.error("the point-mass game's inputs (Fx, wz) cannot command a bicycle: add --track")
+    if args.track and args.opponent == 'pid':
+        ap.error('--track drives every car; leave --opponent at game')
 
     game = point_mass_racing_game('curve', N=args.N) if args.model == 'point-mass' else kinematic_racing_game('curve', N=args.N)
     s = DGSQP(*game.solver_args(), print_method=None)
     B, T = args.batch, args.steps
     smp = s.sample_batch(game, B, seed=args.seed)
-    nominal = [copy.deepcopy(m.model_config) for m in game.joint_model.dynamics_models]
+    cross = args.plant_class == 'dynamic'
+    nominal = [copy.deepcopy(m.model_config) for m in (dynamic_racing_game(N=5) if cross else game).joint_model.dynamics_models]
     noise = args.noise * np.random.default_rng(args.seed).standard_normal((B, T, s.n_q))
     P = s._problem
     has_rate = all(P.agents[a].has_rate for a in range(s.M))          # (a game without rate rows stores rate_ub = 0)
@@ -96,12 +112,15 @@ def main():
     if hold is not None:
         print(f'a plan every {args.replan_every} control step(s), after a failed solve: {args.on_fail}')
     opponents = [('self-play', None)] + ([('pid', Drivers(kinds=['game', 'pid']))] if args.opponent == 'pid' else [])
+    if args.track:
+        opponents = [('tracked', Drivers(kinds=['track'] * s.M))]
     print('spread   car 2       chains with a contact   min clearance   mean clearance   mean box_excess   mean steps run   kernel [ms]   max jump / (dt rate_ub): u_a, u_steer   steps over the limit'
           + ('   held steps   fallback steps' if hold is not None else ''))
     for spread in args.spreads:
-        fields = ('mass', 'damping_coefficient') if args.model == 'point-mass' else ('mass', 'drag_coefficient', 'slip_coefficient')
+        fields = (('mass', 'drag_coefficient', 'yaw_inertia') if cross else ('mass', 'damping_coefficient') if args.model == 'point-mass'
+                  else ('mass', 'drag_coefficient', 'slip_coefficient'))
         ens = perturbed_configs(nominal, {f: spread for f in fields}, B, args.seed)
-        plant = PlantModel(per_chain_configs=ens, method='rk4', M=2, sim_steps=args.sim_steps)
+        plant = PlantModel(dynamics_configs=nominal if cross else None, per_chain_configs=ens, method='rk4', M=2, sim_steps=args.sim_steps, own_class=cross)
         for name, drivers in opponents:
             r = s.step_batch(smp['x0'], smp['u_ws'], T, plant=plant, estimate_noise=noise, monitor='stop', drivers=drivers,
                              u_prev=True if args.carry_u_prev else None, hold=hold)

@@ -434,8 +434,9 @@ int dgsqp_fetch_monitor(dgsqp_handle_t h, double* clearance, double* box_excess,
  *                        integrator and the previous command persist along the chain and start at 0 for every chain.  `substeps` is
  *                        not read.  For the 6- and 8-state models only (the unicycle has no e_y / e_psi).
  *   DGSQP_DRIVER_REPLAY  u_replay[t][b] of that agent.  A non-finite entry makes the next state non-finite and ends that chain.
+ *   DGSQP_DRIVER_TRACK   with a cross plant only (dgsqp_set_cross_plant, below): the lane follower tracks the game's plan.
  */
-enum { DGSQP_DRIVER_GAME = 0, DGSQP_DRIVER_PID = 1, DGSQP_DRIVER_REPLAY = 2 };
+enum { DGSQP_DRIVER_GAME = 0, DGSQP_DRIVER_PID = 1, DGSQP_DRIVER_REPLAY = 2, DGSQP_DRIVER_TRACK = 3 };
 typedef struct {
   int32_t kind[DGSQP_MAX_AGENTS];     /* DGSQP_DRIVER_*; entries beyond M are not read */
   dgsqp_pid_t pid[DGSQP_MAX_AGENTS];  /* read for PID agents */
@@ -521,6 +522,55 @@ typedef struct {
    run). */
 int dgsqp_set_plan_hold(dgsqp_handle_t h, const dgsqp_hold_t* hold);
 int dgsqp_fetch_plan_hold(dgsqp_handle_t h, double* u_game /* [T][B][n_u] */, int32_t* plan_stage /* [T][B] */, int64_t capacity_doubles);
+
+/*
+ * A plant of ANOTHER MODEL CLASS than the game's (the reference's race demo plans with a point-mass game and drives a dynamic bicycle with
+ * Pacejka tyres: scripts/race/race_main.py:438-456, 586-597).  The plant keeps a state z of its own, [T+1][B][n_z], n_z the sum of the
+ * plant agents' state counts, and the game sees the projection q = p(z), agent by agent:
+ *
+ *   game -> plant                                     projection
+ *   same class (all four classes)                     identity
+ *   kinematic bicycle (0) -> dynamic bicycle (1)      z[[0,1,2,5,6,7]]
+ *   Frenet point mass (3) -> kinematic bicycle (0)    identity
+ *   Frenet point mass (3) -> dynamic bicycle (1)      z[[0,1,2,5,6,7]]
+ *
+ * (8 states [x, y, vx, vy, w, e_psi, s, e_y]; 6 states [x, y, v, e_psi, s, e_y], the point mass [x, y, v, e_psi, s, x_tran];
+ * race_main.py:533-541 maps between them in the same way.)  Every other pair is refused; agents of one game may use different pairs.
+ *
+ * dgsqp_set_cross_plant: sticky like dgsqp_set_plant, every array is copied.  plant->agents[a].model may be any class of the table;
+ * use_game_agents = 1: every agent keeps the game's class and record.  z0 [B][n_z] is slice 0 of z.  It counts as "a plant is set" for the
+ * ensemble, estimate, monitor, drivers, hold and u_prev settings; dgsqp_set_plant(h, ...) and dgsqp_set_cross_plant(h, NULL, 0, NULL)
+ * clear it.  DGSQP_E_ARG, message starting "cross plant: ": what dgsqp_set_plant refuses, a pair outside the table, B < 1, z0 = NULL.
+ *
+ * dgsqp_closed_loop_batch with a cross plant set: x0 must equal p(z0) bit for bit and B must be z0's, w must be NULL (a disturbance in
+ * the game's layout has no place in z), else DGSQP_E_ARG ("cross plant: ...").  Step t: z[t+1][b] is z[t][b] advanced by the plant as
+ * under dgsqp_set_plant (u_plant, delay lines, sim_steps, integrator and sub-steps work exactly as there) and q[t+1][b] = p(z[t+1][b]).
+ * Every solve still is, bit for bit, the dgsqp_solve_batch solve from (q[t][b] or q_est[t][b], u_ws[t][b]); q_est = p(z) + v, the noise
+ * stays in the game's layout.  A chain ends on a non-finite entry of z[t+1][b] (the projection drops vy and w).  The monitor reads the
+ * projected states after each simulation step: positions, and the game's bounds on the entries the game sees.
+ * dgsqp_set_plant_ensemble compares each vehicle's class with the PLANT's agent class.
+ *
+ * Drivers on a cross plant.  GAME needs inputs of the same meaning: same-class pairs and 0 -> 1; a point-mass agent (Fx, wz) on a bicycle
+ * plant (acceleration, steering) with a GAME driver is refused when the launch starts -- a launch without drivers included, all agents
+ * are GAME then -- with a message starting "drivers: " that names the agent.  PID and REPLAY read and command the PLANT's agent (e_psi at
+ * 5 and e_y at 7 of an 8-state block; with ref = NULL the references come from z0).  DGSQP_DRIVER_TRACK is accepted only while a cross
+ * plant is set (the identity cross plant will do), for 6- and 8-state agents.  With g = u_game[t][b] of agent a (stage 0 of the solution,
+ * or of the held plan):
+ *   x_ref = one step of the GAME's discrete model for agent a from p_a(z[t][b]) -- the TRUE state -- under g (the game's integrator,
+ *           sub-steps and dt);
+ *   the command is the PID law with v_ref = x_ref[v], lat_ref = x_ref[last] and the heading error e_psi - x_ref[e_psi] in place of
+ *   e_psi; v, e_y and e_psi are the plant agent's.  Integrator and previous command persist and are reset per chain, as for PID.
+ * With the u_prev carry a TRACK agent's u_prev[t+1] takes u_game[t] (the game's rate rows are in the game's units), every other kind
+ * u_cmd[t] as before.
+ *
+ * dgsqp_fetch_plant_state: z [T+1][B][n_z] of the last launch with a cross plant; slice 0 is z0, the state that ended a chain is kept,
+ * slices of steps that never ran hold NaN.  dgsqp_fetch_track_ref: [T][B][M][3] (v_ref, lat_ref, epsi_ref) of that launch; NaN for
+ * agents that are not TRACK and for steps that never ran.  capacity_doubles = what the array can hold (DGSQP_E_ARG when it is too small
+ * or when no such launch has run).  Launches without a cross plant run the kernels they always ran.
+ */
+int dgsqp_set_cross_plant(dgsqp_handle_t h, const dgsqp_plant_t* plant, int64_t B, const double* z0 /* [B][n_z] */);
+int dgsqp_fetch_plant_state(dgsqp_handle_t h, double* z /* [T+1][B][n_z] */, int64_t capacity_doubles);
+int dgsqp_fetch_track_ref(dgsqp_handle_t h, double* out /* [T][B][M][3] */, int64_t capacity_doubles);
 
 /*
  * Device-resident variant used by bench.py: inputs are staged once with

@@ -25,6 +25,9 @@ before its stage 0 (``step_batch(..., u_prev=True)``) -- other solves, so other 
 ``--kinds ...,hold`` adds ``hold`` (named in ``--kinds`` only): the ``plant`` launch with a held plan (``closed_loop.PlanHold``, on_fail 'reference'), once per value of
 ``--replan-every`` (default 1).  R = 1 is the ``plant`` launch's own chains through the held-plan kernel (asserted), so its time stands against ``plant``'s; R > 1 follows each
 accepted plan for R control steps -- other chains -- and the report counts the solves actually run and the held steps.
+``--kinds ...,cross`` with ``--model kinematic`` adds ``cross`` (named in ``--kinds`` only): the kinematic curve game (N = 25) on DYNAMIC-bicycle plants of their own state
+(``PlantModel(own_class=True)``: the Pacejka vehicle of configs[1], the ``plant`` launch's integrator, simulation steps and delay; GAME drivers) -- other chains than ``plant``'s,
+so its time stands next to it.
 ``--kinds`` restricts the list (a library without the newer entry points can still time
 ``plain,plant``), ``--label`` names the build in the output, ``--append`` adds to ``--out`` instead of replacing it.
 
@@ -69,6 +72,7 @@ def host_loop(s, x0, u_am, T):
 KINDS = ('plain', 'plant', 'ensemble', 'ensemble+monitor', 'estimates', 'estimates+monitor', 'pid', 'replay')
 CARRY = 'carry-u-prev'          # added by --carry-u-prev (or named in --kinds): 'plain' with step_batch(..., u_prev=True)
 HOLD = 'hold'                   # named in --kinds: 'plant' with step_batch(..., hold=PlanHold(replan_every=R)) for every R of --replan-every
+CROSS = 'cross'                 # named in --kinds with --model kinematic: the kinematic game on dynamic plants, step_batch(..., plant=PlantModel(own_class=True))
 
 
 def ensemble_bench(args, g, s, x0, u_am):
@@ -79,9 +83,11 @@ def ensemble_bench(args, g, s, x0, u_am):
     kinds = [k for k in args.kinds.split(',') if k]
     if args.carry_u_prev and CARRY not in kinds:
         kinds.append(CARRY)
-    unknown = [k for k in kinds if k not in KINDS + (CARRY, HOLD)]
+    unknown = [k for k in kinds if k not in KINDS + (CARRY, HOLD, CROSS)]
     if unknown:
-        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS + (CARRY, HOLD)}')
+        raise SystemExit(f'unknown kinds {unknown}; choose from {KINDS + (CARRY, HOLD, CROSS)}')
+    if CROSS in kinds and args.model != 'kinematic':
+        raise SystemExit(f'the kind {CROSS} puts dynamic plants under a kinematic game: --model kinematic')
     base = dict(method='rk4', M=10, sim_steps=2)
     calls = {'plain': lambda: s.step_batch(x0, u_am, T)}
     if CARRY in kinds:
@@ -98,6 +104,11 @@ def ensemble_bench(args, g, s, x0, u_am):
         again = calls['replay']()
         for key in ('status', 'num_iters', 'q', 'u_plant'):
             assert np.array_equal(again[key], own[key], equal_nan=True), f'{key}: the replay of the plant launch\'s own commands differs from it'
+    if CROSS in kinds:
+        from dgsqp_amd.montecarlo import dynamic_racing_game
+        dyn = [copy.deepcopy(m.model_config) for m in dynamic_racing_game(N=5).joint_model.dynamics_models]
+        cross = closed_loop.PlantModel(dynamics_configs=dyn, own_class=True, delay_steps=[[0, 1], [0, 0]], **base)
+        calls[CROSS] = lambda: s.step_batch(x0, u_am, T, plant=cross)
     if HOLD in kinds:
         at = kinds.index(HOLD)
         kinds[at:at + 1] = [f'{HOLD} R={R}' for R in args.replan_every]
@@ -107,7 +118,7 @@ def ensemble_bench(args, g, s, x0, u_am):
             own, held = calls['plant'](), calls[f'{HOLD} R=1']()
             for key in ('status', 'num_iters', 'q', 'u_plant'):
                 assert np.array_equal(held[key], own[key], equal_nan=True), f'{key}: the held-plan launch with R = 1 differs from the plant launch'
-    if any(k not in ('plain', 'plant', 'pid', 'replay', CARRY) and not k.startswith(HOLD) for k in kinds):
+    if any(k not in ('plain', 'plant', 'pid', 'replay', CARRY, CROSS) and not k.startswith(HOLD) for k in kinds):
         cfgs = [copy.deepcopy(m.model_config) for m in g.joint_model.dynamics_models]
         spread = dict(mass=0.1, drag_coefficient=0.1, pacejka_d_front=0.1, pacejka_d_rear=0.1)
         delays = np.random.default_rng(args.seed).integers(0, 3, size=(B, len(cfgs), 2))
@@ -128,7 +139,7 @@ def ensemble_bench(args, g, s, x0, u_am):
             kern[k].append(r['kernel_ms'] / 1e3)
             last[k] = r
     ms = lambda v: f'median {np.median(v) * 1e3:8.1f} ms (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f}; spread {(max(v) - min(v)) / np.median(v) * 100:.1f} %)'
-    lines = [f'[{args.label}] closed loop, dyn_curve_N25 (BASELINE configs[1]), B = {B} chains x T = {T} steps, device-sampled inputs (seed {args.seed}); '
+    lines = [f'[{args.label}] closed loop, {args.game_name}, B = {B} chains x T = {T} steps, device-sampled inputs (seed {args.seed}); '
              f'{args.repeats} alternated repeats of every kind after one warm-up each; plant: rk4, 10 sub-steps, 2 simulation steps per control step']
     for k in kinds:
         r = last[k]
@@ -154,16 +165,20 @@ def main():
     ap.add_argument('--replan-every', type=int, nargs='+', default=[1], help='with --ensemble and the kind ' + HOLD + ': one launch kind per value R')
     ap.add_argument('--label', default='this build', help='with --ensemble: names the build in the report')
     ap.add_argument('--append', action='store_true', help='with --ensemble: add to --out instead of replacing it')
-    ap.add_argument('--model', choices=('dynamic', 'point-mass'), default='dynamic',
-                    help="the game: BASELINE configs[1] (dynamic bicycles, N = 25), or the race demo's point-mass game on its circuit (N = 20)")
+    ap.add_argument('--model', choices=('dynamic', 'point-mass', 'kinematic'), default='dynamic',
+                    help="the game: BASELINE configs[1] (dynamic bicycles, N = 25), the race demo's point-mass game on its circuit (N = 20), or the kinematic "
+                         "curve game (N = 25; for the kind " + CROSS + ')')
     ap.add_argument('--out', default=None, help='default: profiles/closed_loop_<game>.txt')
     args = ap.parse_args()
-    from dgsqp_amd.montecarlo import dynamic_racing_game, point_mass_racing_game
+    from dgsqp_amd.montecarlo import dynamic_racing_game, kinematic_racing_game, point_mass_racing_game
     from dgsqp_amd.solver import DGSQP
     if args.model == 'point-mass':
         g, game_name = point_mass_racing_game('barc', N=20), 'pm_barc_N20 (scripts/race/game_setup_unicycle.py)'
+    elif args.model == 'kinematic':
+        g, game_name = kinematic_racing_game('curve', N=25), 'kb_curve_N25 (kinematic curve game)'
     else:
         g, game_name = dynamic_racing_game(N=25, rk4_substeps=10), 'dyn_curve_N25 (BASELINE configs[1])'
+    args.game_name = game_name
     if args.out is None:
         args.out = str(ROOT / 'profiles' / f'closed_loop_{game_name.split()[0]}.txt')
     s = DGSQP(*g.solver_args(), print_method=None, qp_method='active_set')
