@@ -618,9 +618,11 @@ __device__ __noinline__ void dev_rollout_with_derivs(const Ctx& c, clptr ue, lpt
 __device__ inline void gd_store(const Ctx& c, int idx, double val) {
   if (dg_prob.gd_global) (c.ws + dg_prob.ws_gd)[idx] = val; else LP(dg_prob.L.gd)[idx] = val;
 }
+// `tang` (null unless the Hessian rows follow): every stage's tangent dx_k of input column `it`, [k][i][it] in the global scratch --
+// the rows' second-order adjoint runs over the very same vectors, so they are propagated once, here
 template <int NQA>
-__device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it);
-__device__ __noinline__ void dev_chains(const Ctx& c, clptr ue) {
+__device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it, gptr tang);
+__device__ __noinline__ void dev_chains(const Ctx& c, clptr ue, bool hessian) {
   const DgProb& D = dg_prob;
   const DgLds& L = D.L;
   lptr lds = LP(0);
@@ -634,14 +636,16 @@ __device__ __noinline__ void dev_chains(const Ctx& c, clptr ue) {
     for (int i = 0; i < D.nqa[a]; i++) lds[L.e_dJ + k * D.nq + D.qoff[a] + i] = Dx[D.qoff[a] + i];
   }
   __syncthreads();
+  gptr tang = hessian ? c.ws + D.ws_tang : nullptr;
   for (int it = TID; it < D.n; it += NT) {
     const int a = it / (D.N * DGSQP_NUA);
-    if (D.nqa[a] == 8) dev_chain_item<8>(c, ue, it); else if (D.nqa[a] == 4) dev_chain_item<4>(c, ue, it); else dev_chain_item<6>(c, ue, it);
+    if (D.nqa[a] == 8) dev_chain_item<8>(c, ue, it, tang); else if (D.nqa[a] == 4) dev_chain_item<4>(c, ue, it, tang); else dev_chain_item<6>(c, ue, it, tang);
   }
+  if (hessian) __threadfence_block();     // the tangents change lanes on their way to the rows
   __syncthreads();
 }
 template <int NQA>
-__device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it) {
+__device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it, gptr tang) {
   const DgProb& D = dg_prob;
   const DgLds& L = D.L;
   lptr lds = LP(0);
@@ -662,6 +666,10 @@ __device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it) {
     int d = D.stage_dense0[t0 + 1];  // dense gradients are ordered by stage
     for (int k = t0 + 1; k <= D.N; k++) {
       clptr xk = x + k * D.nq;
+      if (tang) {
+#pragma unroll
+        for (int i = 0; i < nqa; i++) tang[((int64_t)k * DGSQP_MAX_NQA + i) * D.n + it] = v[i];
+      }
       for (; d < D.stage_dense0[k + 1]; d++) {
         const DgDense dd = ld_dense(d);
         if (dd.kind == 0) {
@@ -767,29 +775,10 @@ __device__ __noinline__ void dev_hessian_row_generic(const Ctx& c, int row, int 
   constexpr int EE = DG_MAXEFF * DG_MAXEFF;
   constexpr int NE = NQA;            // effective variables: states 2..NQA-1, then the two inputs
   const int qa = D.qoff[a];
-  // forward tangent dx_t (block a only), t = k0+1 .. N, stored to the per-workgroup scratch (coalesced over lanes)
-  double v[NQA], w[NQA];
-  {
-    clptr B = lds + L.e_B[a] + k0 * NQA * 2;
+  // forward tangent dx_t (block a only), t = k0+1 .. N: left in the per-workgroup scratch by dev_chains (coalesced over lanes)
+  double v[NQA];
 #pragma unroll
-    for (int i = 0; i < NQA; i++) v[i] = B[i * 2 + j0];
-    for (int t = k0 + 1; t <= N; t++) {
-#pragma unroll
-      for (int i = 0; i < NQA; i++) tang[((int64_t)t * DGSQP_MAX_NQA + i) * n + row] = v[i];
-      if (t < N) {
-        clptr A = lds + L.e_A[a] + t * NQA * NQA;
-#pragma unroll
-        for (int i = 0; i < NQA; i++) {
-          double s = 0;
-#pragma unroll
-          for (int m = 0; m < NQA; m++) s += A[i * NQA + m] * v[m];
-          w[i] = s;
-        }
-#pragma unroll
-        for (int i = 0; i < NQA; i++) v[i] = w[i];
-      }
-    }
-  }
+  for (int i = 0; i < NQA; i++) v[i] = tang[((int64_t)N * DGSQP_MAX_NQA + i) * n + row];
   // backward second-order adjoint; mu is joint (n_q) because the state Hessian couples the agents
   double mu[DGSQP_MAX_AGENTS * DGSQP_MAX_NQA];
   // mu_N = L_xx,N dx_N  (v holds dx_N)
@@ -871,111 +860,94 @@ __device__ __noinline__ void dev_hessian_row_generic(const Ctx& c, int row, int 
   }
 }
 
-// uniform-model variant (every agent has NQA states): all register arrays are statically indexed
-template <int NQA, int MM>
-__device__ __noinline__ void dev_hessian_row(const Ctx& c, int row, int a, int k0, int j0) {
+// uniform-model variant (every agent has NQA states): all register arrays are statically indexed.
+// One lane per (row, block b): the second-order adjoint mu is block diagonal in its recursion -- the blocks meet only in the tangent dx_t
+// (read from the scratch by every lane) and in hz, which enters block a alone -- so each lane carries one block's mu and writes that
+// block's entries of the row.  Every entry is summed in the order the one-lane-per-row form used.
+template <int NQA>
+__device__ __noinline__ void dev_hessian_row(const Ctx& c, int row, int a, int b, int k0, int j0) {
   const DgProb& D = dg_prob;
   const DgLds& L = D.L;
   lptr lds = LP(0);
-  const int n = D.n, N = D.N;
+  const int n = D.n, N = D.N, M = D.M;
   clptr Kc = lds + L.e_K;
-  cgptr Hg = c.ws + D.ws_H;
+  gptr Hg = c.ws + D.ws_H;
   gptr tang = c.ws + D.ws_tang;
   gptr Qrow = c.ws + D.ws_q + (int64_t)row * n;
   const dgsqp_agent_t& ag = D.P.agents[a];
   constexpr int EE = DG_MAXEFF * DG_MAXEFF;
   constexpr int NU = DGSQP_NUA;
   const double wr = ag.w_rate[j0], win = ag.w_in[j0];
-  double v[NQA], w[NQA];
+  const bool own = b == a;
+  double v[NQA];
+#pragma unroll
+  for (int i = 0; i < NQA; i++) v[i] = tang[((int64_t)N * DGSQP_MAX_NQA + i) * n + row];    // dx_N
+  double mu[NQA];
   {
-    clptr B = lds + L.e_B[a] + k0 * NQA * NU;
+    clptr K = Kc + ((a * (N + 1) + N) * M + b) * 5;
 #pragma unroll
-    for (int i = 0; i < NQA; i++) v[i] = B[i * NU + j0];
-    for (int t = k0 + 1; t <= N; t++) {
-#pragma unroll
-      for (int i = 0; i < NQA; i++) tang[((int64_t)t * DGSQP_MAX_NQA + i) * n + row] = v[i];
-      if (t < N) {
-        clptr A = lds + L.e_A[a] + t * NQA * NQA;
-#pragma unroll
-        for (int i = 0; i < NQA; i++) {
-          double s = 0;
-#pragma unroll
-          for (int m = 0; m < NQA; m++) s += A[i * NQA + m] * v[m];
-          w[i] = s;
-        }
-#pragma unroll
-        for (int i = 0; i < NQA; i++) v[i] = w[i];
-      }
-    }
+    for (int i = 0; i < NQA; i++) mu[i] = 0.0;
+    mu[0] = K[0] * v[0] + K[1] * v[1];
+    mu[1] = K[1] * v[0] + K[2] * v[1];
+    mu[NQA - 1] = K[3] * v[NQA - 1];
+    mu[NQA - 2] = K[4] * v[NQA - 2];
   }
-  double mu[MM][NQA];
-  {
-    clptr K = Kc + (a * (N + 1) + N) * MM * 5;
-#pragma unroll
-    for (int b = 0; b < MM; b++) {
-#pragma unroll
-      for (int i = 0; i < NQA; i++) mu[b][i] = 0.0;
-      mu[b][0] = K[b * 5 + 0] * v[0] + K[b * 5 + 1] * v[1];
-      mu[b][1] = K[b * 5 + 1] * v[0] + K[b * 5 + 2] * v[1];
-      mu[b][NQA - 1] = K[b * 5 + 3] * v[NQA - 1];
-      mu[b][NQA - 2] = K[b * 5 + 4] * v[NQA - 2];
-    }
-  }
-  // own-block offset in the agent-major column order
   for (int t = N - 1; t >= 0; t--) {
     const bool live = t > k0;
 #pragma unroll
     for (int i = 0; i < NQA; i++) v[i] = live ? tang[((int64_t)t * DGSQP_MAX_NQA + i) * n + row] : 0.0;
-    const double du = (t == k0) ? 1.0 : 0.0;
-    cgptr Ha = Hg + (((int64_t)a * N + t) * MM + a) * EE;
     double hz[NQA];
 #pragma unroll
-    for (int e = 0; e < NQA; e++) {
-      double s = 0;
-#pragma unroll
-      for (int f = 0; f < NQA - 2; f++) s += Ha[e * DG_MAXEFF + f] * v[f + 2];
-      s += Ha[e * DG_MAXEFF + (NQA - 2 + j0)] * du;
-      hz[e] = s;
-    }
+    for (int e = 0; e < NQA; e++) hz[e] = 0.0;
     double dir0 = 0.0;   // agent a's own L_uu entry on input j0 at this stage
-    if (t == k0) dir0 = win + wr + (t + 1 < N ? wr : 0.0);
-    else if (t == k0 + 1 || t == k0 - 1) dir0 = -wr;
+    if (own) {
+      const double du = (t == k0) ? 1.0 : 0.0;
+      gptr Ha = Hg + (((int64_t)a * N + t) * M + a) * EE;
 #pragma unroll
-    for (int b = 0; b < MM; b++) {
+      for (int e = 0; e < NQA; e++) {
+        double s = 0;
+#pragma unroll
+        for (int f = 0; f < NQA - 2; f++) s += Ha[e * DG_MAXEFF + f] * v[f + 2];
+        s += Ha[e * DG_MAXEFF + (NQA - 2 + j0)] * du;
+        hz[e] = s;
+      }
+      if (t == k0) dir0 = win + wr + (t + 1 < N ? wr : 0.0);
+      else if (t == k0 + 1 || t == k0 - 1) dir0 = -wr;
+    }
+    {
       clptr B = lds + L.e_B[b] + t * NQA * NU;
 #pragma unroll
       for (int j = 0; j < NU; j++) {
         double s = 0;
 #pragma unroll
-        for (int m = 0; m < NQA; m++) s += B[m * NU + j] * mu[b][m];
-        if (b == a) s += (j == 0 ? hz[NQA - 2] : hz[NQA - 1]) + (j == j0 ? dir0 : 0.0);
+        for (int m = 0; m < NQA; m++) s += B[m * NU + j] * mu[m];
+        if (own) s += (j == 0 ? hz[NQA - 2] : hz[NQA - 1]) + (j == j0 ? dir0 : 0.0);
         Qrow[(b * N + t) * NU + j] = s;
       }
     }
     if (t > 0) {
-      clptr K = Kc + (a * (N + 1) + t) * MM * 5;
+      clptr K = Kc + ((a * (N + 1) + t) * M + b) * 5;
+      clptr A = lds + L.e_A[b] + t * NQA * NQA;
+      double nm[NQA];
 #pragma unroll
-      for (int b = 0; b < MM; b++) {
-        clptr A = lds + L.e_A[b] + t * NQA * NQA;
-        double nm[NQA];
+      for (int i = 0; i < NQA; i++) {
+        double s = 0;
 #pragma unroll
-        for (int i = 0; i < NQA; i++) {
-          double s = 0;
-#pragma unroll
-          for (int m = 0; m < NQA; m++) s += A[m * NQA + i] * mu[b][m];
-          nm[i] = s;
-        }
-        // state-Hessian columns (v is zero when t <= k0, so no branch is needed)
-        nm[0] += K[b * 5 + 0] * v[0] + K[b * 5 + 1] * v[1];
-        nm[1] += K[b * 5 + 1] * v[0] + K[b * 5 + 2] * v[1];
-        nm[NQA - 1] += K[b * 5 + 3] * v[NQA - 1];
-        nm[NQA - 2] += K[b * 5 + 4] * v[NQA - 2];
-        const double own = b == a ? 1.0 : 0.0;
-#pragma unroll
-        for (int f = 0; f < NQA - 2; f++) nm[f + 2] += own * hz[f];
-#pragma unroll
-        for (int i = 0; i < NQA; i++) mu[b][i] = nm[i];
+        for (int m = 0; m < NQA; m++) s += A[m * NQA + i] * mu[m];
+        nm[i] = s;
       }
+      // state-Hessian columns (v is zero when t <= k0, so no branch is needed)
+      nm[0] += K[0] * v[0] + K[1] * v[1];
+      nm[1] += K[1] * v[0] + K[2] * v[1];
+      nm[NQA - 1] += K[3] * v[NQA - 1];
+      nm[NQA - 2] += K[4] * v[NQA - 2];
+      // hz enters block a only (nm is never -0.0 here -- its sums start from +0.0 -- so the other blocks' former `+ 0.0 * hz` changed nothing)
+      if (own) {
+#pragma unroll
+        for (int f = 0; f < NQA - 2; f++) nm[f + 2] += hz[f];
+      }
+#pragma unroll
+      for (int i = 0; i < NQA; i++) mu[i] = nm[i];
     }
   }
 }
@@ -985,16 +957,27 @@ __device__ __noinline__ void dev_hessian_row(const Ctx& c, int row, int a, int k
 // dL^a/du_i, i.e. one Hessian-vector product of agent a's Lagrangian L^a = J^a + l^T C with e_i:
 //   costates      lam_k  = L_x,k + A_k^T lam_{k+1}                                    (once per agent)
 //   H_k^b         = sum_o lam_{k+1}[b,o] grad^2 f^b_{k,o}   (Taylor tensor contracted with the costate, all (a,k,b) in parallel)
-//   tangent       dx_{t+1} = A_t dx_t + B_t e_i                                        (one lane per i)
+//   tangent       dx_{t+1} = A_t dx_t + B_t e_i                                        (one lane per i: dev_chains leaves it in the scratch)
 //   2nd adjoint   mu_t   = A_t^T mu_{t+1} + (L_xx,t + H_xx,t) dx_t + H_xu,t du_t
 //   row entries   Q[i, (b,t,j)] = B_t^T mu_{t+1} + H_ux,t dx_t + (H_uu,t + L_uu) du_t
 // Mathematically identical to the reference's backward DP (DGSQP.py:679-727, :828-877, f_Q :920-934) and to its
-// own f_Duu_L (:937-941); here all N*n_u rows are independent lanes with 25 uniform steps each.
+// own f_Duu_L (:937-941); here all N*n_u rows -- and, mu being block diagonal in its recursion, the M blocks of each -- are independent
+// lanes with 25 uniform steps each.
 // ------------------------------------------------------------------------------------------------
 // Costates of every agent's Lagrangian L^a = J^a + lm^T C along the current trajectory (multipliers lm in LDS):
 //   lam^a_N = L^a_x,N ,  lam^a_k = L^a_x,k + A_k^T lam^a_{k+1}     (joint n_q vectors, e_lam[a][k][.])
 // Stage 0 also leaves the compact state-Hessian columns (e_K) the second-order pass needs.  Used by the game Hessian
 // and by the merit of a line-search trial point (gradient of the Lagrangians without forming G).
+// WITH_K = false leaves e_K alone: only the Hessian rows read the columns, a trial merit needs the costates alone.
+// ------------------------------------------------------------------------------------------------
+// One costate component of stage k: s + sum_m A_k[m][col] lam_{k+1}[m], lam_{k+1}[m] held by lane qo + m of the wavefront (`next`)
+template <int NQA>
+__device__ inline double dev_costate_step(clptr A, int col, int qo, double s, double next) {
+#pragma unroll
+  for (int m = 0; m < NQA; m++) s += A[m * NQA + col] * __shfl(next, qo + m);
+  return s;
+}
+template <bool WITH_K>
 __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
   const DgProb& D = dg_prob;
   const DgLds& L = D.L;
@@ -1009,7 +992,7 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
   // vectors lived in scratch memory, 57 scratch accesses inside the loops of a function every line-search trial calls)
   auto stage = [&](int a, int k, lptr Dx, auto Kl) {
     for (int i = 0; i < nq; i++) Dx[i] = 0.0;
-    for (int i = 0; i < M * 5; i++) Kl[i] = 0.0;
+    if constexpr (WITH_K) for (int i = 0; i < M * 5; i++) Kl[i] = 0.0;
     clptr xk = x + k * nq;
     const dgsqp_agent_t& ag = D.P.agents[a];
     const int ia = D.qoff[a];
@@ -1018,7 +1001,7 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
       if (ag.w_goal[i] != 0.0) {   // weights sit on x, y and the last two states only (checked at create)
         const double w = (k == N ? ag.goal_term_mult : 1.0) * ag.w_goal[i];
         Dx[ia + i] += w * (xk[ia + i] - ag.goal[i]);
-        Kl[a * 5 + (i == 0 ? 0 : (i == 1 ? 2 : (i == D.nqa[a] - 1 ? 3 : 4)))] += w;
+        if constexpr (WITH_K) Kl[a * 5 + (i == 0 ? 0 : (i == 1 ? 2 : (i == D.nqa[a] - 1 ? 3 : 4)))] += w;
       }
     for (int b = 0; b < M; b++) {
       if (b == a) continue;
@@ -1027,7 +1010,7 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
         const int ea = ia + D.eyidx[a], eb = ib + D.eyidx[b];
         const double dd = xk[ea] - xk[eb];
         Dx[ea] += ag.w_block * dd; Dx[eb] -= ag.w_block * dd;
-        Kl[a * 5 + 3] += ag.w_block; Kl[b * 5 + 3] -= ag.w_block;
+        if constexpr (WITH_K) { Kl[a * 5 + 3] += ag.w_block; Kl[b * 5 + 3] -= ag.w_block; }
       }
       if (ag.w_obs != 0.0) {
         const double dx = xk[ia] - xk[ib], dy = xk[ia + 1] - xk[ib + 1];
@@ -1036,9 +1019,11 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
         if (z > 0) {
           const double ex = dx / r, ey = dy / r;
           Dx[ia] -= ag.w_obs * z * ex; Dx[ia + 1] -= ag.w_obs * z * ey; Dx[ib] += ag.w_obs * z * ex; Dx[ib + 1] += ag.w_obs * z * ey;
-          const double hxx = ag.w_obs * (ex * ex - z * (1 - ex * ex) / r), hxy = ag.w_obs * (ex * ey + z * ex * ey / r), hyy = ag.w_obs * (ey * ey - z * (1 - ey * ey) / r);
-          Kl[a * 5 + 0] += hxx; Kl[a * 5 + 1] += hxy; Kl[a * 5 + 2] += hyy;
-          Kl[b * 5 + 0] -= hxx; Kl[b * 5 + 1] -= hxy; Kl[b * 5 + 2] -= hyy;
+          if constexpr (WITH_K) {
+            const double hxx = ag.w_obs * (ex * ex - z * (1 - ex * ex) / r), hxy = ag.w_obs * (ex * ey + z * ex * ey / r), hyy = ag.w_obs * (ey * ey - z * (1 - ey * ey) / r);
+            Kl[a * 5 + 0] += hxx; Kl[a * 5 + 1] += hxy; Kl[a * 5 + 2] += hyy;
+            Kl[b * 5 + 0] -= hxx; Kl[b * 5 + 1] -= hxy; Kl[b * 5 + 2] -= hyy;
+          }
         }
       }
     }
@@ -1052,8 +1037,10 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
         if (ag.comp_type == DGSQP_COMP_ATAN) {
           const double w = 1.0 + dl * dl;
           Dx[sb] += ag.w_comp / w; Dx[sa] -= ag.w_comp / w;
-          const double f2 = -2.0 * ag.w_comp * dl / (w * w);
-          Kl[a * 5 + 4] += f2; Kl[b * 5 + 4] -= f2;
+          if constexpr (WITH_K) {
+            const double f2 = -2.0 * ag.w_comp * dl / (w * w);
+            Kl[a * 5 + 4] += f2; Kl[b * 5 + 4] -= f2;
+          }
         } else { Dx[sb] += ag.w_comp; Dx[sa] -= ag.w_comp; }
       }
     }
@@ -1066,7 +1053,7 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
         const int ip = D.qoff[R.a], iq = D.qoff[R.b];
         const double dx = xk[ip] - xk[iq], dy = xk[ip + 1] - xk[iq + 1];
         Dx[ip] -= 2 * lr * dx; Dx[ip + 1] -= 2 * lr * dy; Dx[iq] += 2 * lr * dx; Dx[iq + 1] += 2 * lr * dy;
-        if (R.a == a || R.b == a) {
+        if constexpr (WITH_K) if (R.a == a || R.b == a) {
           const int other = R.a == a ? R.b : R.a;
           Kl[a * 5 + 0] -= 2 * lr; Kl[a * 5 + 2] -= 2 * lr;
           Kl[other * 5 + 0] += 2 * lr; Kl[other * 5 + 2] += 2 * lr;
@@ -1085,7 +1072,7 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
     if (D.tab_const) stage(a, k, Dxs + (a * (N + 1) + k) * nq, (gptr)(c.ws + D.ws_K) + (a * (N + 1) + k) * M * 5);
     else stage(a, k, Dxs + (a * (N + 1) + k) * nq, Kc + (a * (N + 1) + k) * M * 5);
   }
-  if (D.tab_const) __threadfence_block();
+  if (WITH_K && D.tab_const) __threadfence_block();
   __syncthreads();
   // ---- 1. costates: one wavefront per agent, lane = state component (in place where e_Dxs shares e_lam's slot)
   {
@@ -1099,13 +1086,14 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
       for (int k = N - 1; k >= 1; k--) {
         // lam_k[i] = Dx_k[i] + sum_m A_k[m][i] lam_{k+1}[m]   (A block diagonal: m in the block of i)
         double s = i < nq ? Dxs[(a * (N + 1) + k) * nq + i] : 0.0;
-        if (i < nq) {
+        if (i < nq) {      // lam_{k+1} of the block comes from its lanes' registers (a cross-lane move), not back from e_lam
           clptr A = lds + L.e_A[b] + k * nqa * nqa;
-          clptr ln = lam + (a * (N + 1) + k + 1) * nq + qo;
-          for (int m = 0; m < nqa; m++) s += A[m * nqa + (i - qo)] * ln[m];
+          if (nqa == 8) s = dev_costate_step<8>(A, i - qo, qo, s, cur);
+          else if (nqa == 4) s = dev_costate_step<4>(A, i - qo, qo, s, cur);
+          else s = dev_costate_step<6>(A, i - qo, qo, s, cur);
           lam[(a * (N + 1) + k) * nq + i] = s;
+          cur = s;
         }
-        __builtin_amdgcn_wave_barrier();
       }
     }
   }
@@ -1127,7 +1115,7 @@ __device__ __noinline__ void dev_hessian_adjoint(const Ctx& c) {
   const gptr T2base = c.ws + D.ws_t2;
   constexpr int EE = DG_MAXEFF * DG_MAXEFF;
   PROF_BEGIN(ph0);
-  dev_costates(c, lds + L.l);
+  dev_costates<true>(c, lds + L.l);
   PROF_END(PH_H_COST, ph0);
   PROF_BEGIN(ph1);
   // ---- 2. H[a][k][b] = sum_o lam^a_{k+1}[b,o] * Hessian of f^b_{k,o} in effective variables (interpolated from the
@@ -1140,9 +1128,11 @@ __device__ __noinline__ void dev_hessian_adjoint(const Ctx& c) {
   int ndmax = 0;
   for (int b = 0; b < M; b++) ndmax = D.ndir[b] > ndmax ? D.ndir[b] : ndmax;
   const bool use_cv = M * N * M * ndmax <= cvcap;
+  // Only the own blocks b == a are formed: the tangent of one of agent a's inputs lives in block a, so the rows read no other block
+  // (cv and Hg keep their [a][k][b] layout; the use_cv threshold above is the one the full set of blocks had)
   if (use_cv) {
-    for (int it = TID; it < M * N * M * ndmax; it += NT) {
-      const int dir = it % ndmax, b = (it / ndmax) % M, k = (it / (ndmax * M)) % N, a = it / (ndmax * M * N);
+    for (int it = TID; it < M * N * ndmax; it += NT) {
+      const int dir = it % ndmax, k = (it / ndmax) % N, a = it / (ndmax * N), b = a;
       double sv = 0.0;
       if (dir < D.ndir[b]) {
         cgptr T2 = T2base + D.t2off[b] + (int64_t)k * D.t2k[b];
@@ -1150,13 +1140,13 @@ __device__ __noinline__ void dev_hessian_adjoint(const Ctx& c) {
         const int nd = D.ndir[b];
         for (int o = 0; o < D.nqa[b]; o++) sv += lk[o] * T2[o * nd + dir];
       }
-      cvb[it] = sv;
+      cvb[((a * N + k) * M + b) * ndmax + dir] = sv;
     }
     __syncthreads();
   }
   // (b) Hessian entries from the contracted coefficients
-  for (int it = TID; it < M * N * M * EE; it += NT) {
-    const int e = it % EE, b = (it / EE) % M, k = (it / (EE * M)) % N, a = it / (EE * M * N);
+  for (int it = TID; it < M * N * EE; it += NT) {
+    const int e = it % EE, k = (it / EE) % N, a = it / (EE * N), b = a;
     const int i = e / DG_MAXEFF, j = e % DG_MAXEFF, ne = D.neff[b];
     double h = 0.0;
     if (i < ne && j < ne) {
@@ -1174,45 +1164,36 @@ __device__ __noinline__ void dev_hessian_adjoint(const Ctx& c) {
         else { for (int o = 0; o < D.nqa[b]; o++) sv += lk[o] * (T2[o * nd + dirp] - T2[o * nd + lo] - T2[o * nd + hi]); h = sv; }
       }
     }
-    Hg[it] = h;
+    Hg[(((int64_t)a * N + k) * M + b) * EE + e] = h;
   }
+  __threadfence_block();
   __syncthreads();
   PROF_END(PH_H_CONTR, ph1);
   PROF_BEGIN(ph2);
-  // ---- 3. one lane per row of Q
-  for (int row = TID; row < n; row += NT) {
-    const int a = row / (N * DGSQP_NUA), rem = row % (N * DGSQP_NUA), k0 = rem / DGSQP_NUA, j0 = rem % DGSQP_NUA;
-    if (D.tab_const) {
-      if (D.nqa[a] == 8) dev_hessian_row_generic<8, true>(c, row, a, k0, j0);
-      else if (D.nqa[a] == 4) dev_hessian_row_generic<4, true>(c, row, a, k0, j0);
-      else dev_hessian_row_generic<6, true>(c, row, a, k0, j0);
-    } else if (!D.uniform_nqa) {
-      if (D.nqa[a] == 8) dev_hessian_row_generic<8>(c, row, a, k0, j0);
-      else if (D.nqa[a] == 4) dev_hessian_row_generic<4>(c, row, a, k0, j0);
-      else dev_hessian_row_generic<6>(c, row, a, k0, j0);
-    } else if (D.nqa[0] == 8) {
-      switch (M) {
-        case 1: dev_hessian_row<8, 1>(c, row, a, k0, j0); break;
-        case 2: dev_hessian_row<8, 2>(c, row, a, k0, j0); break;
-        case 3: dev_hessian_row<8, 3>(c, row, a, k0, j0); break;
-        case 4: dev_hessian_row<8, 4>(c, row, a, k0, j0); break;
-        default: dev_hessian_row_generic<8>(c, row, a, k0, j0); break;   // 5, 6 agents
-      }
-    } else if (D.nqa[0] == 4) {
-      switch (M) {
-        case 1: dev_hessian_row<4, 1>(c, row, a, k0, j0); break;
-        case 2: dev_hessian_row<4, 2>(c, row, a, k0, j0); break;
-        case 3: dev_hessian_row<4, 3>(c, row, a, k0, j0); break;
-        case 4: dev_hessian_row<4, 4>(c, row, a, k0, j0); break;
-        default: dev_hessian_row_generic<4>(c, row, a, k0, j0); break;   // 5, 6 agents
-      }
-    } else {
-      switch (M) {
-        case 1: dev_hessian_row<6, 1>(c, row, a, k0, j0); break;
-        case 2: dev_hessian_row<6, 2>(c, row, a, k0, j0); break;
-        case 3: dev_hessian_row<6, 3>(c, row, a, k0, j0); break;
-        case 4: dev_hessian_row<6, 4>(c, row, a, k0, j0); break;
-        default: dev_hessian_row_generic<6>(c, row, a, k0, j0); break;   // 5, 6 agents
+  // ---- 3. rows of Q.  Uniform models of up to 4 agents: one lane per (row, block), the own blocks (the longer items: they form hz) first and
+  //         each group of blocks starting on a wavefront of its own; otherwise one lane per row
+  if (!D.tab_const && D.uniform_nqa && M <= 4) {
+    const int npad = (n + 63) & ~63;
+    for (int it = TID; it < M * npad; it += NT) {
+      const int shift = it / npad, row = it % npad;
+      if (row >= n) continue;
+      const int a = row / (N * DGSQP_NUA), rem = row % (N * DGSQP_NUA), k0 = rem / DGSQP_NUA, j0 = rem % DGSQP_NUA;
+      const int b = a + shift < M ? a + shift : a + shift - M;
+      if (D.nqa[0] == 8) dev_hessian_row<8>(c, row, a, b, k0, j0);
+      else if (D.nqa[0] == 4) dev_hessian_row<4>(c, row, a, b, k0, j0);
+      else dev_hessian_row<6>(c, row, a, b, k0, j0);
+    }
+  } else {
+    for (int row = TID; row < n; row += NT) {
+      const int a = row / (N * DGSQP_NUA), rem = row % (N * DGSQP_NUA), k0 = rem / DGSQP_NUA, j0 = rem % DGSQP_NUA;
+      if (D.tab_const) {
+        if (D.nqa[a] == 8) dev_hessian_row_generic<8, true>(c, row, a, k0, j0);
+        else if (D.nqa[a] == 4) dev_hessian_row_generic<4, true>(c, row, a, k0, j0);
+        else dev_hessian_row_generic<6, true>(c, row, a, k0, j0);
+      } else {      // mixed models, or 5 and 6 agents
+        if (D.nqa[a] == 8) dev_hessian_row_generic<8>(c, row, a, k0, j0);
+        else if (D.nqa[a] == 4) dev_hessian_row_generic<4>(c, row, a, k0, j0);
+        else dev_hessian_row_generic<6>(c, row, a, k0, j0);
       }
     }
   }
@@ -1272,7 +1253,7 @@ __device__ inline void dev_evaluate_derivs(const Ctx& c, bool hessian) {
     if (TID == 0 && LP(L.scal)[DG_XVALID] == 1.0) LP(L.scal)[DG_XVALID] = 2.0;
   }
   else { PROF_BEGIN(pt_); dev_dyn_derivs<1>(c, ue); PROF_END(PH_DERIV1, pt_); }
-  { PROF_BEGIN(pt_); dev_chains(c, ue); PROF_END(PH_CHAINS, pt_); }
+  { PROF_BEGIN(pt_); dev_chains(c, ue, hessian); PROF_END(PH_CHAINS, pt_); }
   if (hessian) {
     PROF_BEGIN(pt_);
     dev_hessian_adjoint(c);

@@ -1166,7 +1166,7 @@ __device__ __noinline__ double dev_phi_trial_adjoint(const Ctx& c, double alpha,
     sg += g[r];
   }
   __syncthreads();
-  dev_costates(c, lt);
+  dev_costates<false>(c, lt);   // the state-Hessian columns e_K are the Hessian rows' business
   clptr lam = lds + L.e_lam;
   double dd = 0;
   for (int i = TID; i < D.n; i += NT) {
