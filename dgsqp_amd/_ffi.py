@@ -127,6 +127,28 @@ class TimingT(C.Structure):
                 ('grid', C.c_int32), ('block', C.c_int32)]
 
 
+class MpcT(C.Structure):
+    """dgsqp_mpc_t: the reference tracker's record (ltv_mpc.CA_LTV_MPC lowers to it)."""
+    _fields_ = [('agent', C.c_int32), ('N', C.c_int32), ('qp_iters', C.c_int32), ('zero_du', C.c_int32), ('damping', C.c_double),
+                ('w_q', C.c_double * MAX_NQA), ('c_N', C.c_double * MAX_NQA), ('w_u', dbl2), ('w_du', dbl2),
+                ('q_ub', C.c_double * MAX_NQA), ('q_lb', C.c_double * MAX_NQA), ('u_ub', dbl2), ('u_lb', dbl2), ('du_ub', dbl2), ('du_lb', dbl2),
+                ('n_soft', C.c_int32), ('reserved_', C.c_int32), ('soft_idx', C.c_int32 * MAX_NQA),
+                ('soft_quad', C.c_double * MAX_NQA), ('soft_lin', C.c_double * MAX_NQA), ('obs_r', C.c_double)]
+
+
+class MpcRowT(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('stage', C.c_int32), ('index', C.c_int32), ('sign', C.c_int32)]
+
+
+class MpcDimsT(C.Structure):
+    _fields_ = [('n', C.c_int32), ('n_rows', C.c_int32), ('len_D', C.c_int32), ('n_q', C.c_int32), ('lds_bytes', C.c_int32),
+                ('reserved_', C.c_int32), ('workspace_bytes', C.c_int64)]
+
+
+MPC_ROW_RATE, MPC_ROW_SLACK, MPC_ROW_INPUT, MPC_ROW_STATE, MPC_ROW_SOFT, MPC_ROW_OBS = range(6)     # DGSQP_MPC_ROW_*
+MPC_NMAX = 128                                                                                      # DGSQP_MPC_NMAX
+E_ARG, E_DEVICE, E_NOMEM, E_TOO_LARGE = -1, -2, -3, -4                                              # DGSQP_E_*
+
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
 _PF = C.POINTER(C.c_float)
@@ -193,6 +215,11 @@ SIGNATURES = {
     'dgsqp_gather_stats': (C.c_int, [_H, C.c_int64, C.c_void_p]),
     'dgsqp_comm_barrier': (C.c_int, [_H]),
     'dgsqp_comm_allreduce_max': (C.c_int, [_H, _PD, C.c_int]),
+    'dgsqp_set_mpc': (C.c_int, [_H, C.POINTER(MpcT)]),
+    'dgsqp_mpc_dims': (C.c_int, [_H, C.POINTER(MpcDimsT), C.POINTER(MpcRowT), C.c_int64]),
+    'dgsqp_mpc_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _TM]),
+    'dgsqp_set_mpc_log': (C.c_int, [_H, C.c_int]),
+    'dgsqp_fetch_mpc_log': (C.c_int, [_H, _PD, _PD, _PD, C.c_int64]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)
 

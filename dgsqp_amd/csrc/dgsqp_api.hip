@@ -128,6 +128,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 #include "dgsqp_closed_loop.h"
 #include "dgsqp_pid.h"
 #include "dgsqp_sampler.h"
+#include "dgsqp_mpc.h"
 
 // Test hook: one _evaluate(hessian=True) (+ dual init) per scenario, results expanded to dense arrays.
 __global__ void __launch_bounds__(DG_BLOCK, 2)
@@ -341,6 +342,17 @@ struct DgUPrevState {
   std::vector<double> cl_host;        // u_prev0 [cl_B][n_u]
 };
 
+// The tracker of dgsqp_set_mpc: the resolved device record (pointers are filled per launch), its row table and the log of the last launch.
+struct DgMpcState {
+  bool set = false;
+  dg_mpc::DgMpcDev dev;
+  std::vector<dgsqp_mpc_row_t> rows;
+  bool log_on = false;
+  double *logD = nullptr, *logDb = nullptr, *loglam = nullptr;    // device, of the last logged launch
+  int64_t log_B = 0;
+  int log_iters = 0, log_lenD = 0, log_rows = 0;
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -368,6 +380,7 @@ struct dgsqp_solver {
   DgCrossState cross;
   DgSide side;                             // ... and their device buffers
   DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
+  DgMpcState mpc;                          // the reference tracker (dgsqp_set_mpc)
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -399,6 +412,8 @@ static thread_local std::string g_create_err;
   } while (0)
 
 #include "dgsqp_comm.h"
+
+static void mpc_log_free(dgsqp_solver* h);
 
 static void rec_free(DgRecords& S) {
   for (int r = 0; r < DG_REC_COUNT; r++) { if (S.p[r]) (void)hipFree(S.p[r]); S.p[r] = nullptr; S.bytes[r] = 0; }
@@ -1049,6 +1064,7 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->up.staged.p) (void)hipFree(h->up.staged.p);
   if (h->d_coop) (void)hipFree(h->d_coop);
   if (h->d_coop_payload) (void)hipFree(h->d_coop_payload);
+  mpc_log_free(h);
   {
     std::lock_guard<std::mutex> lk(g_reg_mutex);
     DgParkPool& pool = g_park[h->device & 63];
@@ -1803,6 +1819,225 @@ int dgsqp_fetch_trace(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
 int dgsqp_set_iterate_log(dgsqp_handle_t h, int records_per_scenario) { return h ? log_set(h, h->itlog, records_per_scenario) : DGSQP_E_ARG; }
 int dgsqp_fetch_iterate_log(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
   return h ? log_fetch(h, h->itlog, out, capacity_doubles, "no iterate log recorded", "iterate-log buffer too small: need ") : DGSQP_E_ARG;
+}
+
+// ---- the reference tracker (dgsqp_mpc.h) ----
+static void mpc_log_free(dgsqp_solver* h) {
+  DgMpcState& S = h->mpc;
+  if (S.logD) (void)hipFree(S.logD);
+  if (S.logDb) (void)hipFree(S.logDb);
+  if (S.loglam) (void)hipFree(S.loglam);
+  S.logD = S.logDb = S.loglam = nullptr;
+  S.log_B = 0;
+}
+// Validates the record against the handle's game and lays the tracker out: the row table, the LDS arena behind DgLds.scr and the
+// workgroup's scratch.  DGSQP_E_ARG / DGSQP_E_TOO_LARGE with the reason in msg.
+static int mpc_plan(const DgProb& D, const dgsqp_mpc_t& c, dg_mpc::DgMpcDev& M, std::vector<dgsqp_mpc_row_t>& rows, std::string& msg) {
+  auto bad = [&](const std::string& m) { msg = "mpc: " + m; return DGSQP_E_ARG; };
+  if (c.agent < 0 || c.agent >= D.M) return bad("agent " + std::to_string(c.agent) + " is outside the game's 0.." + std::to_string(D.M - 1));
+  if (c.N < 1) return bad("N < 1");
+  if (c.qp_iters < 1) return bad("qp_iters < 1");
+  if (!(c.damping >= 0.0 && c.damping <= 1.0)) return bad("damping outside [0, 1]");
+  const int nq = D.nqa[c.agent], nu = DGSQP_NUA;
+  if (c.n_soft < 0 || c.n_soft > 1) return bad("n_soft outside 0..1 (with more soft states the reference's rows overwrite one another)");
+  for (int j = 0; j < nu; j++) {
+    if (!(c.w_du[j] > 0.0) || !std::isfinite(c.w_du[j])) return bad("w_du must be positive for every channel (the QP is solved exactly: it has to be strictly convex)");
+    if (!(c.w_u[j] >= 0.0) || !std::isfinite(c.w_u[j])) return bad("w_u must be finite and non-negative");
+    if (std::isnan(c.u_ub[j]) || std::isnan(c.u_lb[j]) || std::isnan(c.du_ub[j]) || std::isnan(c.du_lb[j])) return bad("a bound is NaN");
+  }
+  for (int i = 0; i < nq; i++) {
+    if (!(c.w_q[i] >= 0.0) || !std::isfinite(c.w_q[i])) return bad("w_q must be finite and non-negative");
+    if (!std::isfinite(c.c_N[i])) return bad("c_N must be finite");
+    if (std::isnan(c.q_ub[i]) || std::isnan(c.q_lb[i])) return bad("a bound is NaN");
+  }
+  for (int i = 0; i < c.n_soft; i++) {
+    if (c.soft_idx[i] < 0 || c.soft_idx[i] >= nq) return bad("soft state index out of range");
+    if (!(c.soft_quad[i] > 0.0) || !std::isfinite(c.soft_quad[i]) || !(c.soft_lin[i] >= 0.0) || !std::isfinite(c.soft_lin[i])) return bad("soft_quad must be positive and soft_lin non-negative");
+    if (!std::isfinite(c.q_ub[c.soft_idx[i]]) || !std::isfinite(c.q_lb[c.soft_idx[i]])) return bad("a soft state needs finite bounds");
+  }
+  if (!(c.obs_r >= 0.0) || !std::isfinite(c.obs_r)) return bad("obs_r must be finite and non-negative");
+  const int64_t n64 = (int64_t)c.N * nu + 2 * c.n_soft;
+  if (n64 > DGSQP_MPC_NMAX) { msg = "mpc: N n_u + 2 n_soft = " + std::to_string(n64) + " condensed variables exceed " + std::to_string(DGSQP_MPC_NMAX); return DGSQP_E_TOO_LARGE; }
+  memset(&M, 0, sizeof M);
+  M.c = c;
+  const int N = c.N, n = (int)n64, ns = c.n_soft, nz = nq + nu;
+  M.nqa = nq; M.nz = nz; M.n = n; M.ns = ns; M.mdl = D.mdl[c.agent]; M.spl = D.P.track_kind == DGSQP_TRACK_SPLINE;
+  M.lenD = (N + 1) * nz + N * nu + 2 * ns;
+  M.dt = D.P.dt; M.omd = 1.0 - c.damping;
+  // rows: a bound of magnitude >= 1e9 (the reference's 1e10 "none", +-inf) generates none
+  rows.clear();
+  auto fin = [](double v) { return std::fabs(v) < 1e9; };
+  auto is_soft = [&](int i) { for (int s = 0; s < ns; s++) if (c.soft_idx[s] == i) return true; return false; };
+  for (int k = 0; k < N; k++)
+    for (int j = 0; j < nu; j++) {
+      if (fin(c.du_ub[j])) rows.push_back({DGSQP_MPC_ROW_RATE, k, j, 1});
+      if (fin(c.du_lb[j])) rows.push_back({DGSQP_MPC_ROW_RATE, k, j, -1});
+    }
+  for (int i = 0; i < 2 * ns; i++) rows.push_back({DGSQP_MPC_ROW_SLACK, 0, i, -1});
+  for (int k = 1; k <= N; k++)
+    for (int j = 0; j < nu; j++) {
+      if (fin(c.u_ub[j])) rows.push_back({DGSQP_MPC_ROW_INPUT, k, j, 1});
+      if (fin(c.u_lb[j])) rows.push_back({DGSQP_MPC_ROW_INPUT, k, j, -1});
+    }
+  for (int k = 1; k <= N; k++)
+    for (int i = 0; i < nq; i++) {
+      if (is_soft(i)) continue;
+      if (fin(c.q_ub[i])) rows.push_back({DGSQP_MPC_ROW_STATE, k, i, 1});
+      if (fin(c.q_lb[i])) rows.push_back({DGSQP_MPC_ROW_STATE, k, i, -1});
+    }
+  for (int s = 0; s < ns; s++)
+    for (int k = 1; k <= N; k++) { rows.push_back({DGSQP_MPC_ROW_SOFT, k, s, 1}); rows.push_back({DGSQP_MPC_ROW_SOFT, k, s, -1}); }
+  if (c.obs_r > 0.0) for (int k = 1; k <= N; k++) rows.push_back({DGSQP_MPC_ROW_OBS, k, 0, 1});
+  M.nrows = (int)rows.size();
+  M.max_steps = 20 * n + 2 * M.nrows + 100;
+  // LDS, behind the game's persistent part (the track and atan tables f_c reads)
+  int o = D.L.scr;
+  auto take = [&](int cnt) { int r = o; o += (cnt + 1) & ~1; return r; };
+  M.o_J = take(n * (n + 1) / 2);
+  M.o_g = take(n); M.o_y = take(n); M.o_x = take(n); M.o_a = take(n); M.o_d = take(n); M.o_z = take(n); M.o_w = take(n); M.o_r = take(n); M.o_lam = take(n);
+  M.o_act = take((n + 2) / 2); M.o_D = take(M.lenD); M.o_Db = take(M.lenD); M.o_P0 = take(nz); M.o_flag = take((M.nrows + 2) / 2);
+  M.o_end = o;
+  if ((long)o * 8 > DG_LDS_LIMIT) {
+    msg = "mpc: the tracker needs " + std::to_string((long)o * 8) + " B of LDS per workgroup (limit " + std::to_string(DG_LDS_LIMIT) + "): N=" + std::to_string(N) + " n=" + std::to_string(n);
+    return DGSQP_E_TOO_LARGE;
+  }
+  int64_t w = 0;
+  auto wtake = [&](int64_t cnt) { int64_t r = w; w += (cnt + 31) / 32 * 32; return r; };
+  M.ws_AB = wtake((int64_t)N * nq * nz); M.ws_f = wtake((int64_t)N * nq); M.ws_gk = wtake((int64_t)N * nq); M.ws_qbar = wtake((int64_t)(N + 1) * nq);
+  M.ws_S = wtake((int64_t)N * nq * n); M.ws_Qm = wtake((int64_t)n * n); M.ws_Ri = wtake((int64_t)n * n);
+  M.ws_doubles = w;
+  return DGSQP_OK;
+}
+
+int dgsqp_set_mpc(dgsqp_handle_t h, const dgsqp_mpc_t* mpc) {
+  if (!h) return DGSQP_E_ARG;
+  if (!mpc) { h->mpc.set = false; h->mpc.rows.clear(); return DGSQP_OK; }
+  dg_mpc::DgMpcDev M;
+  std::vector<dgsqp_mpc_row_t> rows;
+  std::string msg;
+  const int rc = mpc_plan(h->hp, *mpc, M, rows, msg);
+  if (rc) { h->err = msg; return rc; }
+  h->mpc.dev = M;
+  h->mpc.rows.swap(rows);
+  h->mpc.set = true;
+  return DGSQP_OK;
+}
+
+int dgsqp_mpc_dims(dgsqp_handle_t h, dgsqp_mpc_dims_t* out, dgsqp_mpc_row_t* rows, int64_t row_capacity) {
+  if (!h || !out) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
+  if (!h->mpc.set) { h->err = "mpc: no tracker set (dgsqp_set_mpc)"; return DGSQP_E_ARG; }
+  const dg_mpc::DgMpcDev& M = h->mpc.dev;
+  memset(out, 0, sizeof *out);
+  out->n = M.n; out->n_rows = M.nrows; out->len_D = M.lenD; out->n_q = M.nqa; out->lds_bytes = M.o_end * 8;
+  out->workspace_bytes = M.ws_doubles * (int64_t)sizeof(double);
+  if (rows) {
+    if (row_capacity < M.nrows) { h->err = "mpc: row table too small: need " + std::to_string(M.nrows); return DGSQP_E_ARG; }
+    memcpy(rows, h->mpc.rows.data(), sizeof(dgsqp_mpc_row_t) * (size_t)M.nrows);
+  }
+  return DGSQP_OK;
+}
+
+int dgsqp_set_mpc_log(dgsqp_handle_t h, int on) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  h->mpc.log_on = on != 0;
+  mpc_log_free(h);
+  return DGSQP_OK;
+}
+
+int dgsqp_fetch_mpc_log(dgsqp_handle_t h, double* D, double* D_bar, double* lam, int64_t capacity) {
+  if (!h) return DGSQP_E_ARG;
+  DgMpcState& S = h->mpc;
+  if (!S.logD || S.log_B <= 0) { h->err = "mpc: no log recorded"; return DGSQP_E_ARG; }
+  if (capacity < S.log_B) { h->err = "mpc: log buffers too small: need " + std::to_string(S.log_B) + " scenarios"; return DGSQP_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nd = (size_t)S.log_B * S.log_iters * S.log_lenD, nl = (size_t)S.log_B * S.log_iters * S.log_rows;
+  if (D) HIPCHK(h, hipMemcpy(D, S.logD, sizeof(double) * nd, hipMemcpyDeviceToHost));
+  if (D_bar) HIPCHK(h, hipMemcpy(D_bar, S.logDb, sizeof(double) * nd, hipMemcpyDeviceToHost));
+  if (lam && nl) HIPCHK(h, hipMemcpy(lam, S.loglam, sizeof(double) * nl, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
+int dgsqp_mpc_batch(dgsqp_handle_t h, int64_t B, const double* q0, const double* u_ws, const double* du_ws, const double* q_ref,
+                    const double* p_obs, double* q_pred, double* u_pred, double* du_pred, int32_t* status, int32_t* qp_steps,
+                    dgsqp_timing_t* timing) {
+  if (!h) return DGSQP_E_ARG;
+  if (!h->mpc.set) { h->err = "mpc: no tracker set (dgsqp_set_mpc)"; return DGSQP_E_ARG; }
+  if (B < 0 || !q0 || !u_ws || !du_ws || !q_ref) { h->err = "mpc: bad argument"; return DGSQP_E_ARG; }
+  dg_mpc::DgMpcDev M = h->mpc.dev;
+  if (M.c.obs_r > 0.0 && !p_obs) { h->err = "mpc: obs_r > 0 needs p_obs"; return DGSQP_E_ARG; }
+  if (timing) memset(timing, 0, sizeof *timing);
+  if (B == 0) return DGSQP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  const int N = M.c.N, nq = M.nqa, nu = DGSQP_NUA;
+  const auto t0 = std::chrono::steady_clock::now();
+  int grid = (int)std::min<int64_t>(B, (int64_t)h->num_cu * DG_WG_PER_CU);
+  if (grid < 1) grid = 1;
+  TmpBuf tb;
+  const size_t nQ0 = (size_t)B * nq, nU = (size_t)B * (N + 1) * nu, nDU = (size_t)B * N * nu, nQ = (size_t)B * (N + 1) * nq, nP = (size_t)B * N * 2;
+  double* dq0 = tb.alloc<double>(nQ0); double* duw = tb.alloc<double>(nU); double* ddu = tb.alloc<double>(nDU); double* dqr = tb.alloc<double>(nQ);
+  double* dpo = M.c.obs_r > 0.0 ? tb.alloc<double>(nP) : nullptr;
+  double* oq = tb.alloc<double>(nQ); double* ou = tb.alloc<double>(nDU); double* od = tb.alloc<double>(nDU);
+  int32_t* ost = tb.alloc<int32_t>(B); int32_t* osp = tb.alloc<int32_t>(B);
+  double* ws = tb.alloc<double>((size_t)grid * M.ws_doubles);
+  dgsqp_mpc_row_t* drows = tb.alloc<dgsqp_mpc_row_t>(M.nrows);
+  dg_mpc::DgMpcDev* dM = tb.alloc<dg_mpc::DgMpcDev>(1);
+  if (!dq0 || !duw || !ddu || !dqr || (M.c.obs_r > 0.0 && !dpo) || !oq || !ou || !od || !ost || !osp || !ws || !drows || !dM) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  DgMpcState& S = h->mpc;
+  if (S.log_on) {
+    mpc_log_free(h);
+    const size_t nd = (size_t)B * M.c.qp_iters * M.lenD, nl = (size_t)B * M.c.qp_iters * (M.nrows ? M.nrows : 1);
+    HIPCHK(h, hipMalloc(&S.logD, sizeof(double) * nd));
+    HIPCHK(h, hipMalloc(&S.logDb, sizeof(double) * nd));
+    HIPCHK(h, hipMalloc(&S.loglam, sizeof(double) * nl));
+    S.log_B = B; S.log_iters = M.c.qp_iters; S.log_lenD = M.lenD; S.log_rows = M.nrows;
+  }
+  HIPCHK(h, hipMemcpy(dq0, q0, sizeof(double) * nQ0, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(duw, u_ws, sizeof(double) * nU, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(ddu, du_ws, sizeof(double) * nDU, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(dqr, q_ref, sizeof(double) * nQ, hipMemcpyHostToDevice));
+  if (dpo) HIPCHK(h, hipMemcpy(dpo, p_obs, sizeof(double) * nP, hipMemcpyHostToDevice));
+  if (M.nrows) HIPCHK(h, hipMemcpy(drows, S.rows.data(), sizeof(dgsqp_mpc_row_t) * (size_t)M.nrows, hipMemcpyHostToDevice));
+  M.rows = drows; M.q0 = dq0; M.u_ws = duw; M.du_ws = ddu; M.q_ref = dqr; M.p_obs = dpo;
+  M.q_pred = oq; M.u_pred = ou; M.du_pred = od; M.status = ost; M.qp_steps = osp; M.ws = ws;
+  M.logD = S.log_on ? S.logD : nullptr; M.logDb = S.log_on ? S.logDb : nullptr; M.loglam = S.log_on ? S.loglam : nullptr;
+  HIPCHK(h, hipMemcpy(dM, &M, sizeof M, hipMemcpyHostToDevice));
+  const auto t1 = std::chrono::steady_clock::now();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPCHK(h, hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); h->err = "hipEventCreate failed"; return DGSQP_E_DEVICE; }
+  const size_t lds = (size_t)M.o_end * sizeof(double);
+  if (hipFuncSetAttribute((const void*)dg_mpc::dg_mpc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    h->err = "hipFuncSetAttribute(dynamic LDS) failed for the tracker";
+    return DGSQP_E_DEVICE;
+  }
+  int rc = run_sync(h, [&]() -> int {
+    HIPCHK(h, hipEventRecord(e0, h->stream));
+    hipLaunchKernelGGL(dg_mpc::dg_mpc_kernel, dim3(grid), dim3(DG_BLOCK), lds, h->stream, B, (const dg_mpc::DgMpcDev*)dM);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(e1, h->stream));
+    return DGSQP_OK;
+  });
+  float ms = 0.0f;
+  if (!rc && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 0.0f;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  const auto t2 = std::chrono::steady_clock::now();
+  if (q_pred) HIPCHK(h, hipMemcpy(q_pred, oq, sizeof(double) * nQ, hipMemcpyDeviceToHost));
+  if (u_pred) HIPCHK(h, hipMemcpy(u_pred, ou, sizeof(double) * nDU, hipMemcpyDeviceToHost));
+  if (du_pred) HIPCHK(h, hipMemcpy(du_pred, od, sizeof(double) * nDU, hipMemcpyDeviceToHost));
+  if (status) HIPCHK(h, hipMemcpy(status, ost, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  if (qp_steps) HIPCHK(h, hipMemcpy(qp_steps, osp, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  const auto t3 = std::chrono::steady_clock::now();
+  if (timing) {
+    auto msd = [](auto a, auto b_) { return std::chrono::duration<double, std::milli>(b_ - a).count(); };
+    timing->h2d_ms = msd(t0, t1); timing->kernel_ms = ms; timing->d2h_ms = msd(t2, t3); timing->total_ms = msd(t0, t3);
+    timing->grid = grid; timing->block = DG_BLOCK;
+  }
+  return DGSQP_OK;
 }
 
 int dgsqp_synchronize(dgsqp_handle_t h) {

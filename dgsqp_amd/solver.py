@@ -843,6 +843,12 @@ class DGSQP(AbstractSolver):
             raise RuntimeError(f'dgsqp_qp_batch failed ({rc}): {self._lib.dgsqp_last_error(self._h).decode()}')
         return out           # info: OSQP's diagnostics with qp_method='osqp' (include/dgsqp.h: dgsqp_qp_batch_info), zeros otherwise
 
+    def mpc_batch(self, agent: int, cost, bounds: dict, q0, u_ws, du_ws, q_ref, p_obs=None, **kw) -> dict:
+        """The LTV-MPC reference tracker (ltv_mpc.py, reference CA_LTV_MPC) for one agent of this game, on this handle: see
+        ``ltv_mpc.mpc_batch`` for the arguments.  Solves and closed-loop launches before and after it are not affected."""
+        from .ltv_mpc import mpc_batch
+        return mpc_batch(self, agent, cost, bounds, q0, u_ws, du_ws, q_ref, p_obs, **kw)
+
     def pid_warm_start_batch(self, q0, u_max=(2.1, 0.436), du_max=(10.0, 4.5), substeps=10, want_trajectories=False):
         """PID lane-follower warm start of a batch on the device (chicane.py:411-447 with PID.py; collision check
         chicane.py:38-43).  q0 [B, n_q] -> dict(u_ws [B, N, n_u] time-major as ``set_warm_start`` / ``solve_batch`` take it,

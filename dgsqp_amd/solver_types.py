@@ -106,3 +106,33 @@ class DGSQPV2Params(ControllerConfig):
     save_plot: bool = False
     show_ts: bool = False
     local_pos: bool = False
+
+
+@dataclass
+class CALTVMPCParams(ControllerConfig):
+    """Reference DGSQP/solvers/solver_types.py:203-233 (field names and defaults identical).  What the device tracker refuses --
+    ``delay``, ``wrapped_state_*``, ``soft_constraint_*``, another ``qp_interface``, ``code_gen`` / ``jit``, ``reg != 0`` -- is refused by
+    ``ltv_mpc.CA_LTV_MPC``, not here."""
+    N: int = 10
+    verbose: bool = False
+    code_gen: bool = False
+    jit: bool = False
+    opt_flag: str = 'O0'
+    solver_name: str = 'LTV_MPC'
+    solver_dir: str = None
+    debug_plot: bool = False
+    soft_state_bound_idxs: list = None
+    soft_state_bound_quad: list = None
+    soft_state_bound_lin: list = None
+    soft_constraint_idxs: list = None
+    soft_constraint_quad: list = None
+    soft_constraint_lin: list = None
+    wrapped_state_idxs: list = None
+    wrapped_state_periods: list = None
+    reg: float = 0
+    state_scaling: list = None
+    input_scaling: list = None
+    damping: float = 0.75
+    qp_iters: int = 2
+    qp_interface: str = 'casadi'
+    delay: list = None

@@ -730,6 +730,62 @@ int dgsqp_fetch_iterate_log(dgsqp_handle_t h, double* out, int64_t capacity_doub
 /* Wait for everything enqueued on the handle's stream (what a caller without a HIP runtime of its own uses as a fence). */
 int dgsqp_synchronize(dgsqp_handle_t h);
 
+/*
+ * LTV-MPC reference tracker (DGSQP/solvers/CA_LTV_MPC.py, qp_interface 'casadi'), batched: row (f9) of the hot-path scope.  One agent
+ * of the handle's game (its model, vehicle, integrator, dt and track) follows per-scenario reference trajectories: rollout of the warm
+ * start, then qp_iters times { QP of the cost's Gauss-Newton model and the dynamics linearised at (q_k, u_{k-1}) about the current
+ * decision vector D; D <- damping D + (1 - damping) D_bar; slacks (zero_du: and du) <- 0 }.  The QP is solved exactly (dense dual
+ * active set on the condensed problem), where the reference calls OSQP.
+ *   D = [(q_0, u_-1), ..., (q_N, u_N-1), du_0 .. du_N-1, s_ub, s_lb]      len_D = (N + 1)(n_q + n_u) + N n_u + 2 n_soft
+ *   cost   sum_{k=0..N} 0.5 (q_k - q_ref_k)' diag(w_q) (q_k - q_ref_k) + c_N' q_N + sum_{k=0..N} 0.5 u_{k-1}' diag(w_u) u_{k-1}
+ *          + sum_{k<N} 0.5 du_k' diag(w_du) du_k + soft_quad s^2 + soft_lin s        (+ the reference's 1e-10 I on every (q, u) block)
+ *   boxes  u_lb <= u_{k-1} <= u_ub (k = 0..N), q_lb <= q_k <= q_ub (k = 1..N), du_lb <= du_k <= du_ub; a bound of magnitude >= 1e9
+ *          generates no row.  The bounds of a soft state are lifted: q_k[j] <= q_ub[j] + s_ub, q_k[j] >= q_lb[j] - s_lb, s >= 0 (one
+ *          slack pair over the horizon; n_soft <= 1: with more, the reference's rows of different states overwrite one another).
+ *   obs_r > 0: one row per stage k = 1..N, (2 obs_r)^2 - |(x, y)_k - p_obs_k|^2 <= 0, linearised about D.
+ * zero_du != 0 is the loop of set_warm_start (CA_LTV_MPC.py:174-197): du of D is zeroed after every iteration, and a failed QP leaves
+ * the current D as the result.  Otherwise a failed QP (status DGSQP_QP_FAIL) returns the warm start: q_ws, u_ws[1:], du_ws.
+ * A u_prev (= u_ws[0]) more than 1e-12 max(1, |bound|) beyond an input bound makes every QP infeasible, as in the reference, where u_-1 is
+ * both fixed and bounded; closer than that (a saturated input this tracker returned, fed back) it is moved onto the bound.
+ */
+typedef struct {
+  int32_t agent, N, qp_iters, zero_du;
+  double damping;
+  double w_q[DGSQP_MAX_NQA], c_N[DGSQP_MAX_NQA], w_u[DGSQP_NUA], w_du[DGSQP_NUA];   /* w_du > 0: the QP is strictly convex */
+  double q_ub[DGSQP_MAX_NQA], q_lb[DGSQP_MAX_NQA], u_ub[DGSQP_NUA], u_lb[DGSQP_NUA], du_ub[DGSQP_NUA], du_lb[DGSQP_NUA];
+  int32_t n_soft, reserved_;
+  int32_t soft_idx[DGSQP_MAX_NQA];                   /* entries past n_soft (<= 1 today) are reserved: room for more soft states */
+  double soft_quad[DGSQP_MAX_NQA], soft_lin[DGSQP_MAX_NQA];
+  double obs_r;                                                                      /* 0: no obstacle rows */
+} dgsqp_mpc_t;
+/* rows of the condensed QP, x = (du_0 .. du_N-1, s_ub, s_lb): sign * value <= sign * bound */
+enum { DGSQP_MPC_ROW_RATE = 0,   /* du_stage[index] */
+       DGSQP_MPC_ROW_SLACK = 1,  /* slack index (0 .. 2 n_soft - 1), sign -1: s >= 0 */
+       DGSQP_MPC_ROW_INPUT = 2,  /* u of block `stage` (1..N), i.e. u_{stage-1}[index] */
+       DGSQP_MPC_ROW_STATE = 3,  /* q_stage[index] */
+       DGSQP_MPC_ROW_SOFT = 4,   /* soft state `index` (slot) at `stage`: sign +1 the upper row, -1 the lower */
+       DGSQP_MPC_ROW_OBS = 5 };  /* obstacle row of `stage` */
+typedef struct { int32_t kind, stage, index, sign; } dgsqp_mpc_row_t;
+typedef struct { int32_t n, n_rows, len_D, n_q, lds_bytes, reserved_; int64_t workspace_bytes; } dgsqp_mpc_dims_t;
+#define DGSQP_MPC_NMAX 128   /* condensed variables: N n_u + 2 n_soft */
+/* Validated and copied; NULL clears it.  DGSQP_E_ARG, message starting "mpc: ": agent out of range, N < 1, qp_iters < 1, damping outside
+   [0, 1], w_du <= 0, a negative weight, n_soft outside 0..1 or its index out of range, obs_r < 0, a non-finite entry.
+   DGSQP_E_TOO_LARGE: N n_u + 2 n_soft > DGSQP_MPC_NMAX, or the workgroup's LDS arena cannot hold it (the 256-thread build has half). */
+int dgsqp_set_mpc(dgsqp_handle_t h, const dgsqp_mpc_t* mpc);
+/* rows: the row table in the order of the multipliers of dgsqp_fetch_mpc_log (may be NULL); row_capacity = what it can hold. */
+int dgsqp_mpc_dims(dgsqp_handle_t h, dgsqp_mpc_dims_t* out, dgsqp_mpc_row_t* rows, int64_t row_capacity);
+/* q0 [B][n_q] (n_q of the agent), u_ws [B][N+1][n_u] (row 0 = u_prev), du_ws [B][N][n_u], q_ref [B][N+1][n_q], p_obs [B][N][2] (stage
+   1..N; required when obs_r > 0, else ignored); out: q_pred [B][N+1][n_q], u_pred [B][N][n_u], du_pred [B][N][n_u], status [B] (0 or
+   DGSQP_QP_FAIL), qp_steps [B] (active-set steps of all QPs), each may be NULL. */
+int dgsqp_mpc_batch(dgsqp_handle_t h, int64_t B, const double* q0, const double* u_ws, const double* du_ws, const double* q_ref,
+                    const double* p_obs, double* q_pred, double* u_pred, double* du_pred, int32_t* status, int32_t* qp_steps,
+                    dgsqp_timing_t* timing);
+/* Test hook: per-iteration log of the next dgsqp_mpc_batch calls: D before the iteration, D_bar, the multipliers of the rows.  An
+   iteration that did not run (after a failed QP) and a failed QP's D_bar / multipliers are NaN. */
+int dgsqp_set_mpc_log(dgsqp_handle_t h, int on);
+/* D, D_bar [B][qp_iters][len_D], lam [B][qp_iters][n_rows] of the last launch; capacity = scenarios each array can hold. */
+int dgsqp_fetch_mpc_log(dgsqp_handle_t h, double* D, double* D_bar, double* lam, int64_t capacity);
+
 
 /*
  * Multi-GPU (one process per GPU, scenarios sharded, no data-path collective): the library owns the RCCL communicator.
