@@ -1,4 +1,5 @@
-"""Reference path DGSQP/tracks/track_lib.py (``StraightTrack`` :14, ``CurveTrack`` :27, ``ChicaneTrack`` :54, ``get_track`` :96)
--> dgsqp_amd.tracks.  The scripts use ``from DGSQP.tracks.track_lib import *``."""
-from dgsqp_amd.tracks import RadiusArclengthTrack, StraightTrack, CurveTrack, ChicaneTrack, CubicSplineTrack, get_track  # noqa: F401
-__all__ = ['RadiusArclengthTrack', 'StraightTrack', 'CurveTrack', 'ChicaneTrack', 'CubicSplineTrack', 'get_track']
+"""Reference path DGSQP/tracks/track_lib.py (``StraightTrack`` :14, ``CurveTrack`` :27, ``ChicaneTrack`` :54, ``get_track`` :96,
+``load_mpclab_raceline`` :124) -> dgsqp_amd.tracks.  The scripts use ``from DGSQP.tracks.track_lib import *``."""
+from dgsqp_amd.tracks import (RadiusArclengthTrack, StraightTrack, CurveTrack, ChicaneTrack, CubicSplineTrack, get_track,  # noqa: F401
+                              load_mpclab_raceline)
+__all__ = ['RadiusArclengthTrack', 'StraightTrack', 'CurveTrack', 'ChicaneTrack', 'CubicSplineTrack', 'get_track', 'load_mpclab_raceline']

@@ -145,6 +145,21 @@ class MpcDimsT(C.Structure):
                 ('reserved_', C.c_int32), ('workspace_bytes', C.c_int64)]
 
 
+RL_COLS = 9          # DGSQP_RL_COLS: columns of the raceline table (x, y, psi, v_long, v_tran, psidot, e_psi, s, e_y)
+
+
+class RacelineWsT(C.Structure):
+    """dgsqp_raceline_ws_t: the warm-start program of warm_start_dynamic.py (montecarlo.raceline_ws lowers to it)."""
+    _fields_ = [('mpc', MpcT), ('u_init', C.c_double), ('du_init', C.c_double), ('init_iters', C.c_int32), ('reserved_', C.c_int32),
+                ('init_damping', C.c_double)]
+
+
+class RacelineSamplerT(C.Structure):
+    """dgsqp_raceline_sampler_t: the placement of monte_carlo_sampler_dynamic.py (sampler.raceline_sampler_spec fills it)."""
+    _fields_ = [('n_key', C.c_int32), ('reserved_', C.c_int32), ('seed', C.c_uint64), ('half_width', C.c_double), ('obs_d', C.c_double),
+                ('collision_d', C.c_double), ('key_pts', (C.c_double * 6) * (MAX_SEGS + 1))]
+
+
 MPC_ROW_RATE, MPC_ROW_SLACK, MPC_ROW_INPUT, MPC_ROW_STATE, MPC_ROW_SOFT, MPC_ROW_OBS = range(6)     # DGSQP_MPC_ROW_*
 MPC_NMAX = 128                                                                                      # DGSQP_MPC_NMAX
 E_ARG, E_DEVICE, E_NOMEM, E_TOO_LARGE = -1, -2, -3, -4                                              # DGSQP_E_*
@@ -220,6 +235,11 @@ SIGNATURES = {
     'dgsqp_mpc_batch': (C.c_int, [_H, C.c_int64, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI, _PI, _TM]),
     'dgsqp_set_mpc_log': (C.c_int, [_H, C.c_int]),
     'dgsqp_fetch_mpc_log': (C.c_int, [_H, _PD, _PD, _PD, C.c_int64]),
+    'dgsqp_set_raceline': (C.c_int, [_H, C.c_int64, _PD, _PD]),
+    'dgsqp_raceline_warm_start_batch': (C.c_int, [_H, C.c_int64, _PD, C.POINTER(RacelineWsT), _PD, _PI]),
+    'dgsqp_fetch_raceline_ref': (C.c_int, [_H, _PD, C.c_int64]),
+    'dgsqp_sample_raceline_batch': (C.c_int, [_H, C.c_int64, C.POINTER(RacelineSamplerT), C.POINTER(RacelineWsT), _PD, _PD,
+                                              C.POINTER(C.c_int64), C.c_int]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)
 

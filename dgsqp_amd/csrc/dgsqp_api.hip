@@ -129,6 +129,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 #include "dgsqp_pid.h"
 #include "dgsqp_sampler.h"
 #include "dgsqp_mpc.h"
+#include "dgsqp_raceline.h"
 
 // Test hook: one _evaluate(hessian=True) (+ dual init) per scenario, results expanded to dense arrays.
 __global__ void __launch_bounds__(DG_BLOCK, 2)
@@ -353,6 +354,16 @@ struct DgMpcState {
   int log_iters = 0, log_lenD = 0, log_rows = 0;
 };
 
+// The raceline of dgsqp_set_raceline (device copy of the table) and the reference trajectories of the last warm-start program.
+struct DgRacelineState {
+  DgRaceline dev{0, nullptr, nullptr};
+  double* T = nullptr;                 // device [n]
+  double* cols = nullptr;              // device [n][DGSQP_RL_COLS]
+  double* qref = nullptr;              // device [M][B][N+1][n_qa] of the last program (dgsqp_fetch_raceline_ref)
+  size_t qref_cap = 0;                 // doubles allocated
+  int64_t ref_B = 0;
+};
+
 struct dgsqp_comm_state;
 struct dgsqp_solver {
   int device = 0;
@@ -381,6 +392,7 @@ struct dgsqp_solver {
   DgSide side;                             // ... and their device buffers
   DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
   DgMpcState mpc;                          // the reference tracker (dgsqp_set_mpc)
+  DgRacelineState rl;                      // the raceline (dgsqp_set_raceline)
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -1065,6 +1077,9 @@ void dgsqp_destroy(dgsqp_handle_t h) {
   if (h->d_coop) (void)hipFree(h->d_coop);
   if (h->d_coop_payload) (void)hipFree(h->d_coop_payload);
   mpc_log_free(h);
+  if (h->rl.T) (void)hipFree(h->rl.T);
+  if (h->rl.cols) (void)hipFree(h->rl.cols);
+  if (h->rl.qref) (void)hipFree(h->rl.qref);
   {
     std::lock_guard<std::mutex> lk(g_reg_mutex);
     DgParkPool& pool = g_park[h->device & 63];
@@ -1959,6 +1974,34 @@ int dgsqp_fetch_mpc_log(dgsqp_handle_t h, double* D, double* D_bar, double* lam,
   return DGSQP_OK;
 }
 
+// The tracker's launch path from device-resident buffers: dgsqp_mpc_batch between its copies in and its copies out, and the warm-start
+// program of dgsqp_raceline_warm_start_batch.  M carries every device pointer but `rows`.
+//   mpc_upload         the row table and the record to the device (drows, dM: the caller's), host-synchronous
+//   mpc_lds_attribute  the kernel's dynamic LDS size, once before the launches of a record's layout
+//   mpc_enqueue        dg_mpc_kernel on h->stream: inside run_sync's critical section (the kernel reads dg_prob)
+static int mpc_grid(const dgsqp_solver* h, int64_t B) {
+  const int grid = (int)std::min<int64_t>(B, (int64_t)h->num_cu * DG_WG_PER_CU);
+  return grid < 1 ? 1 : grid;
+}
+static int mpc_upload(dgsqp_solver* h, dg_mpc::DgMpcDev& M, const std::vector<dgsqp_mpc_row_t>& rows, dgsqp_mpc_row_t* drows, dg_mpc::DgMpcDev* dM) {
+  if (M.nrows) HIPCHK(h, hipMemcpy(drows, rows.data(), sizeof(dgsqp_mpc_row_t) * (size_t)M.nrows, hipMemcpyHostToDevice));
+  M.rows = drows;
+  HIPCHK(h, hipMemcpy(dM, &M, sizeof M, hipMemcpyHostToDevice));
+  return DGSQP_OK;
+}
+static int mpc_lds_attribute(dgsqp_solver* h, const dg_mpc::DgMpcDev& M) {
+  if (hipFuncSetAttribute((const void*)dg_mpc::dg_mpc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)M.o_end * sizeof(double))) != hipSuccess) {
+    h->err = "hipFuncSetAttribute(dynamic LDS) failed for the tracker";
+    return DGSQP_E_DEVICE;
+  }
+  return DGSQP_OK;
+}
+static int mpc_enqueue(dgsqp_solver* h, const dg_mpc::DgMpcDev& M, const dg_mpc::DgMpcDev* dM, int64_t B, int grid) {
+  hipLaunchKernelGGL(dg_mpc::dg_mpc_kernel, dim3(grid), dim3(DG_BLOCK), (size_t)M.o_end * sizeof(double), h->stream, B, dM);
+  HIPCHK(h, hipGetLastError());
+  return DGSQP_OK;
+}
+
 int dgsqp_mpc_batch(dgsqp_handle_t h, int64_t B, const double* q0, const double* u_ws, const double* du_ws, const double* q_ref,
                     const double* p_obs, double* q_pred, double* u_pred, double* du_pred, int32_t* status, int32_t* qp_steps,
                     dgsqp_timing_t* timing) {
@@ -1973,8 +2016,7 @@ int dgsqp_mpc_batch(dgsqp_handle_t h, int64_t B, const double* q0, const double*
   { const int rc = wait_idle(h); if (rc) return rc; }
   const int N = M.c.N, nq = M.nqa, nu = DGSQP_NUA;
   const auto t0 = std::chrono::steady_clock::now();
-  int grid = (int)std::min<int64_t>(B, (int64_t)h->num_cu * DG_WG_PER_CU);
-  if (grid < 1) grid = 1;
+  const int grid = mpc_grid(h, B);
   TmpBuf tb;
   const size_t nQ0 = (size_t)B * nq, nU = (size_t)B * (N + 1) * nu, nDU = (size_t)B * N * nu, nQ = (size_t)B * (N + 1) * nq, nP = (size_t)B * N * 2;
   double* dq0 = tb.alloc<double>(nQ0); double* duw = tb.alloc<double>(nU); double* ddu = tb.alloc<double>(nDU); double* dqr = tb.alloc<double>(nQ);
@@ -1999,25 +2041,19 @@ int dgsqp_mpc_batch(dgsqp_handle_t h, int64_t B, const double* q0, const double*
   HIPCHK(h, hipMemcpy(ddu, du_ws, sizeof(double) * nDU, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(dqr, q_ref, sizeof(double) * nQ, hipMemcpyHostToDevice));
   if (dpo) HIPCHK(h, hipMemcpy(dpo, p_obs, sizeof(double) * nP, hipMemcpyHostToDevice));
-  if (M.nrows) HIPCHK(h, hipMemcpy(drows, S.rows.data(), sizeof(dgsqp_mpc_row_t) * (size_t)M.nrows, hipMemcpyHostToDevice));
-  M.rows = drows; M.q0 = dq0; M.u_ws = duw; M.du_ws = ddu; M.q_ref = dqr; M.p_obs = dpo;
+  M.q0 = dq0; M.u_ws = duw; M.du_ws = ddu; M.q_ref = dqr; M.p_obs = dpo;
   M.q_pred = oq; M.u_pred = ou; M.du_pred = od; M.status = ost; M.qp_steps = osp; M.ws = ws;
   M.logD = S.log_on ? S.logD : nullptr; M.logDb = S.log_on ? S.logDb : nullptr; M.loglam = S.log_on ? S.loglam : nullptr;
-  HIPCHK(h, hipMemcpy(dM, &M, sizeof M, hipMemcpyHostToDevice));
+  { const int rcu = mpc_upload(h, M, S.rows, drows, dM); if (rcu) return rcu; }
   const auto t1 = std::chrono::steady_clock::now();
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPCHK(h, hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); h->err = "hipEventCreate failed"; return DGSQP_E_DEVICE; }
-  const size_t lds = (size_t)M.o_end * sizeof(double);
-  if (hipFuncSetAttribute((const void*)dg_mpc::dg_mpc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    h->err = "hipFuncSetAttribute(dynamic LDS) failed for the tracker";
-    return DGSQP_E_DEVICE;
-  }
-  int rc = run_sync(h, [&]() -> int {
+  int rc = mpc_lds_attribute(h, M);
+  if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+  rc = run_sync(h, [&]() -> int {
     HIPCHK(h, hipEventRecord(e0, h->stream));
-    hipLaunchKernelGGL(dg_mpc::dg_mpc_kernel, dim3(grid), dim3(DG_BLOCK), lds, h->stream, B, (const dg_mpc::DgMpcDev*)dM);
-    HIPCHK(h, hipGetLastError());
+    { const int rce = mpc_enqueue(h, M, dM, B, grid); if (rce) return rce; }
     HIPCHK(h, hipEventRecord(e1, h->stream));
     return DGSQP_OK;
   });
@@ -2180,6 +2216,242 @@ int dgsqp_sample_batch(dgsqp_handle_t h, int64_t B, const dgsqp_sampler_t* spec,
   if (x0_out) HIPCHK(h, hipMemcpy(x0_out, d_x0, sizeof(double) * B * D.nq, hipMemcpyDeviceToHost));
   if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, d_uws, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
   h->B = stage ? B : 0;          // (the staging buffers were used either way: without `stage` nothing is left staged)
+  return DGSQP_OK;
+}
+
+// ---- raceline warm starts (dgsqp_raceline.h) ----
+int dgsqp_set_raceline(dgsqp_handle_t h, int64_t n, const double* T, const double* cols) {
+  if (!h) return DGSQP_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  DgRacelineState& S = h->rl;
+  if (T && cols) {
+    if (n < 2 || n > (1 << 30)) return refuse(h, "raceline: ", "n = " + std::to_string(n) + " knots (at least 2)");
+    int64_t bad = first_non_finite(T, n);
+    if (bad >= 0) return refuse(h, "raceline: ", "T[" + std::to_string(bad) + "] is not finite");
+    bad = first_non_finite(cols, n * DGSQP_RL_COLS);
+    if (bad >= 0) return refuse(h, "raceline: ", "entry [" + std::to_string(bad / DGSQP_RL_COLS) + "][" + std::to_string(bad % DGSQP_RL_COLS) + "] is not finite");
+    for (int64_t i = 1; i < n; i++) {
+      if (!(T[i] > T[i - 1])) return refuse(h, "raceline: ", "T is not strictly increasing at knot " + std::to_string(i));
+      if (!(cols[i * DGSQP_RL_COLS + 7] > cols[(i - 1) * DGSQP_RL_COLS + 7])) return refuse(h, "raceline: ", "the s column is not strictly increasing at knot " + std::to_string(i));
+    }
+  }
+  if (S.T) (void)hipFree(S.T);
+  if (S.cols) (void)hipFree(S.cols);
+  S.T = S.cols = nullptr;
+  S.dev = DgRaceline{0, nullptr, nullptr};
+  if (!T || !cols) return DGSQP_OK;
+  HIPCHK(h, hipMalloc(&S.T, sizeof(double) * (size_t)n));
+  HIPCHK(h, hipMalloc(&S.cols, sizeof(double) * (size_t)n * DGSQP_RL_COLS));
+  HIPCHK(h, hipMemcpy(S.T, T, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(S.cols, cols, sizeof(double) * (size_t)n * DGSQP_RL_COLS, hipMemcpyHostToDevice));
+  S.dev = DgRaceline{(int)n, S.T, S.cols};
+  return DGSQP_OK;
+}
+
+// The warm-start program for `cap` scenarios at a time: the two records of every agent planned and uploaded, the buffers between the
+// launches.  Everything is sized for cap scenarios; enqueue() may run for any B <= cap.
+struct DgRacelineProgram {
+  int64_t cap = 0;
+  int grid = 1;
+  dg_mpc::DgMpcDev rec[DGSQP_MAX_AGENTS][2];              // host images, device pointers filled
+  dg_mpc::DgMpcDev* drec = nullptr;                       // device [M][2]
+  double *q0a = nullptr, *u1 = nullptr, *du1 = nullptr, *u2 = nullptr, *du2 = nullptr, *up1 = nullptr, *dup1 = nullptr, *up2 = nullptr;
+  int32_t* st2 = nullptr;
+  double u_init = 0.0, du_init = 0.0;
+};
+static int raceline_check(dgsqp_solver* h, const dgsqp_raceline_ws_t* W) {
+  const DgProb& D = h->hp;
+  if (!W) return refuse(h, "raceline: ", "no warm-start description");
+  if (h->rl.dev.n < 2) return refuse(h, "raceline: ", "no raceline set (dgsqp_set_raceline)");
+  for (int a = 0; a < D.M; a++) {
+    if (D.mdl[a] != DG_KIN && D.mdl[a] != DG_DYN) return refuse(h, "raceline: ", "agent " + std::to_string(a) + " is no Frenet-frame bicycle (the reference states are laid out for the kinematic and the dynamic bicycle)");
+    if (D.mdl[a] != D.mdl[0]) return refuse(h, "raceline: ", "agents of different models");
+  }
+  if (W->init_iters < 1) return refuse(h, "raceline: ", "init_iters < 1");
+  if (!std::isfinite(W->u_init) || !std::isfinite(W->du_init)) return refuse(h, "raceline: ", "u_init / du_init is not finite");
+  return DGSQP_OK;
+}
+static int raceline_program(dgsqp_solver* h, const dgsqp_raceline_ws_t& W, int64_t cap, TmpBuf& tb, DgRacelineProgram& P) {
+  const DgProb& D = h->hp;
+  const int N = W.mpc.N, nu = DGSQP_NUA, nqa = D.nqa[0];
+  if (N != D.N) return refuse(h, "raceline: ", "the tracker's N = " + std::to_string(N) + " is not the game's N = " + std::to_string(D.N) + " (its u_pred becomes the game's warm start)");
+  P.cap = cap; P.grid = mpc_grid(h, cap); P.u_init = W.u_init; P.du_init = W.du_init;
+  DgRacelineState& S = h->rl;
+  const size_t need = (size_t)D.M * cap * (N + 1) * nqa;
+  if (S.qref_cap < need) {
+    if (S.qref) (void)hipFree(S.qref);
+    S.qref = nullptr; S.qref_cap = 0; S.ref_B = 0;
+    HIPCHK(h, hipMalloc(&S.qref, sizeof(double) * need));
+    S.qref_cap = need;
+  }
+  const size_t nU = (size_t)cap * (N + 1) * nu, nDU = (size_t)cap * N * nu;
+  P.q0a = tb.alloc<double>((size_t)D.M * cap * nqa);
+  P.u1 = tb.alloc<double>(nU); P.du1 = tb.alloc<double>(nDU); P.u2 = tb.alloc<double>(nU); P.du2 = tb.alloc<double>(nDU);
+  P.up1 = tb.alloc<double>(nDU); P.dup1 = tb.alloc<double>(nDU); P.up2 = tb.alloc<double>(nDU);
+  P.st2 = tb.alloc<int32_t>(cap);
+  P.drec = tb.alloc<dg_mpc::DgMpcDev>((size_t)D.M * 2);
+  if (!P.q0a || !P.u1 || !P.du1 || !P.u2 || !P.du2 || !P.up1 || !P.dup1 || !P.up2 || !P.st2 || !P.drec) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  double* ws = nullptr;
+  for (int a = 0; a < D.M; a++) {
+    std::vector<dgsqp_mpc_row_t> rows;
+    for (int ph = 0; ph < 2; ph++) {
+      dgsqp_mpc_t c = W.mpc;
+      c.agent = a;
+      c.zero_du = ph == 0 ? 1 : 0;
+      if (ph == 0) { c.qp_iters = W.init_iters; c.damping = W.init_damping; }
+      dg_mpc::DgMpcDev& M = P.rec[a][ph];
+      std::string msg;
+      const int rc = mpc_plan(D, c, M, rows, msg);
+      if (rc) { h->err = msg; return rc; }
+      if (c.obs_r > 0.0) return refuse(h, "raceline: ", "obstacle rows are not part of the warm-start program (obs_r must be 0)");
+      if (!ws) { ws = tb.alloc<double>((size_t)P.grid * M.ws_doubles); if (!ws) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; } }
+      dgsqp_mpc_row_t* drows = tb.alloc<dgsqp_mpc_row_t>(M.nrows);
+      if (!drows) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+      M.q0 = P.q0a + (size_t)a * cap * nqa;
+      M.q_ref = S.qref + (size_t)a * cap * (N + 1) * nqa;
+      M.p_obs = nullptr; M.q_pred = nullptr; M.qp_steps = nullptr; M.ws = ws;
+      M.logD = M.logDb = M.loglam = nullptr;
+      if (ph == 0) { M.u_ws = P.u1; M.du_ws = P.du1; M.u_pred = P.up1; M.du_pred = P.dup1; M.status = nullptr; }
+      else { M.u_ws = P.u2; M.du_ws = P.du2; M.u_pred = P.up2; M.du_pred = nullptr; M.status = P.st2; }
+      const int rcu = mpc_upload(h, M, rows, drows, P.drec + a * 2 + ph);
+      if (rcu) return rcu;
+    }
+  }
+  return mpc_lds_attribute(h, P.rec[0][1]);
+}
+// The program for B <= cap scenarios whose joint states are at d_x0 [B][n_q] (device): on h->stream, inside run_sync's critical section.
+// d_u [B][n] agent-major and d_ok [B] receive the result.  The buffers are laid out for cap scenarios, so B must equal cap wherever an
+// agent's block follows another's (q0a, q_ref): the callers run it with B == cap.
+static int raceline_enqueue(dgsqp_solver* h, const DgRacelineProgram& P, int64_t B, const double* d_x0, double* d_u, int32_t* d_ok) {
+  const DgProb& D = h->hp;
+  const int N = D.N;
+  auto blocks = [&](int64_t lanes) { return dim3((unsigned)std::min<int64_t>((lanes + 255) / 256, 4 * (int64_t)h->num_cu)); };
+  hipLaunchKernelGGL(dg_raceline_ref_kernel, blocks(B * D.M * (N + 1)), dim3(256), 0, h->stream, B, h->rl.dev, d_x0, P.u_init, P.du_init,
+                     P.q0a, h->rl.qref, P.u1, P.du1);
+  HIPCHK(h, hipGetLastError());
+  for (int a = 0; a < D.M; a++) {
+    int rc = mpc_enqueue(h, P.rec[a][0], P.drec + a * 2, B, P.grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dg_ws_chain_kernel, blocks(B * (N + 1) * DGSQP_NUA), dim3(256), 0, h->stream, B, N, (const double*)P.u1, (const double*)P.up1,
+                       (const double*)P.dup1, P.u2, P.du2);
+    HIPCHK(h, hipGetLastError());
+    rc = mpc_enqueue(h, P.rec[a][1], P.drec + a * 2 + 1, B, P.grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dg_ws_assemble_kernel, blocks(B * N * DGSQP_NUA), dim3(256), 0, h->stream, B, N, D.n, a, (const double*)P.up2,
+                       (const int32_t*)P.st2, d_u, d_ok);
+    HIPCHK(h, hipGetLastError());
+  }
+  h->rl.ref_B = B;
+  return DGSQP_OK;
+}
+
+int dgsqp_raceline_warm_start_batch(dgsqp_handle_t h, int64_t B, const double* x0, const dgsqp_raceline_ws_t* W, double* u_ws_out,
+                                    int32_t* ok_out) {
+  if (!h) return DGSQP_E_ARG;
+  if (B < 0) return refuse(h, "raceline: ", "B < 0");
+  { const int rc = raceline_check(h, W); if (rc) return rc; }
+  if (!x0 && h->B != B) return refuse(h, "raceline: ", "x0 = NULL needs a staged batch of B = " + std::to_string(B) + " scenarios (staged: " + std::to_string(h->B) + ")");
+  if (B == 0) return DGSQP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  const DgProb& D = h->hp;
+  TmpBuf tb;
+  DgRacelineProgram P;
+  { const int rc = raceline_program(h, *W, B, tb, P); if (rc) return rc; }
+  const double* d_x0 = nullptr;
+  double* d_u = nullptr;
+  if (x0) {
+    double* dx = tb.alloc<double>((size_t)B * D.nq);
+    d_u = tb.alloc<double>((size_t)B * D.n);
+    if (!dx || !d_u) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+    HIPCHK(h, hipMemcpy(dx, x0, sizeof(double) * (size_t)B * D.nq, hipMemcpyHostToDevice));
+    d_x0 = dx;
+  } else {
+    d_x0 = h->staged.dbl(DG_Q);
+    d_u = h->staged.dbl(DG_UWS);
+  }
+  int32_t* d_ok = tb.alloc<int32_t>(B);
+  if (!d_ok) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  const int rc = run_sync(h, [&]() -> int { return raceline_enqueue(h, P, B, d_x0, d_u, d_ok); });
+  if (rc) return rc;
+  if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, d_u, sizeof(double) * (size_t)B * D.n, hipMemcpyDeviceToHost));
+  if (ok_out) HIPCHK(h, hipMemcpy(ok_out, d_ok, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
+int dgsqp_fetch_raceline_ref(dgsqp_handle_t h, double* out, int64_t capacity_doubles) {
+  if (!h) return DGSQP_E_ARG;
+  const DgProb& D = h->hp;
+  DgRacelineState& S = h->rl;
+  if (!S.qref || S.ref_B <= 0) return refuse(h, "raceline: ", "no reference trajectories recorded");
+  const int nqa = D.nqa[0];
+  const int64_t per = (int64_t)(D.N + 1) * nqa, B = S.ref_B, total = B * D.M * per;
+  if (!out || capacity_doubles < total) return refuse(h, "raceline: ", "reference buffer too small: need " + std::to_string(total) + " doubles");
+  HIPCHK(h, hipSetDevice(h->device));
+  // device [M][B][..] (an agent's block is what the tracker reads) -> the caller's [B][M][..]
+  std::vector<double> tmp((size_t)total);
+  HIPCHK(h, hipMemcpy(tmp.data(), S.qref, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
+  for (int a = 0; a < D.M; a++)
+    for (int64_t b = 0; b < B; b++)
+      memcpy(out + (b * D.M + a) * per, tmp.data() + ((int64_t)a * B + b) * per, sizeof(double) * (size_t)per);
+  return DGSQP_OK;
+}
+
+int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_sampler_t* spec, const dgsqp_raceline_ws_t* W,
+                                double* x0_out, double* u_ws_out, int64_t* candidates, int stage) {
+  if (!h) return DGSQP_E_ARG;
+  if (B < 0 || !spec) return refuse(h, "raceline: ", "bad argument (B < 0 or no sampler description)");
+  if (spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1 || !(spec->collision_d >= 0.0) || !std::isfinite(spec->collision_d) ||
+      !std::isfinite(spec->obs_d) || !std::isfinite(spec->half_width) || first_non_finite(&spec->key_pts[0][0], (int64_t)spec->n_key * 6) >= 0 ||
+      !(spec->key_pts[spec->n_key - 1][3] > 0.0))          // (the placement wraps s into [0, L): L must be a positive length)
+    return refuse(h, "raceline: ", "bad sampler description");
+  { const int rc = raceline_check(h, W); if (rc) return rc; }
+  const DgProb& D = h->hp;
+  if (D.M != 2) return refuse(h, "raceline: ", "the study's sampler places two cars");
+  if (candidates) *candidates = 0;
+  if (B == 0) return DGSQP_OK;
+  { const int rc = stage_begin(h, B); if (rc) return rc; }
+  double *const d_x0 = h->staged.dbl(DG_Q), *const d_uws = h->staged.dbl(DG_UWS);
+  const int64_t nround = std::max<int64_t>(256, std::min<int64_t>(2 * B, 1 << 16));        // candidates per round, as dgsqp_sample_batch
+  dgsqp_sampler_t track;
+  memset(&track, 0, sizeof track);
+  track.n_key = spec->n_key;
+  memcpy(track.key_pts, spec->key_pts, sizeof track.key_pts);
+  TmpBuf tb;
+  DgRacelineProgram P;
+  { const int rc = raceline_program(h, *W, nround, tb, P); if (rc) { h->B = 0; return rc; } }
+  double* dq0 = tb.alloc<double>(nround * D.nq); double* du = tb.alloc<double>(nround * D.n);
+  int32_t* dok = tb.alloc<int32_t>(nround); int32_t* dcol = tb.alloc<int32_t>(nround); int32_t* dpos = tb.alloc<int32_t>(nround); int32_t* dcnt = tb.alloc<int32_t>(1);
+  if (!dq0 || !du || !dok || !dcol || !dpos || !dcnt) { h->err = "hipMalloc failed"; h->B = 0; return DGSQP_E_NOMEM; }
+  const int rcs = run_sync(h, [&]() -> int {
+    int64_t have = 0;
+    unsigned long long c0 = 0;
+    for (int round = 0; have < B; round++) {
+      if (round > 10000) { h->err = "raceline: the sampler did not produce enough scenarios"; return DGSQP_E_ARG; }
+      hipLaunchKernelGGL(dg_raceline_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, track, h->rl.dev, dq0, dcol);
+      HIPCHK(h, hipGetLastError());
+      { const int rc = raceline_enqueue(h, P, nround, dq0, du, dok); if (rc) return rc; }
+      hipLaunchKernelGGL(dg_sample_scan_kernel, dim3(1), dim3(1024), 0, h->stream, nround, dok, dcol, dpos, dcnt);
+      hipLaunchKernelGGL(dg_sample_gather_kernel, dim3(1024), dim3(128), 0, h->stream, nround, have, B, dpos, dq0, (const double*)du, d_x0, d_uws);
+      HIPCHK(h, hipGetLastError());
+      int32_t cnt = 0;
+      HIPCHK(h, hipMemcpyAsync(&cnt, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if (have + cnt >= B && candidates) {
+        std::vector<int32_t> pos((size_t)nround);
+        HIPCHK(h, hipMemcpy(pos.data(), dpos, sizeof(int32_t) * nround, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < nround; i++) if (pos[i] == (int32_t)(B - have - 1)) { *candidates = (int64_t)(c0 + i + 1); break; }
+      }
+      have += cnt;
+      c0 += (unsigned long long)nround;
+    }
+    return DGSQP_OK;
+  });
+  if (rcs) { h->B = 0; return rcs; }
+  if (x0_out) HIPCHK(h, hipMemcpy(x0_out, d_x0, sizeof(double) * B * D.nq, hipMemcpyDeviceToHost));
+  if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, d_uws, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
+  h->B = stage ? B : 0;
   return DGSQP_OK;
 }
 

@@ -13,8 +13,13 @@ three callers build (scripts/race/car{1,2}_tracking_controller_setup.py, compari
 
 Two stated deviations: the QP is solved exactly where the reference calls OSQP with polish
 (``rate_weight > 0`` is required, so the minimiser is unique); ``state_scaling`` is accepted and ignored -- a change of variables that does
-not move the exact minimiser (only the reference's ``1e-10 I`` term moves with it).  ``input_scaling`` is NOT one in the reference (its
-``du``, rate cost and rate box end up in scaled units) and is refused.  ``q_ref`` must be continuous in ``s`` along the horizon (no wrap at
+not move the exact minimiser (only the reference's ``1e-10 I`` term moves with it).  ``input_scaling`` is accepted as what it is in the
+reference: with ``Tu = 1 / input_scaling`` the reference leaves ``u_{k+1} = u_k + dt du`` unscaled (CA_LTV_MPC.py:396-405), so its QP variable
+is ``du' = Tu du`` and its rate cost and rate box are in those units.  That is an exact change of variables of the rate channel, lowered on
+the host: the record carries ``w_du Tu^2`` and ``du_lb / Tu``, ``du_ub / Tu``; the caller's ``du_ws`` is divided by ``Tu`` and the returned
+``du_pred`` multiplied by it, so ``du_ws`` / ``du_pred`` are in the reference's units; the input cost and the input box are not touched (again
+only the ``1e-10 I`` term moves).  ``host_scaling`` does that step; ``check_params`` checks what is left for the device and still refuses
+``input_scaling`` itself.  ``q_ref`` must be continuous in ``s`` along the horizon (no wrap at
 the start line): the caller's duty, as in the reference, whose ``wrapped_state_idxs`` unwrapping is refused here along with ``delay``,
 ``soft_constraint_*``, other QP interfaces, code generation, ``reg != 0`` and rate-constraint functions.  A ``u_prev`` beyond an input bound
 by more than 1e-12 (relative to max(1, |bound|)) makes every QP infeasible, as in the reference, where ``u_{-1}`` is fixed and bounded;
@@ -22,6 +27,7 @@ closer than that -- what the tracker's own saturated output can be -- it is move
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -53,7 +59,8 @@ class ObstacleAvoidance:
 
 
 def check_params(params: CALTVMPCParams) -> None:
-    """Everything the device does not implement is refused here, before anything reaches the library."""
+    """Everything the device does not implement is refused here, before anything reaches the library.  ``input_scaling`` is among it: the
+    callers pass the parameters through ``host_scaling`` first, which lowers it on the host."""
     if params.delay is not None:
         raise NotImplementedError('CA_LTV_MPC: delay (input delay buffers) is not supported')
     if params.wrapped_state_idxs is not None or params.wrapped_state_periods is not None:
@@ -67,17 +74,38 @@ def check_params(params: CALTVMPCParams) -> None:
     if params.reg != 0:
         raise NotImplementedError('CA_LTV_MPC: reg != 0 is not supported')
     if params.input_scaling is not None:
-        raise NotImplementedError('CA_LTV_MPC: input_scaling is not supported: the reference leaves u_{k+1} = u_k + dt du unscaled '
-                                  '(CA_LTV_MPC.py:398-405), so with it du, the rate cost and the rate box are in scaled units -- another '
-                                  'controller, not a change of variables.  Scale du bounds and rate weights yourself, or drop the option')
+        raise NotImplementedError('CA_LTV_MPC: input_scaling is no option of the device record: it is a change of variables of the rate channel '
+                                  'that the host applies first (ltv_mpc.host_scaling, as CA_LTV_MPC and mpc_batch do); check the parameters '
+                                  'it returns')
     v = params.state_scaling
     if v is not None and not (np.all(np.isfinite(v)) and np.all(np.asarray(v, float) > 0)):
         raise ValueError('CA_LTV_MPC: state_scaling must be positive')
 
 
+def host_scaling(params: CALTVMPCParams):
+    """The host's share of the parameters: ``(device_params, Tu)``.  ``input_scaling`` is taken out -- ``Tu = 1 / input_scaling`` is the factor
+    of the rate channel's change of variables that ``lower`` and ``solve_batch`` apply -- and ``device_params`` is what ``check_params``
+    sees; ``Tu`` is None without ``input_scaling``."""
+    v = params.input_scaling
+    if v is None:
+        return params, None
+    if len(v) != _ffi.NUA:
+        raise ValueError('CA_LTV_MPC: input_scaling needs one entry per input')
+    if not (np.all(np.isfinite(v)) and np.all(np.asarray(v, float) > 0)):
+        raise ValueError('CA_LTV_MPC: input_scaling must be positive')
+    return dataclasses.replace(params, input_scaling=None), rate_scale(v)
+
+
+def rate_scale(input_scaling) -> Optional[np.ndarray]:
+    """``Tu = 1 / input_scaling`` (CA_LTV_MPC.py:121), or None: the factor between the reference's rate variable ``du' = Tu du`` and ``du``."""
+    return None if input_scaling is None else 1.0 / np.asarray(input_scaling, np.float64)
+
+
 def lower(agent: int, n_q: int, cost: TrackingCost, soft: Optional[SoftStateBounds], obstacle: Optional[ObstacleAvoidance],
-          q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, N: int, qp_iters: int, damping: float, zero_du: bool = False) -> _ffi.MpcT:
-    """The dgsqp_mpc_t record (validated again by dgsqp_set_mpc)."""
+          q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, N: int, qp_iters: int, damping: float, zero_du: bool = False,
+          input_scaling=None) -> _ffi.MpcT:
+    """The dgsqp_mpc_t record (validated again by dgsqp_set_mpc).  ``input_scaling``: the rate cost and the rate box are the reference's, in
+    its scaled rate ``du' = Tu du``; the record states them for ``du``: ``w_du Tu^2``, ``du_lb / Tu``, ``du_ub / Tu``."""
     if len(cost.state_weight) != n_q:
         raise ValueError(f'TrackingCost.state_weight needs {n_q} entries')
     if cost.terminal_linear is not None and len(cost.terminal_linear) != n_q:
@@ -93,9 +121,11 @@ def lower(agent: int, n_q: int, cost: TrackingCost, soft: Optional[SoftStateBoun
         m.c_N[i] = float(cost.terminal_linear[i]) if (cost.terminal_linear is not None and i < n_q) else 0.0
         m.q_ub[i] = float(q_ub[i]) if i < n_q else np.inf
         m.q_lb[i] = float(q_lb[i]) if i < n_q else -np.inf
+    Tu = rate_scale(input_scaling)
     for j in range(_ffi.NUA):
-        m.w_u[j], m.w_du[j] = float(cost.input_weight[j]), float(cost.rate_weight[j])
-        m.u_ub[j], m.u_lb[j], m.du_ub[j], m.du_lb[j] = float(u_ub[j]), float(u_lb[j]), float(du_ub[j]), float(du_lb[j])
+        t = 1.0 if Tu is None else float(Tu[j])
+        m.w_u[j], m.w_du[j] = float(cost.input_weight[j]), float(cost.rate_weight[j]) * t * t
+        m.u_ub[j], m.u_lb[j], m.du_ub[j], m.du_lb[j] = float(u_ub[j]), float(u_lb[j]), float(du_ub[j]) / t, float(du_lb[j]) / t
     if soft is not None:
         if not (len(soft.idxs) == len(soft.quad) == len(soft.lin)):
             raise ValueError('soft state bounds: idxs, quad and lin must have the same length')
@@ -171,9 +201,10 @@ def run_batch(lib, h, record: _ffi.MpcT, n_q: int, q0, u_ws, du_ws, q_ref, p_obs
 
 def mpc_batch(solver, agent: int, cost: TrackingCost, bounds: dict, q0, u_ws, du_ws, q_ref, p_obs=None, N: Optional[int] = None,
               qp_iters: int = 2, damping: float = 0.75, soft: Optional[SoftStateBounds] = None,
-              obstacle: Optional[ObstacleAvoidance] = None, zero_du: bool = False, log: bool = False) -> dict:
+              obstacle: Optional[ObstacleAvoidance] = None, zero_du: bool = False, log: bool = False, input_scaling=None) -> dict:
     """The tracker for agent ``agent`` of the game of ``solver`` (a ``DGSQP``): its model, vehicle, integrator, dt and track.  ``bounds``:
-    ``qu_ub``, ``qu_lb``, ``du_ub``, ``du_lb`` as ``VehicleState`` (the reference's dict)."""
+    ``qu_ub``, ``qu_lb``, ``du_ub``, ``du_lb`` as ``VehicleState`` (the reference's dict).  ``input_scaling`` as in ``CALTVMPCParams``:
+    ``du_ws`` and ``du_pred`` are then the reference's scaled rates."""
     mdl = solver.joint_dynamics.dynamics_models[agent] if 0 <= int(agent) < solver.M else None
     if mdl is None:
         raise ValueError(f'agent {agent} is outside the game\'s 0..{solver.M - 1}')
@@ -181,8 +212,13 @@ def mpc_batch(solver, agent: int, cost: TrackingCost, bounds: dict, q0, u_ws, du
     q_lb, u_lb = mdl.state2qu(bounds['qu_lb'])
     _, du_ub = mdl.state2qu(bounds['du_ub'])
     _, du_lb = mdl.state2qu(bounds['du_lb'])
-    rec = lower(agent, mdl.n_q, cost, soft, obstacle, q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, solver.N if N is None else N, qp_iters, damping, zero_du)
-    return run_batch(solver._lib, solver._h, rec, mdl.n_q, q0, u_ws, du_ws, q_ref, p_obs, log=log)
+    rec = lower(agent, mdl.n_q, cost, soft, obstacle, q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, solver.N if N is None else N, qp_iters, damping, zero_du,
+                input_scaling=input_scaling)
+    Tu = rate_scale(input_scaling)
+    out = run_batch(solver._lib, solver._h, rec, mdl.n_q, q0, u_ws, du_ws if Tu is None else np.asarray(du_ws, np.float64) / Tu, q_ref, p_obs, log=log)
+    if Tu is not None:
+        out['du_pred'] = out['du_pred'] * Tu
+    return out
 
 
 def shift_warm_start(u_pred: np.ndarray, du_pred: np.ndarray):
@@ -200,7 +236,7 @@ class CA_LTV_MPC:
     def __init__(self, dynamics, costs: TrackingCost, constraints, bounds: dict, control_params: CALTVMPCParams = None, print_method=print,
                  device: int = 0, workgroups_per_cu: int = 1):
         params = control_params if control_params is not None else CALTVMPCParams()
-        check_params(params)
+        check_params(host_scaling(params)[0])
         if isinstance(constraints, dict):
             if constraints.get('rate') is not None and any(c is not None for c in np.atleast_1d(np.asarray(constraints['rate'], dtype=object))):
                 raise NotImplementedError('CA_LTV_MPC: rate-constraint functions are not supported (the rate box is)')
@@ -256,7 +292,7 @@ class CA_LTV_MPC:
 
     def _record(self, qp_iters: int, damping: float, zero_du: bool) -> _ffi.MpcT:
         return lower(0, self.n_q, self.costs, self.soft, self.constraints, self.state_ub, self.state_lb, self.input_ub, self.input_lb,
-                     self.input_rate_ub, self.input_rate_lb, self.N, qp_iters, damping, zero_du)
+                     self.input_rate_ub, self.input_rate_lb, self.N, qp_iters, damping, zero_du, input_scaling=self.params.input_scaling)
 
     def initialize(self) -> None:
         return
@@ -276,7 +312,13 @@ class CA_LTV_MPC:
         p_obs [B, N, 2].  Returns q_pred, u_pred, du_pred, status (0 or 4 = 'qp_fail': the outputs are then the warm start), success,
         qp_steps, timing."""
         rec = self._record(self.qp_iters if qp_iters is None else qp_iters, self.damping if damping is None else damping, zero_du)
-        return run_batch(self._solver._lib, self._solver._h, rec, self.n_q, q0, u_ws, du_ws, q_ref, p_obs, log=log)
+        Tu = rate_scale(self.params.input_scaling)
+        if Tu is None:
+            return run_batch(self._solver._lib, self._solver._h, rec, self.n_q, q0, u_ws, du_ws, q_ref, p_obs, log=log)
+        # du_ws and du_pred are the reference's scaled rates du' = Tu du; the device works in du
+        out = run_batch(self._solver._lib, self._solver._h, rec, self.n_q, q0, u_ws, np.asarray(du_ws, np.float64) / Tu, q_ref, p_obs, log=log)
+        out['du_pred'] = out['du_pred'] * Tu
+        return out
 
     def set_warm_start(self, u_ws: np.ndarray, du_ws: np.ndarray, state: VehicleState = None, parameters: np.ndarray = np.array([]),
                        l_ws: np.ndarray = None) -> None:

@@ -27,6 +27,81 @@ from .types import (BodyAngularVelocity, BodyLinearVelocity, OrientationEuler, P
                     VehicleActuation, VehicleState)
 
 
+class Raceline:
+    """The two-lap, time-parametrised raceline table of ``track_lib.load_mpclab_raceline`` (track_lib.py:124-143) and the numpy mirror of
+    the device's two look-ups (csrc/dgsqp_raceline.h).  ``T`` [n] strictly increasing; ``cols`` [n, 9] = (x, y, psi, v_long, v_tran, psidot,
+    e_psi, s, e_y) with ``s`` strictly increasing.  Both look-ups are linear, evaluated as ``y0 + (y1 - y0) * ((x - x0) / (x1 - x0))`` on
+    the segment with ``x0 <= x < x1``, and continue the first / last segment linearly outside the table."""
+    COLUMNS = ('x', 'y', 'psi', 'v_long', 'v_tran', 'psidot', 'e_psi', 's', 'e_y')
+
+    def __init__(self, T, cols, lap_mat=None):
+        self.T = np.ascontiguousarray(T, np.float64)
+        self.cols = np.ascontiguousarray(cols, np.float64)
+        n = self.T.shape[0] if self.T.ndim == 1 else 0
+        if n < 2 or self.cols.shape != (n, 9):
+            raise ValueError('raceline: T [n] and cols [n, 9] with n >= 2')
+        if not (np.isfinite(self.T).all() and np.isfinite(self.cols).all()):
+            raise ValueError('raceline: a non-finite entry')
+        if not (np.diff(self.T) > 0).all():
+            raise ValueError('raceline: T is not strictly increasing')
+        if not (np.diff(self.cols[:, 7]) > 0).all():
+            raise ValueError('raceline: the s column is not strictly increasing')
+        self.lap_mat = self.cols if lap_mat is None else lap_mat
+
+    @classmethod
+    def from_file(cls, file_path, track_name, time_scale=1.0):
+        """track_lib.py:124-135: velocities divided and T multiplied by ``time_scale``; the second lap appended with ``s += L`` and
+        ``T += T[-1]``, its first row dropped."""
+        L = get_track(track_name).track_length
+        f = np.load(file_path)
+        mat = np.vstack((f['x'], f['y'], f['psi'], f['v_long'] / time_scale, f['v_tran'] / time_scale, f['psidot'] / time_scale,
+                         f['e_psi'], f['s'], f['e_y'])).T
+        T = f['t'] * time_scale
+        mat2 = mat.copy()
+        mat2[:, 7] += L
+        T2 = T + T[-1]
+        return cls(np.append(T, T2[1:]), np.vstack((mat, mat2[1:])), lap_mat=mat)
+
+    @staticmethod
+    def _lerp(X, Y, x):
+        x = np.asarray(x, np.float64)
+        i = np.clip(np.searchsorted(X, x, side='right') - 1, 0, len(X) - 2)
+        w = (x - X[i]) / (X[i + 1] - X[i])
+        if Y.ndim == 2:
+            w = w[..., None]
+        return Y[i] + (Y[i + 1] - Y[i]) * w
+
+    def s2t(self, s):
+        return self._lerp(self.cols[:, 7], self.T, s)
+
+    def eval(self, t):
+        """The nine columns at t: [..., 9]."""
+        return self._lerp(self.T, self.cols, t)
+
+    def q_ref(self, q0, N: int, dt: float):
+        """warm_start_dynamic.py:148-155 for agent states q0 [B, n_qa] (8: dynamic bicycle, 6: kinematic) -> q_ref [B, N + 1, n_qa], the
+        arithmetic of dg_raceline_ref_kernel."""
+        q0 = np.asarray(q0, np.float64)
+        nqa = q0.shape[1]
+        if nqa not in (6, 8):
+            raise ValueError('raceline: reference states are laid out for the kinematic (6) and the dynamic (8) bicycle')
+        t0 = self.s2t(q0[:, nqa - 2])
+        r0 = self.eval(t0)
+        offset = q0[:, nqa - 1] - r0[:, 8]
+        scaling = q0[:, 2] / r0[:, 3]
+        tk = t0[:, None] + dt * np.arange(N + 1, dtype=np.float64)[None, :] * scaling[:, None]
+        r = self.eval(tk)
+        out = np.zeros((q0.shape[0], N + 1, nqa))
+        out[..., 0], out[..., 1], out[..., 2] = r[..., 0], r[..., 1], r[..., 3] * scaling[:, None]
+        if nqa == 8:
+            out[..., 3], out[..., 4] = r[..., 4] * scaling[:, None], r[..., 5] * scaling[:, None]
+        out[..., nqa - 3], out[..., nqa - 2], out[..., nqa - 1] = r[..., 6], r[..., 7], r[..., 8] + offset[:, None]
+        return out
+
+
+STUDY_COLLISION_D = 2 * np.sqrt((0.37 / 2) ** 2 + (0.195 / 2) ** 2)      # monte_carlo_sampler_dynamic.py:21-22 with globals.py's VL, VW
+
+
 @dataclass
 class Game:
     """Everything ``DGSQP(...)`` takes, plus what the sampler needs."""
@@ -40,8 +115,10 @@ class Game:
     half_width: float
     obs_d: float
     name: str = ''
-    sampler: str = 'first_segment'      # 'first_segment' (chicane.py/curve.py/agents.py) or 'circuit' (comp.py)
+    sampler: str = 'first_segment'      # 'first_segment' (chicane.py/curve.py/agents.py), 'circuit' (comp.py), 'raceline' (the BARC study)
     second_car_ahead: bool = False      # the sampler also rejects placements with car 2 behind car 1 (ablation.py:387)
+    raceline: object = None             # sampler 'raceline': the ``Raceline`` the cars are drawn around and warm-started along
+    collision_d: float = 0.0            # sampler 'raceline': r1 + r2 of the placement's collision check
 
     def solver_args(self):
         return (self.joint_model, self.costs, self.agent_constraints, self.shared_constraints, self.bounds, self.params)
@@ -120,7 +197,8 @@ def ablation_racing_game(N=25, nonmono_ls=True, merit_function='stat_l1', theta_
                 name=f'ablation_N{N}_{"nms" if nonmono_ls else "ls"}_{merit_function}', second_car_ahead=True)
 
 
-def dynamic_racing_game(track_kind='curve', theta_deg=45, N=25, reg=1e-3, rk4_substeps=10, game_def='exact_dynamic', solver='v1') -> Game:
+def dynamic_racing_game(track_kind='curve', theta_deg=45, N=25, reg=1e-3, rk4_substeps=10, game_def='exact_dynamic', solver='v1',
+                        sampler=None, raceline=None) -> Game:
     """BASELINE.json config 2: 2-agent dynamic-bicycle (Pacejka) race on the curve track (curve.py:140-146), rk4 with
     M=10 sub-steps (comparison_study_barc/globals.py:17-18), vehicle of exact_dynamic_game_dynamic.py:26-66.
 
@@ -134,7 +212,10 @@ def dynamic_racing_game(track_kind='curve', theta_deg=45, N=25, reg=1e-3, rk4_su
     scenarios drive the open-loop rollout into |dx/du| ~ 1e17 (profiles/r02_dyn_curve_divergence.txt), it is kept as a
     stress case.  ``solver='v2'``: the DG-SQP v2 parameters of the reference's study (comparison_study_barc/globals.py:27-55:
     reg 1e2 decaying by 0.95, nms with frequency / memory 10, 20 line-search trials, tolerance 1e-4, up to 500 m-steps);
-    ``reg`` is then ignored.  ``track_kind='barc'`` puts the game on the study's own L_track_barc circuit."""
+    ``reg`` is then ignored.  ``track_kind='barc'`` puts the game on the study's own L_track_barc circuit, with ``sampler='circuit'`` (the
+    default there: the placement of DGSQP_comp_monte_carlo.py and PID warm starts) or ``sampler='raceline'``: the study's own front end
+    (monte_carlo_sampler_dynamic.py, warm_start_dynamic.py), which needs ``raceline`` -- a ``Raceline``, or the path of the study's
+    ``L_track_barc_raceline.npz`` (loaded with its time_scale 1.7)."""
     dt, half_width, M = 0.1, 1.0, 2
     if track_kind == 'barc':
         track = get_track('L_track_barc')
@@ -149,6 +230,17 @@ def dynamic_racing_game(track_kind='curve', theta_deg=45, N=25, reg=1e-3, rk4_su
     joint = CasadiDecoupledMultiAgentDynamicsModel(0, models, MultiAgentModelConfig(
         dt=dt, discretization_method='rk4', use_mx=False, code_gen=False, verbose=False, compute_hessians=True,
         M=rk4_substeps))
+    if sampler is None:
+        sampler = 'circuit' if track_kind == 'barc' else 'first_segment'
+    if sampler not in ('circuit', 'first_segment', 'raceline') or (sampler != 'first_segment') != (track_kind == 'barc'):
+        raise ValueError(f"sampler {sampler!r} does not fit track_kind {track_kind!r} ('circuit' / 'raceline': 'barc'; 'first_segment': the others)")
+    if sampler == 'raceline':
+        if raceline is None:
+            raise ValueError("sampler='raceline' needs raceline= (a Raceline, or the path of L_track_barc_raceline.npz)")
+        if not isinstance(raceline, Raceline):
+            raceline = Raceline.from_file(raceline, 'L_track_barc', time_scale=1.7)
+    else:
+        raceline = None
     if solver == 'v2':
         params = DGSQPV2Params(solver_name='DGSQP', dt=dt, N=N, nms=True, nms_frequency=10, nms_memory_size=10, line_search_iters=20,
                                sqp_iters=500, p_tol=1e-4, d_tol=1e-4, reg=1e2, reg_decay=0.95, delta_decay=0.99, merit_decrease=0.01,
@@ -171,7 +263,7 @@ def dynamic_racing_game(track_kind='curve', theta_deg=45, N=25, reg=1e-3, rk4_su
         raise ValueError(game_def)
     return Game(joint, [cost() for _ in range(M)], rows, CollisionAvoidance([r] * M), _bounds(half_width, M), params, track,
                 half_width, 2 * r, name=f'dyn_{track_kind}_N{N}' + ('' if game_def == 'exact_dynamic' else '_' + game_def) + ('_v2' if solver == 'v2' else ''),
-                sampler='circuit' if track_kind == 'barc' else 'first_segment')
+                sampler=sampler, raceline=raceline, collision_d=STUDY_COLLISION_D if sampler == 'raceline' else 0.0)
 
 
 def barc_racing_game(N=15, M=2, reg=0.0) -> Game:
@@ -381,6 +473,8 @@ def sample_scenarios(game: Game, B: int, seed: int = 1, max_rounds: int = 200, s
     Returns x0 [B, n_q] and u_ws [B, N, n_u] (time-major, as ``set_warm_start`` expects).
     With ``solver`` (a ``dgsqp_amd.solver.DGSQP`` of this game) the PID warm starts and the collision check run on the
     device (``dgsqp_pid_warm_start_batch``); the random draws are the same either way."""
+    if game.sampler == 'raceline':
+        return _sample_scenarios_raceline(game, B, seed, solver)
     if game.sampler == 'circuit':
         return _sample_scenarios_circuit(game, B, seed, max_rounds)
     if game.sampler == 'merge':
@@ -527,6 +621,93 @@ def _sample_scenarios_circuit(game: Game, B: int, seed: int, max_rounds: int):
     if x0.shape[0] < B:
         raise RuntimeError('sampler did not produce enough collision-free scenarios')
     return np.ascontiguousarray(x0), np.ascontiguousarray(u)
+
+
+def study_tracker(game: Game) -> dict:
+    """The LTV-MPC tracker of warm_start_dynamic.py:60-127 for a car of ``game``: ``cost`` (Q = diag(1, 0, 0, 1, 1, 1) on (v_long, v_tran,
+    psidot, e_psi, s, e_y), input weights 1e-2, rate weights 0.1; x, y carry zero weight), ``bounds`` (:68-81), ``params`` (:115-122:
+    state_scaling, input_scaling = [2, 0.45], damping 0.75, qp_iters 5) and ``u_init`` / ``du_init`` = 0.01 (:156-157)."""
+    from .ltv_mpc import TrackingCost
+    from .solver_types import CALTVMPCParams
+    mdl = game.joint_model.dynamics_models[0]
+    L, H = game.track.track_length, game.track.half_width
+    w = [0, 0, 1, 0, 0, 1, 1, 1] if mdl.n_q == 8 else [0, 0, 1, 1, 1, 1]
+    ub = VehicleState(x=Position(x=1e9, y=1e9), e=OrientationEuler(psi=1e9), p=ParametricPose(s=2 * L, x_tran=H, e_psi=1e9),
+                      v=BodyLinearVelocity(v_long=5, v_tran=2), w=BodyAngularVelocity(w_psi=10), u=VehicleActuation(u_a=2.0, u_steer=0.436))
+    lb = VehicleState(x=Position(x=-1e9, y=-1e9), e=OrientationEuler(psi=-1e9), p=ParametricPose(s=-2 * L, x_tran=-H, e_psi=-1e9),
+                      v=BodyLinearVelocity(v_long=0.1, v_tran=-2), w=BodyAngularVelocity(w_psi=-10), u=VehicleActuation(u_a=-2.0, u_steer=-0.436))
+    bounds = dict(qu_ub=ub, qu_lb=lb, du_ub=VehicleState(u=VehicleActuation(u_a=10.0, u_steer=4.5)),
+                  du_lb=VehicleState(u=VehicleActuation(u_a=-10.0, u_steer=-4.5)))
+    params = CALTVMPCParams(N=game.params.N, state_scaling=[10, 10, 7, np.pi / 2, L, 1.0], input_scaling=[2, 0.45], damping=0.75, qp_iters=5,
+                            delay=None, verbose=False, qp_interface='casadi')
+    return dict(cost=TrackingCost(state_weight=w, input_weight=(1e-2, 1e-2), rate_weight=(0.1, 0.1)), bounds=bounds, params=params,
+                u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5)
+
+
+def raceline_ws(game: Game, tracker: dict = None):
+    """``dgsqp_raceline_ws_t`` of ``tracker`` (default: ``study_tracker(game)``): the record of ``ltv_mpc.lower`` with the parameters'
+    ``input_scaling`` lowered, the initial constants and the first phase's iterations and damping."""
+    from . import _ffi, ltv_mpc
+    t = study_tracker(game) if tracker is None else tracker
+    ltv_mpc.check_params(ltv_mpc.host_scaling(t['params'])[0])
+    mdl = game.joint_model.dynamics_models[0]
+    b = t['bounds']
+    q_ub, u_ub = mdl.state2qu(b['qu_ub'])
+    q_lb, u_lb = mdl.state2qu(b['qu_lb'])
+    _, du_ub = mdl.state2qu(b['du_ub'])
+    _, du_lb = mdl.state2qu(b['du_lb'])
+    p = t['params']
+    W = _ffi.RacelineWsT()
+    W.mpc = ltv_mpc.lower(0, mdl.n_q, t['cost'], None, None, q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, int(p.N), int(p.qp_iters), float(p.damping),
+                          input_scaling=p.input_scaling)
+    W.u_init, W.du_init = float(t.get('u_init', 0.01)), float(t.get('du_init', 0.01))
+    W.init_iters, W.init_damping = int(t.get('init_iters', 2)), float(t.get('init_damping', 0.5))
+    return W
+
+
+def place_raceline_sequential(game: Game, rng):
+    """One pass of ``get_sample``'s loop (monte_carlo_sampler_dynamic.py:27-57): six scalar ``rng.random()`` calls in the script's order
+    (s1, e_y1, v1, s2, e_y2, v2).  Returns (x0 [n_q], margin): the candidate is in collision when margin >= 0."""
+    rl, track = game.raceline, game.track
+    L, lim = track.track_length, 0.9 * track.half_width
+    models = game.joint_model.dynamics_models
+    q, xy = [], []
+    s1 = None
+    for a, mdl in enumerate(models[:2]):
+        s = L * rng.random() if a == 0 else s1 + 1.2 * game.obs_d * (2 * rng.random() - 1)
+        s1 = s if a == 0 else s1
+        r = rl.eval(rl.s2t(s))
+        ey = max(min(r[8] + (2 * rng.random() - 1), lim), -lim)
+        v = r[3] + (1.5 * rng.random() - 0.75)
+        x, y = track.local_to_global((s, ey, 0.0))[:2]
+        qa = np.zeros(mdl.n_q)
+        qa[0], qa[1], qa[2], qa[mdl.epsi_idx], qa[mdl.s_idx], qa[mdl.ey_idx] = x, y, v, r[6], s, ey
+        q.append(qa); xy.append((x, y))
+    d2 = (xy[0][0] - xy[1][0]) ** 2 + (xy[0][1] - xy[1][1]) ** 2
+    return np.concatenate(q), game.collision_d ** 2 - d2
+
+
+def _sample_scenarios_raceline(game: Game, B: int, seed: int, solver):
+    """The study's own sequential draws (monte_carlo_main.py:92-100 with monte_carlo_sampler_dynamic.py): ``np.random.default_rng(seed)``
+    (the script seeds with 0), candidates redrawn while they collide, then the tracker's warm start -- on the device, ``solver`` is
+    required -- and a sample whose warm start fails is thrown away and redrawn."""
+    if solver is None:
+        raise ValueError("sampler 'raceline': the warm start is the LTV-MPC tracker, which runs on the device: pass solver=")
+    rng = np.random.default_rng(seed)
+    solver.set_raceline(game.raceline)
+    W = raceline_ws(game)
+    x0s, uws, have = [], [], 0
+    while have < B:
+        cand = []
+        while len(cand) < max(64, 2 * (B - have)):
+            x0, margin = place_raceline_sequential(game, rng)
+            if margin < 0:
+                cand.append(x0)
+        cand = np.array(cand)
+        out = solver.raceline_warm_start_batch(cand, W)
+        x0s.append(cand[out['ok']]); uws.append(out['u_ws'][out['ok']])
+        have += int(out['ok'].sum())
+    return np.ascontiguousarray(np.concatenate(x0s)[:B]), np.ascontiguousarray(np.concatenate(uws)[:B])
 
 
 def _sample_scenarios_merge(game: Game, B: int, seed: int):

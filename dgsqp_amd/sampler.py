@@ -178,3 +178,66 @@ def sample_scenarios_counter(game, B: int, seed: int = 1, chunk: int = 512, max_
             used = c0 + int(take[-1]) + 1
         c0 += chunk
     return np.ascontiguousarray(np.concatenate(x0s)), np.ascontiguousarray(np.concatenate(uws)), used
+
+
+# ---- the BARC study's sampler (dgsqp_sample_raceline_batch, csrc/dgsqp_raceline.h: dg_raceline_place_kernel) ----
+def raceline_sampler_spec(game, seed: int) -> _ffi.RacelineSamplerT:
+    """The C-ABI description of the study's placement (include/dgsqp.h: dgsqp_raceline_sampler_t)."""
+    kp = np.asarray(game.track.key_pts, dtype=float)
+    if kp.shape[0] > _ffi.MAX_SEGS + 1:
+        raise ValueError('the device sampler places cars on arc tracks of at most %d segments' % _ffi.MAX_SEGS)
+    S = _ffi.RacelineSamplerT()
+    S.n_key, S.seed = kp.shape[0], int(seed)
+    S.half_width, S.obs_d, S.collision_d = float(game.track.half_width), float(game.obs_d), float(game.collision_d)
+    for i in range(kp.shape[0]):
+        for j in range(6):
+            S.key_pts[i][j] = float(kp[i, j])
+    return S
+
+
+def place_raceline(game, seed: int, cand):
+    """monte_carlo_sampler_dynamic.py:27-57 for the candidates ``cand`` with the counter-based uniforms, six per candidate in the script's
+    order (s1, e_y1, v1, s2, e_y2, v2) -> (x0 [n, n_q], margin [n]); a candidate is in collision when margin >= 0."""
+    cand = np.asarray(cand, dtype=np.uint64)
+    U = lambda k: uniform(seed, cand, k)
+    rl, track = game.raceline, game.track
+    L, lim = track.track_length, 0.9 * track.half_width
+    models = game.joint_model.dynamics_models
+    s1 = L * U(0)
+    q0, xy = [], []
+    for a, mdl in enumerate(models[:2]):
+        s = s1 if a == 0 else s1 + 1.2 * game.obs_d * (2 * U(3) - 1)
+        r = rl.eval(rl.s2t(s))
+        ey = np.maximum(np.minimum(r[:, 8] + (2 * U(3 * a + 1) - 1), lim), -lim)
+        v = r[:, 3] + (1.5 * U(3 * a + 2) - 0.75)
+        p = np.array([track.local_to_global((si, ei, 0.0))[:2] for si, ei in zip(s, ey)]).reshape(-1, 2)
+        q = np.zeros((len(cand), mdl.n_q))
+        q[:, 0], q[:, 1], q[:, 2] = p[:, 0], p[:, 1], v
+        q[:, mdl.epsi_idx], q[:, mdl.s_idx], q[:, mdl.ey_idx] = r[:, 6], s, ey
+        q0.append(q); xy.append(p)
+    d = xy[0] - xy[1]
+    return np.concatenate(q0, axis=1), game.collision_d ** 2 - (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+
+
+def sample_raceline_counter(game, solver, B: int, seed: int = 1, ws=None, max_candidates: int = 10_000_000):
+    """Host mirror of ``dgsqp_sample_raceline_batch``: placement and collision check in numpy, the warm-start program through
+    ``solver.raceline_warm_start_batch`` (the tracker has no host form), the first B accepted candidates in candidate order, in the device's
+    rounds.  Returns x0 [B, n_q], u_ws [B, N, n_u] (time-major), the candidates consumed and the smallest |margin| seen."""
+    from .montecarlo import raceline_ws
+    W = raceline_ws(game) if ws is None else ws
+    nround = max(256, min(2 * B, 1 << 16))
+    x0s, uws, have, c0, used, closest = [], [], 0, 0, 0, np.inf
+    while have < B:
+        if c0 >= max_candidates:
+            raise RuntimeError('sampler did not produce enough scenarios')
+        x0, margin = place_raceline(game, seed, np.arange(c0, c0 + nround, dtype=np.uint64))
+        closest = min(closest, float(np.abs(margin).min()))
+        out = solver.raceline_warm_start_batch(x0, W)
+        idx = np.nonzero((margin < 0) & out['ok'])[0]
+        take = idx[:B - have]
+        x0s.append(x0[take]); uws.append(out['u_ws'][take])
+        have += len(take)
+        if have >= B:
+            used = c0 + int(take[-1]) + 1
+        c0 += nround
+    return np.ascontiguousarray(np.concatenate(x0s)), np.ascontiguousarray(np.concatenate(uws)), used, closest

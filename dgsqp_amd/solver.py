@@ -904,6 +904,77 @@ class DGSQP(AbstractSolver):
             out['u_ws'] = np.ascontiguousarray(u_am.reshape(B, self.M, self.N, nua).transpose(0, 2, 1, 3).reshape(B, self.N, self.n_u))
         return out
 
+    # ---- raceline warm starts: the BARC study's front end (csrc/dgsqp_raceline.h) -------------------
+    def _raceline_check(self, rc: int, what: str):
+        if rc != 0:
+            msg = self._lib.dgsqp_last_error(self._h)
+            raise (ValueError if rc == _ffi.E_ARG else MemoryError if rc == _ffi.E_TOO_LARGE else RuntimeError)(
+                f'{what} failed ({rc}): {msg.decode() if msg else ""}')
+
+    def set_raceline(self, raceline):
+        """Copy a ``montecarlo.Raceline`` (or ``(T, cols)``) to the device (``dgsqp_set_raceline``); ``None`` clears it."""
+        if raceline is None:
+            return self._raceline_check(self._lib.dgsqp_set_raceline(self._h, 0, None, None), 'dgsqp_set_raceline')
+        T, cols = (raceline.T, raceline.cols) if hasattr(raceline, 'cols') else raceline
+        T, cols = np.ascontiguousarray(T, np.float64), np.ascontiguousarray(cols, np.float64)
+        if T.ndim != 1 or cols.shape != (T.shape[0], _ffi.RL_COLS):
+            raise ValueError(f'raceline: T [n] and cols [n, {_ffi.RL_COLS}]')
+        self._raceline_check(self._lib.dgsqp_set_raceline(self._h, T.shape[0], _ffi.dptr(T), _ffi.dptr(cols)), 'dgsqp_set_raceline')
+
+    def raceline_warm_start_batch(self, x0, ws, fetch=True, B=None):
+        """The warm-start program of warm_start_dynamic.py for every car of a batch, on the device (``dgsqp_raceline_warm_start_batch``):
+        reference trajectory along the raceline, the tracker's two phases, assembly.  ``ws``: ``montecarlo.raceline_ws(game)``.  ``x0``
+        [B, n_q], or ``None`` with ``B``: the staged batch of B scenarios, whose staged warm start receives the result.  Returns dict(u_ws
+        [B, N, n_u] time-major, ok [B] bool)."""
+        if x0 is None:
+            if B is None:
+                raise ValueError('x0=None (the staged batch) needs B')
+            B, px = int(B), None
+        else:
+            x0 = np.ascontiguousarray(x0, np.float64)
+            if x0.ndim != 2 or x0.shape[1] != self.n_q:
+                raise ValueError(f'x0 must be [B, {self.n_q}]')
+            B, px = x0.shape[0], _ffi.dptr(x0)
+        u_am = np.empty((B, self.n)) if fetch else None
+        ok = np.empty(B, np.int32) if fetch else None
+        self._raceline_check(self._lib.dgsqp_raceline_warm_start_batch(self._h, B, px, C.byref(ws), _ffi.dptr(u_am), _ffi.iptr(ok)),
+                             'dgsqp_raceline_warm_start_batch')
+        if not fetch:
+            return {}
+        nua = self.n_u // self.M
+        return dict(u_ws=np.ascontiguousarray(u_am.reshape(B, self.M, self.N, nua).transpose(0, 2, 1, 3).reshape(B, self.N, self.n_u)),
+                    ok=ok.astype(bool))
+
+    def fetch_raceline_ref(self, B: int):
+        """Test hook: q_ref [B, M, N + 1, n_qa] of the last warm-start program."""
+        out = np.empty((B, self.M, self.N + 1, self.num_qa_d[0]))
+        self._raceline_check(self._lib.dgsqp_fetch_raceline_ref(self._h, _ffi.dptr(out), out.size), 'dgsqp_fetch_raceline_ref')
+        return out
+
+    def sample_raceline_batch(self, game, B: int, seed: int = 1, ws=None, stage=False, fetch=True):
+        """The BARC study's sampler on the device (``dgsqp_sample_raceline_batch``, mirrored by ``sampler.sample_raceline_counter``): cars
+        placed around ``game.raceline``, the tracker's warm starts, rejection of colliding placements and of failed warm starts, the first
+        ``B`` accepted candidates in candidate order.  ``ws`` defaults to ``montecarlo.raceline_ws(game)``; ``stage`` / ``fetch`` as
+        ``sample_batch``.  Returns dict(x0, u_ws [B, N, n_u] time-major, candidates)."""
+        from . import sampler as smp
+        from .montecarlo import raceline_ws
+        if game.raceline is None:
+            raise ValueError("the game carries no raceline (dynamic_racing_game(..., sampler='raceline', raceline=...))")
+        self.set_raceline(game.raceline)
+        spec = smp.raceline_sampler_spec(game, seed)
+        W = raceline_ws(game) if ws is None else ws
+        x0 = np.empty((B, self.n_q)) if fetch else None
+        u_am = np.empty((B, self.n)) if fetch else None
+        used = C.c_int64(0)
+        self._raceline_check(self._lib.dgsqp_sample_raceline_batch(self._h, int(B), C.byref(spec), C.byref(W), _ffi.dptr(x0), _ffi.dptr(u_am),
+                                                                   C.byref(used), 1 if stage else 0), 'dgsqp_sample_raceline_batch')
+        out = dict(candidates=int(used.value))
+        if fetch:
+            nua = self.n_u // self.M
+            out['x0'] = x0
+            out['u_ws'] = np.ascontiguousarray(u_am.reshape(B, self.M, self.N, nua).transpose(0, 2, 1, 3).reshape(B, self.N, self.n_u))
+        return out
+
     # ---- reference single-scenario surface -----------------------------------------------------
     def solve(self, states: List[VehicleState], parameters: np.ndarray = np.array([])) -> dict:
         solve_start = time.time()

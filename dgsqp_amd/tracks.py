@@ -310,3 +310,22 @@ def get_track(name: str):
         raise ValueError('Chosen Track is unavailable: %s\n Available Tracks: %s' % (name, sorted(_TRACK_DATA)))
     d = _TRACK_DATA[key]
     return RadiusArclengthTrack().initialize(d['track_width'], d['slack'], np.array(d['cl_segs'], dtype=float))
+
+
+def load_mpclab_raceline(file_path, track_name, time_scale=1.0):
+    """Reference DGSQP/tracks/track_lib.py:124-143: the reference's triple ``(raceline, s2t, raceline_mat)``.  ``raceline(t)`` returns the
+    nine interpolated columns (x, y, psi, v_long, v_tran, psidot, e_psi, s, e_y) of the two-lap table -- a list of nine values, as the
+    CasADi function does, each of ``t``'s shape --, ``s2t(s)`` the table's time at arclength ``s``; ``raceline_mat`` is the one-lap
+    table [n, 9].  Both callables are the numpy look-ups of ``montecarlo.Raceline`` (``raceline.table`` is that object): linear, and
+    continued linearly outside the table."""
+    from .montecarlo import Raceline
+    rl = Raceline.from_file(file_path, track_name, time_scale)
+
+    def raceline(t):
+        v = rl.eval(t)
+        return [v[..., c] for c in range(v.shape[-1])]
+
+    def s2t(s):
+        return rl.s2t(s)
+    raceline.table = s2t.table = rl
+    return raceline, s2t, rl.lap_mat

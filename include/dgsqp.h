@@ -786,6 +786,67 @@ int dgsqp_set_mpc_log(dgsqp_handle_t h, int on);
 /* D, D_bar [B][qp_iters][len_D], lam [B][qp_iters][n_rows] of the last launch; capacity = scenarios each array can hold. */
 int dgsqp_fetch_mpc_log(dgsqp_handle_t h, double* D, double* D_bar, double* lam, int64_t capacity);
 
+/*
+ * Raceline warm starts: the front end of scripts/comparison_study_barc/monte_carlo_main.py (monte_carlo_sampler_dynamic.py,
+ * warm_start_dynamic.py) on the device.
+ *
+ * The raceline is the two-lap, time-parametrised table of track_lib.load_mpclab_raceline: n knots T (strictly increasing) and nine
+ * columns (x, y, psi, v_long, v_tran, psidot, e_psi, s, e_y), s strictly increasing.  Two look-ups (csrc/dgsqp_raceline.h): s2t(s),
+ * linear interpolation of T over the s column, and raceline(t), linear over T; both find their segment by binary search and continue
+ * the first / last segment linearly outside the table (what CasADi's 'linear' interpolant is understood to do: a stated definition).
+ * dgsqp_set_raceline validates and copies the table to the device; T = NULL or cols = NULL clears it.  DGSQP_E_ARG, message starting
+ * "raceline: ": n < 2, a non-finite entry, T or the s column not strictly increasing.
+ */
+#define DGSQP_RL_COLS 9
+int dgsqp_set_raceline(dgsqp_handle_t h, int64_t n, const double* T /* [n] */, const double* cols /* [n][9] */);
+
+/*
+ * The warm-start program of warm_start_dynamic.py:145-165 for every agent of a batch, stream-ordered on the device:
+ *   reference   t0 = s2t(s_0), offset = e_y0 - raceline(t0)[8], scaling = v_long0 / raceline(t0)[3], t_k = t0 + dt k scaling,
+ *               q_ref_k = raceline(t_k)[3:] with the three velocities multiplied by scaling and e_y shifted by offset, laid out for the
+ *               agent's model: dynamic bicycle (x, y, v_long, v_tran, psidot, e_psi, s, e_y), kinematic bicycle (x, y, v_long, e_psi,
+ *               s, e_y); x, y come from the raceline (give them zero weight).  Unicycle models are refused.
+ *   phase 1     the tracker (dg_mpc_kernel) with zero_du, init_iters iterations and init_damping from u_ws = u_init, du_ws = du_init:
+ *               the loop of CA_LTV_MPC.set_warm_start; its status is ignored, as the reference ignores it
+ *   chain       u_ws <- (u_ws[0], u_pred), du_ws <- du_pred
+ *   phase 2     the tracker with the template's qp_iters and damping: CA_LTV_MPC.solve
+ *   assemble    u_pred of phase 2 into the game's agent-major u_ws; ok &= (status == 0)
+ * mpc.agent and mpc.zero_du are ignored; the record is planned per agent (what dgsqp_set_mpc refuses is refused here, message starting
+ * "mpc: ").  The handle's own tracker setting (dgsqp_set_mpc) is not touched.
+ */
+typedef struct {
+  dgsqp_mpc_t mpc;
+  double u_init, du_init;   /* warm_start_dynamic.py:156-157: 0.01 */
+  int32_t init_iters, reserved_;
+  double init_damping;      /* CA_LTV_MPC.py:174-197: 2 iterations, damping 0.5 */
+} dgsqp_raceline_ws_t;
+/* x0 [B][n_q] (host), or NULL: the handle's staged batch of B scenarios, whose staged u_ws then receives the result
+   (dgsqp_solve_staged may follow).  u_ws_out [B][n] agent-major, ok_out [B] (1: every agent's phase 2 succeeded); each may be NULL.
+   DGSQP_E_ARG, message starting "raceline: ": no raceline set, a unicycle agent, agents of different models, B < 0, x0 = NULL without a
+   staged batch of that size. */
+int dgsqp_raceline_warm_start_batch(dgsqp_handle_t h, int64_t B, const double* x0, const dgsqp_raceline_ws_t* ws, double* u_ws_out,
+                                    int32_t* ok_out);
+/* Test hook: q_ref [B][M][N+1][n_qa] of the last dgsqp_raceline_warm_start_batch (of the last round of dgsqp_sample_raceline_batch);
+   capacity_doubles = what out can hold (DGSQP_E_ARG when it is too small or when no such call has run). */
+int dgsqp_fetch_raceline_ref(dgsqp_handle_t h, double* out, int64_t capacity_doubles);
+
+/*
+ * The sampler of monte_carlo_sampler_dynamic.py:27-57 (two cars), in the rounds of dgsqp_sample_batch with the same counter-based
+ * uniforms, six per candidate: s1 = L u0, e_y1 = clip(raceline e_y + (2 u1 - 1), -+0.9 half_width), v1 = raceline v_long + (1.5 u2 - 0.75),
+ * e_psi1 = the raceline's; s2 = s1 + 1.2 obs_d (2 u3 - 1) and the rest likewise from the raceline at s2 with u4, u5.  A candidate is
+ * rejected when collision_d^2 - |p1 - p2|^2 >= 0, or when the warm-start program reports ok = 0 (the study redraws both).
+ */
+typedef struct {
+  int32_t n_key, reserved_;
+  uint64_t seed;
+  double half_width, obs_d;
+  double collision_d;       /* r1 + r2; the study: 2 sqrt((0.37 / 2)^2 + (0.195 / 2)^2) */
+  double key_pts[DGSQP_MAX_SEGS + 1][6];
+} dgsqp_raceline_sampler_t;
+/* x0_out, u_ws_out, candidates, stage: as dgsqp_sample_batch. */
+int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_sampler_t* spec, const dgsqp_raceline_ws_t* ws,
+                                double* x0_out, double* u_ws_out, int64_t* candidates, int stage);
+
 
 /*
  * Multi-GPU (one process per GPU, scenarios sharded, no data-path collective): the library owns the RCCL communicator.
