@@ -160,6 +160,18 @@ class RacelineSamplerT(C.Structure):
                 ('collision_d', C.c_double), ('key_pts', (C.c_double * 6) * (MAX_SEGS + 1))]
 
 
+class RacelineSplineSamplerT(C.Structure):
+    """dgsqp_raceline_spline_sampler_t: the placement of comparison_study_f1/monte_carlo_sampler.py (sampler.raceline_spline_sampler_spec)."""
+    _fields_ = [('seed', C.c_uint64), ('s_lo', C.c_double), ('s_hi', C.c_double), ('gap_lo', C.c_double), ('gap_hi', C.c_double),
+                ('ey_clip', C.c_double), ('collision_d', C.c_double)]
+
+
+class TrackFrameT(C.Structure):
+    """dgsqp_track_frame_t: the track of the batched frame transforms (tracks.track_frame_spec fills it); n_key = 0: the handle's spline."""
+    _fields_ = [('n_key', C.c_int32), ('_pad', C.c_int32), ('half_width', C.c_double), ('slack', C.c_double),
+                ('key_pts', (C.c_double * 6) * (MAX_SEGS + 1))]
+
+
 MPC_ROW_RATE, MPC_ROW_SLACK, MPC_ROW_INPUT, MPC_ROW_STATE, MPC_ROW_SOFT, MPC_ROW_OBS = range(6)     # DGSQP_MPC_ROW_*
 MPC_NMAX = 128                                                                                      # DGSQP_MPC_NMAX
 E_ARG, E_DEVICE, E_NOMEM, E_TOO_LARGE = -1, -2, -3, -4                                              # DGSQP_E_*
@@ -240,6 +252,10 @@ SIGNATURES = {
     'dgsqp_fetch_raceline_ref': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_sample_raceline_batch': (C.c_int, [_H, C.c_int64, C.POINTER(RacelineSamplerT), C.POINTER(RacelineWsT), _PD, _PD,
                                               C.POINTER(C.c_int64), C.c_int]),
+    'dgsqp_sample_raceline_spline_batch': (C.c_int, [_H, C.c_int64, C.POINTER(RacelineSplineSamplerT), C.POINTER(RacelineWsT), _PD, _PD,
+                                                     C.POINTER(C.c_int64), C.c_int]),
+    'dgsqp_local_to_global_batch': (C.c_int, [_H, C.c_int64, C.POINTER(TrackFrameT), _PD, _PD]),
+    'dgsqp_global_to_local_batch': (C.c_int, [_H, C.c_int64, C.POINTER(TrackFrameT), _PD, _PD, _PD, _PI]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)
 

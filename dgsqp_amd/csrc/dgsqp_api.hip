@@ -130,6 +130,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 #include "dgsqp_sampler.h"
 #include "dgsqp_mpc.h"
 #include "dgsqp_raceline.h"
+#include "dgsqp_track_frame.h"
 
 // Test hook: one _evaluate(hessian=True) (+ dual init) per scenario, results expanded to dense arrays.
 __global__ void __launch_bounds__(DG_BLOCK, 2)
@@ -2164,7 +2165,10 @@ int dgsqp_sample_batch(dgsqp_handle_t h, int64_t B, const dgsqp_sampler_t* spec,
   if (!h || B < 0 || !spec || spec->kind < 0 || spec->kind > DGSQP_SAMPLER_MERGE) { if (h) h->err = "bad argument"; return DGSQP_E_ARG; }
   const DgProb& D = h->hp;
   const bool merge = spec->kind == DGSQP_SAMPLER_MERGE;
-  if (!merge && (!pid || pid->substeps < 1 || spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1)) { h->err = "bad sampler description"; return DGSQP_E_ARG; }
+  // n_key = 0 on a spline-track handle: the cars are placed on the handle's spline (dg_sample_place_spline_kernel)
+  const bool on_spline = !merge && spec->n_key == 0 && D.P.track_kind == DGSQP_TRACK_SPLINE;
+  if (on_spline && spec->kind != DGSQP_SAMPLER_CIRCUIT) { h->err = "sampler: a spline track takes the circuit sampler only (first_segment / independent need seg0_len, the first segment of an arc track)"; return DGSQP_E_ARG; }
+  if (!merge && (!pid || pid->substeps < 1 || (!on_spline && (spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1)))) { h->err = "bad sampler description"; return DGSQP_E_ARG; }
   if (spec->kind == DGSQP_SAMPLER_FIRST_SEGMENT && D.M != 2) { h->err = "the first-segment sampler places two cars"; return DGSQP_E_ARG; }
   for (int a = 0; a < D.M; a++)
     if ((D.mdl[a] == DG_UNI) != merge) { h->err = "sampler and vehicle model do not fit (merge: unicycles; the others: Frenet-frame models)"; return DGSQP_E_ARG; }
@@ -2184,7 +2188,8 @@ int dgsqp_sample_batch(dgsqp_handle_t h, int64_t B, const dgsqp_sampler_t* spec,
     unsigned long long c0 = 0;
     for (int round = 0; have < B; round++) {
       if (round > 10000) { h->err = "sampler did not produce enough collision-free scenarios"; return DGSQP_E_ARG; }
-      hipLaunchKernelGGL(dg_sample_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, dq0, dok);
+      if (on_spline) hipLaunchKernelGGL(dg_sample_place_spline_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, dq0, dok);
+      else hipLaunchKernelGGL(dg_sample_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, dq0, dok);
       HIPCHK(h, hipGetLastError());
       if (merge) {
         hipLaunchKernelGGL(dg_sample_zero_rollout_kernel, dim3((unsigned)((nround * D.M + 255) / 256)), dim3(256), 0, h->stream, nround, dq0, dq);
@@ -2398,15 +2403,11 @@ int dgsqp_fetch_raceline_ref(dgsqp_handle_t h, double* out, int64_t capacity_dou
   return DGSQP_OK;
 }
 
-int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_sampler_t* spec, const dgsqp_raceline_ws_t* W,
-                                double* x0_out, double* u_ws_out, int64_t* candidates, int stage) {
-  if (!h) return DGSQP_E_ARG;
-  if (B < 0 || !spec) return refuse(h, "raceline: ", "bad argument (B < 0 or no sampler description)");
-  if (spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1 || !(spec->collision_d >= 0.0) || !std::isfinite(spec->collision_d) ||
-      !std::isfinite(spec->obs_d) || !std::isfinite(spec->half_width) || first_non_finite(&spec->key_pts[0][0], (int64_t)spec->n_key * 6) >= 0 ||
-      !(spec->key_pts[spec->n_key - 1][3] > 0.0))          // (the placement wraps s into [0, L): L must be a positive length)
-    return refuse(h, "raceline: ", "bad sampler description");
-  { const int rc = raceline_check(h, W); if (rc) return rc; }
+// The rounds the two raceline samplers share: `place(nround, c0, dq0, dcol)` enqueues the placement of candidates c0 .. c0 + nround - 1,
+// then the warm-start program, the scan and the gather, until B scenarios are accepted.  The callers have checked their descriptions.
+extern "C++" template <class F>
+int raceline_rounds(dgsqp_solver* h, int64_t B, const dgsqp_raceline_ws_t* W, F place, double* x0_out, double* u_ws_out,
+                    int64_t* candidates, int stage) {
   const DgProb& D = h->hp;
   if (D.M != 2) return refuse(h, "raceline: ", "the study's sampler places two cars");
   if (candidates) *candidates = 0;
@@ -2414,10 +2415,6 @@ int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_racelin
   { const int rc = stage_begin(h, B); if (rc) return rc; }
   double *const d_x0 = h->staged.dbl(DG_Q), *const d_uws = h->staged.dbl(DG_UWS);
   const int64_t nround = std::max<int64_t>(256, std::min<int64_t>(2 * B, 1 << 16));        // candidates per round, as dgsqp_sample_batch
-  dgsqp_sampler_t track;
-  memset(&track, 0, sizeof track);
-  track.n_key = spec->n_key;
-  memcpy(track.key_pts, spec->key_pts, sizeof track.key_pts);
   TmpBuf tb;
   DgRacelineProgram P;
   { const int rc = raceline_program(h, *W, nround, tb, P); if (rc) { h->B = 0; return rc; } }
@@ -2429,7 +2426,7 @@ int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_racelin
     unsigned long long c0 = 0;
     for (int round = 0; have < B; round++) {
       if (round > 10000) { h->err = "raceline: the sampler did not produce enough scenarios"; return DGSQP_E_ARG; }
-      hipLaunchKernelGGL(dg_raceline_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, track, h->rl.dev, dq0, dcol);
+      place(nround, c0, dq0, dcol);
       HIPCHK(h, hipGetLastError());
       { const int rc = raceline_enqueue(h, P, nround, dq0, du, dok); if (rc) return rc; }
       hipLaunchKernelGGL(dg_sample_scan_kernel, dim3(1), dim3(1024), 0, h->stream, nround, dok, dcol, dpos, dcnt);
@@ -2452,6 +2449,119 @@ int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_racelin
   if (x0_out) HIPCHK(h, hipMemcpy(x0_out, d_x0, sizeof(double) * B * D.nq, hipMemcpyDeviceToHost));
   if (u_ws_out) HIPCHK(h, hipMemcpy(u_ws_out, d_uws, sizeof(double) * B * D.n, hipMemcpyDeviceToHost));
   h->B = stage ? B : 0;
+  return DGSQP_OK;
+}
+
+int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_sampler_t* spec, const dgsqp_raceline_ws_t* W,
+                                double* x0_out, double* u_ws_out, int64_t* candidates, int stage) {
+  if (!h) return DGSQP_E_ARG;
+  if (B < 0 || !spec) return refuse(h, "raceline: ", "bad argument (B < 0 or no sampler description)");
+  if (spec->n_key < 2 || spec->n_key > DGSQP_MAX_SEGS + 1 || !(spec->collision_d >= 0.0) || !std::isfinite(spec->collision_d) ||
+      !std::isfinite(spec->obs_d) || !std::isfinite(spec->half_width) || first_non_finite(&spec->key_pts[0][0], (int64_t)spec->n_key * 6) >= 0 ||
+      !(spec->key_pts[spec->n_key - 1][3] > 0.0))          // (the placement wraps s into [0, L): L must be a positive length)
+    return refuse(h, "raceline: ", "bad sampler description");
+  { const int rc = raceline_check(h, W); if (rc) return rc; }
+  dgsqp_sampler_t track;
+  memset(&track, 0, sizeof track);
+  track.n_key = spec->n_key;
+  memcpy(track.key_pts, spec->key_pts, sizeof track.key_pts);
+  return raceline_rounds(h, B, W, [&](int64_t nround, unsigned long long c0, double* dq0, int32_t* dcol) {
+    hipLaunchKernelGGL(dg_raceline_place_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, track, h->rl.dev, dq0, dcol);
+  }, x0_out, u_ws_out, candidates, stage);
+}
+
+int dgsqp_sample_raceline_spline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_spline_sampler_t* spec, const dgsqp_raceline_ws_t* W,
+                                       double* x0_out, double* u_ws_out, int64_t* candidates, int stage) {
+  if (!h) return DGSQP_E_ARG;
+  if (B < 0 || !spec) return refuse(h, "raceline: ", "bad argument (B < 0 or no sampler description)");
+  if (h->hp.P.track_kind != DGSQP_TRACK_SPLINE) return refuse(h, "raceline: ", "the spline-track sampler on an arc-track handle (dgsqp_sample_raceline_batch places cars on arc tracks)");
+  const double v[6] = {spec->s_lo, spec->s_hi, spec->gap_lo, spec->gap_hi, spec->ey_clip, spec->collision_d};
+  if (first_non_finite(v, 6) >= 0 || spec->s_hi < spec->s_lo || spec->gap_hi < spec->gap_lo || spec->ey_clip < 0.0 || spec->collision_d < 0.0)
+    return refuse(h, "raceline: ", "bad sampler description");
+  { const int rc = raceline_check(h, W); if (rc) return rc; }
+  return raceline_rounds(h, B, W, [&](int64_t nround, unsigned long long c0, double* dq0, int32_t* dcol) {
+    hipLaunchKernelGGL(dg_raceline_place_spline_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, h->rl.dev, dq0, dcol);
+  }, x0_out, u_ws_out, candidates, stage);
+}
+
+// ---- track-frame transforms (dgsqp_track_frame.h) ----
+// The ends of the handle's spline meet (tracks.CubicSplineTrack.circuit): the projection wraps s; otherwise it clips to [0, L].
+static bool spline_is_circuit(const DgProb& D) {
+  const int nk = D.P.n_knots, i = nk - 2;
+  const double* cx = D.spl + nk + 4 * i;
+  const double* cy = D.spl + nk + 4 * (nk - 1) + 4 * i;
+  const double t = D.spl[nk - 1] - D.spl[i];
+  const double xe = ((cx[3] * t + cx[2]) * t + cx[1]) * t + cx[0], ye = ((cy[3] * t + cy[2]) * t + cy[1]) * t + cy[0];
+  const double x0 = D.spl[nk], y0 = D.spl[nk + 4 * (nk - 1)];
+  return fabs(x0 - xe) <= 1e-6 + 1e-5 * fabs(xe) && fabs(y0 - ye) <= 1e-6 + 1e-5 * fabs(ye);
+}
+static int track_frame_check(dgsqp_solver* h, int64_t n, const dgsqp_track_frame_t* t, const void* in, const void* out) {
+  if (n < 0) return refuse(h, "track frame: ", "n < 0");
+  if (!t || !in || !out) return refuse(h, "track frame: ", "a NULL pointer (track description, input or output)");
+  const bool spline = h->hp.P.track_kind == DGSQP_TRACK_SPLINE;
+  if (t->n_key == 0 && !spline) return refuse(h, "track frame: ", "n_key = 0 means the handle's spline, and this handle's track is made of arcs: give its key points");
+  if (t->n_key != 0 && spline) return refuse(h, "track frame: ", "key points on a spline-track handle (n_key must be 0: the handle's spline)");
+  if (!std::isfinite(t->half_width) || !std::isfinite(t->slack)) return refuse(h, "track frame: ", "half_width / slack is not finite");
+  if (t->n_key != 0) {
+    if (t->n_key < 2 || t->n_key > DGSQP_MAX_SEGS + 1) return refuse(h, "track frame: ", "n_key = " + std::to_string(t->n_key) + " (2 .. DGSQP_MAX_SEGS + 1 key points)");
+    const int64_t bad = first_non_finite(&t->key_pts[0][0], (int64_t)t->n_key * 6);
+    if (bad >= 0) return refuse(h, "track frame: ", "key point [" + std::to_string(bad / 6) + "][" + std::to_string(bad % 6) + "] is not finite");
+    if (!(t->key_pts[t->n_key - 1][3] > 0.0)) return refuse(h, "track frame: ", "the track length (last key point's cumulative length) is not positive");
+  }
+  return DGSQP_OK;
+}
+static dim3 track_frame_grid(dgsqp_solver* h, int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8 * (int64_t)h->num_cu)); }
+
+int dgsqp_local_to_global_batch(dgsqp_handle_t h, int64_t n, const dgsqp_track_frame_t* t, const double* cl, double* xy) {
+  if (!h) return DGSQP_E_ARG;
+  { const int rc = track_frame_check(h, n, t, cl, xy); if (rc) return rc; }
+  if (n == 0) return DGSQP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  TmpBuf tb;
+  double* dcl = tb.alloc<double>((size_t)n * 3); double* dxy = tb.alloc<double>((size_t)n * 3);
+  if (!dcl || !dxy) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  HIPCHK(h, hipMemcpy(dcl, cl, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  dgsqp_sampler_t track;
+  memset(&track, 0, sizeof track);
+  track.n_key = t->n_key;
+  memcpy(track.key_pts, t->key_pts, sizeof track.key_pts);
+  const int rc = run_sync(h, [&]() -> int {
+    if (t->n_key == 0) hipLaunchKernelGGL(dg_spline_l2g_kernel, track_frame_grid(h, n), dim3(256), 0, h->stream, n, (const double*)dcl, dxy);
+    else hipLaunchKernelGGL(dg_arc_l2g_kernel, track_frame_grid(h, n), dim3(256), 0, h->stream, n, track, (const double*)dcl, dxy);
+    HIPCHK(h, hipGetLastError());
+    return DGSQP_OK;
+  });
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpy(xy, dxy, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  return DGSQP_OK;
+}
+
+int dgsqp_global_to_local_batch(dgsqp_handle_t h, int64_t n, const dgsqp_track_frame_t* t, const double* xy, double* cl, double* resid,
+                                int32_t* status) {
+  if (!h) return DGSQP_E_ARG;
+  { const int rc = track_frame_check(h, n, t, xy, cl); if (rc) return rc; }
+  if (!status) return refuse(h, "track frame: ", "a NULL pointer (status)");
+  if (n == 0) return DGSQP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  { const int rc = wait_idle(h); if (rc) return rc; }
+  TmpBuf tb;
+  double* dxy = tb.alloc<double>((size_t)n * 3); double* dcl = tb.alloc<double>((size_t)n * 3);
+  double* dres = resid ? tb.alloc<double>((size_t)n) : nullptr;
+  int32_t* dst = tb.alloc<int32_t>((size_t)n);
+  if (!dxy || !dcl || (resid && !dres) || !dst) { h->err = "hipMalloc failed"; return DGSQP_E_NOMEM; }
+  HIPCHK(h, hipMemcpy(dxy, xy, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  const int circuit = t->n_key == 0 && spline_is_circuit(h->hp) ? 1 : 0;
+  const int rc = run_sync(h, [&]() -> int {
+    if (t->n_key == 0) hipLaunchKernelGGL(dg_spline_project_kernel, track_frame_grid(h, n), dim3(256), 0, h->stream, n, circuit, t->half_width + t->slack, (const double*)dxy, dcl, dres, dst);
+    else hipLaunchKernelGGL(dg_arc_project_kernel, track_frame_grid(h, n), dim3(256), 0, h->stream, n, *t, (const double*)dxy, dcl, dres, dst);
+    HIPCHK(h, hipGetLastError());
+    return DGSQP_OK;
+  });
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpy(cl, dcl, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  if (resid) HIPCHK(h, hipMemcpy(resid, dres, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(status, dst, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
   return DGSQP_OK;
 }
 

@@ -62,6 +62,50 @@ class Raceline:
         T2 = T + T[-1]
         return cls(np.append(T, T2[1:]), np.vstack((mat, mat2[1:])), lap_mat=mat)
 
+    @classmethod
+    def from_tum(cls, file_path, track_name, tenth_scale=False, time_scale=1.0, solver=None):
+        """track_lib.py:145-213 (``segment=None``): rows ``s; x; y; psi; kappa; vx; ax`` of a TUM raceline file.  x, y are scaled by 0.1 when
+        ``tenth_scale``, v = vx scale / time_scale, psi += pi / 2; (x, y, psi) is projected onto the centre line (``tracks.global_to_local_batch``,
+        or ``solver.global_to_local_batch`` on the device); a row whose s falls below the previous row's gets + track_length; T is the
+        cumulative sum of the file's arclength steps (scaled) over v; the second lap is appended as in ``from_file``.  ``projection_resid``
+        keeps the projections' residuals."""
+        from .tracks import global_to_local_batch
+        track = get_track(track_name)
+        scale = 0.1 if tenth_scale else 1.0
+        rows = []
+        import gzip
+        with (gzip.open if str(file_path).endswith('.gz') else open)(file_path, 'rt') as f:          # (a gzip of the file reads the same)
+            for line in f:
+                d = line.strip().split(';')
+                if not line.strip() or '#' in d[0]:
+                    continue
+                rows.append([float(v) for v in d])
+        rows = np.array(rows)
+        if rows.ndim != 2 or rows.shape[1] != 7 or rows.shape[0] < 2:
+            raise ValueError('TUM raceline: rows of s; x; y; psi; kappa; vx; ax')
+        xy = np.stack([rows[:, 1] * scale, rows[:, 2] * scale, rows[:, 3] + np.pi / 2], axis=1)
+        v = rows[:, 5] * scale / time_scale
+        if solver is None:
+            cl, resid, status = global_to_local_batch(track, xy)
+        else:
+            cl, resid, status = solver.global_to_local_batch(xy, track=track)
+        if (status == 1).any():
+            raise ValueError('TUM raceline: a row that is not finite')
+        s = cl[:, 0].copy()
+        L = track.track_length
+        for k in range(1, len(s)):
+            if s[k] < s[k - 1]:
+                s[k] += L
+        mat = np.stack([xy[:, 0], xy[:, 1], xy[:, 2], v, np.zeros(len(s)), np.zeros(len(s)), cl[:, 2], s, cl[:, 1]], axis=1)
+        s_file = rows[:, 0] * scale
+        T = np.concatenate([[0.0], np.cumsum((s_file[1:] - s_file[:-1]) / v[:-1])])
+        mat2 = mat.copy()
+        mat2[:, 7] += L
+        T2 = T + T[-1]
+        rl = cls(np.append(T, T2[1:]), np.vstack((mat, mat2[1:])), lap_mat=mat)
+        rl.lap_T, rl.projection_resid, rl.projection_status = T, resid, status
+        return rl
+
     @staticmethod
     def _lerp(X, Y, x):
         x = np.asarray(x, np.float64)
@@ -100,6 +144,8 @@ class Raceline:
 
 
 STUDY_COLLISION_D = 2 * np.sqrt((0.37 / 2) ** 2 + (0.195 / 2) ** 2)      # monte_carlo_sampler_dynamic.py:21-22 with globals.py's VL, VW
+F1_STUDY_VL, F1_STUDY_VW = 0.56, 0.2                                     # comparison_study_f1/globals.py
+F1_STUDY_COLLISION_D = 2 * np.sqrt((F1_STUDY_VL / 2) ** 2 + (F1_STUDY_VW / 2) ** 2)      # monte_carlo_sampler.py:18-21
 
 
 @dataclass
@@ -119,6 +165,7 @@ class Game:
     second_car_ahead: bool = False      # the sampler also rejects placements with car 2 behind car 1 (ablation.py:387)
     raceline: object = None             # sampler 'raceline': the ``Raceline`` the cars are drawn around and warm-started along
     collision_d: float = 0.0            # sampler 'raceline': r1 + r2 of the placement's collision check
+    s_range: object = None              # sampler 'raceline' on a spline track: (s_lo, s_hi) of car 1's placement instead of (0, L - 10)
 
     def solver_args(self):
         return (self.joint_model, self.costs, self.agent_constraints, self.shared_constraints, self.bounds, self.params)
@@ -316,11 +363,30 @@ def point_mass_racing_game(track_kind='barc', N=20, M=2, theta_deg=45) -> Game:
                 params, track, H - 0.1, 2 * r, name=f'pm_{track_kind}_M{M}_N{N}', sampler='circuit' if track_kind == 'barc' else 'first_segment')
 
 
-def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10) -> Game:
+def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10, sampler='circuit', raceline=None, time_scale=1.0,
+                   s_range=None) -> Game:
     """BASELINE.json config 4: head-to-head race on the F1 track (``f1_austin_tenth_scale``, a ``CasadiBSplineTrack`` in the
     reference: track_lib.get_track :112-113, scripts/comparison_study_f1), long horizon N = 50.  Costs, rate limits, radii and
     solver parameters are those of the circuit race DGSQP_comp_monte_carlo.py (as ``barc_racing_game``); lateral bounds
-    +-(half width - 0.1); ``model='dynamic'`` puts the Pacejka bicycle of the comparison studies on it (rk4)."""
+    +-(half width - 0.1); ``model='dynamic'`` puts the Pacejka bicycle of the comparison studies on it (rk4).
+    ``sampler='raceline'``: the F1 study's own front end (comparison_study_f1/monte_carlo_sampler.py, warm_start.py) around
+    ``raceline`` -- a ``Raceline``, or the path of the study's TUM file ``traj_race_cl.csv`` (loaded tenth-scale with ``time_scale``);
+    ``s_range=(s_lo, s_hi)`` limits car 1's arclength (the study's [60, 80] m window, without building a sub-track)."""
+    if sampler not in ('circuit', 'raceline'):
+        raise ValueError(f"sampler {sampler!r} does not fit the F1 track ('circuit' or 'raceline')")
+    if sampler == 'raceline':
+        if M != 2:
+            raise ValueError("sampler='raceline' places two cars")
+        if raceline is None:
+            raise ValueError("sampler='raceline' needs raceline= (a Raceline, or the path of traj_race_cl.csv)")
+        if not isinstance(raceline, Raceline):
+            raceline = Raceline.from_tum(raceline, 'f1_austin_tenth_scale', tenth_scale=True, time_scale=time_scale)
+        if s_range is not None:
+            s_range = (float(s_range[0]), float(s_range[1]))
+            if not s_range[0] <= s_range[1]:
+                raise ValueError('s_range: (s_lo, s_hi) with s_lo <= s_hi')
+    else:
+        raceline, s_range = None, None
     dt = 0.1
     track = get_track('f1_austin_tenth_scale')
     H = track.half_width
@@ -344,7 +410,8 @@ def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10) -> G
     cost = lambda: RacingCost(input_weight=(0.1, 0.1), input_rate_weight=(1.0, 1.0), comp_weights=(0.0, 1.0), comp_type='atan')
     return Game(joint, [cost() for _ in range(M)], [InputRateLimits((10.0, 4.5), (-10.0, -4.5)) for _ in range(M)],
                 CollisionAvoidance([r] * M), _bounds(H - 0.1, M), params, track, H - 0.1, 2 * r,
-                name=f'{"kb" if model == "kinematic" else "dyn"}_f1_M{M}_N{N}', sampler='circuit')
+                name=f'{"kb" if model == "kinematic" else "dyn"}_f1_M{M}_N{N}', sampler=sampler, raceline=raceline,
+                collision_d=F1_STUDY_COLLISION_D if sampler == 'raceline' else 0.0, s_range=s_range)
 
 
 _MERGE_GOAL_X = (4.0, 4.5, 4.25, 4.75, 5.25, 5.0)          # merge.py:85-87 for the first three cars
@@ -626,12 +693,28 @@ def _sample_scenarios_circuit(game: Game, B: int, seed: int, max_rounds: int):
 def study_tracker(game: Game) -> dict:
     """The LTV-MPC tracker of warm_start_dynamic.py:60-127 for a car of ``game``: ``cost`` (Q = diag(1, 0, 0, 1, 1, 1) on (v_long, v_tran,
     psidot, e_psi, s, e_y), input weights 1e-2, rate weights 0.1; x, y carry zero weight), ``bounds`` (:68-81), ``params`` (:115-122:
-    state_scaling, input_scaling = [2, 0.45], damping 0.75, qp_iters 5) and ``u_init`` / ``du_init`` = 0.01 (:156-157)."""
+    state_scaling, input_scaling = [2, 0.45], damping 0.75, qp_iters 5) and ``u_init`` / ``du_init`` = 0.01 (:156-157).  For a game on a
+    spline track it is the tracker of comparison_study_f1/warm_start.py instead: state_scaling [100, 100, 7, pi / 2, L, 1], rates +-20 /
+    +-4.5, and the ``e_y`` box at +- the game's lateral bound, which stands in for the study's width functions."""
     from .ltv_mpc import TrackingCost
     from .solver_types import CALTVMPCParams
     mdl = game.joint_model.dynamics_models[0]
     L, H = game.track.track_length, game.track.half_width
     w = [0, 0, 1, 0, 0, 1, 1, 1] if mdl.n_q == 8 else [0, 0, 1, 1, 1, 1]
+    if game.track.kind == 'spline':
+        # comparison_study_f1/warm_start.py:66-80, :123-128 (its e_y box is open and the width functions bound e_y: here the game's constant
+        # lateral bound)
+        Hg = game.half_width
+        ub = VehicleState(x=Position(x=1e9, y=1e9), e=OrientationEuler(psi=1e9), p=ParametricPose(s=2 * L, x_tran=Hg, e_psi=1e9),
+                          v=BodyLinearVelocity(v_long=5, v_tran=2), w=BodyAngularVelocity(w_psi=10), u=VehicleActuation(u_a=2.0, u_steer=0.436))
+        lb = VehicleState(x=Position(x=-1e9, y=-1e9), e=OrientationEuler(psi=-1e9), p=ParametricPose(s=-2 * L, x_tran=-Hg, e_psi=-1e9),
+                          v=BodyLinearVelocity(v_long=0.1, v_tran=-2), w=BodyAngularVelocity(w_psi=-10), u=VehicleActuation(u_a=-2.0, u_steer=-0.436))
+        bounds = dict(qu_ub=ub, qu_lb=lb, du_ub=VehicleState(u=VehicleActuation(u_a=20.0, u_steer=4.5)),
+                      du_lb=VehicleState(u=VehicleActuation(u_a=-20.0, u_steer=-4.5)))
+        params = CALTVMPCParams(N=game.params.N, state_scaling=[100, 100, 7, np.pi / 2, L, 1.0], input_scaling=[2, 0.45], damping=0.75,
+                                qp_iters=5, delay=None, verbose=False, qp_interface='casadi')
+        return dict(cost=TrackingCost(state_weight=w, input_weight=(1e-2, 1e-2), rate_weight=(0.1, 0.1)), bounds=bounds, params=params,
+                    u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5)
     ub = VehicleState(x=Position(x=1e9, y=1e9), e=OrientationEuler(psi=1e9), p=ParametricPose(s=2 * L, x_tran=H, e_psi=1e9),
                       v=BodyLinearVelocity(v_long=5, v_tran=2), w=BodyAngularVelocity(w_psi=10), u=VehicleActuation(u_a=2.0, u_steer=0.436))
     lb = VehicleState(x=Position(x=-1e9, y=-1e9), e=OrientationEuler(psi=-1e9), p=ParametricPose(s=-2 * L, x_tran=-H, e_psi=-1e9),
@@ -673,8 +756,15 @@ def place_raceline_sequential(game: Game, rng):
     models = game.joint_model.dynamics_models
     q, xy = [], []
     s1 = None
+    spline = getattr(track, 'kind', 'arcs') == 'spline'
+    if spline:          # comparison_study_f1/monte_carlo_sampler.py:25-55: car 2 ahead of car 1, s1 in [0, L - 10] (or game.s_range)
+        s_lo, s_hi = (0.0, L - 10.0) if game.s_range is None else game.s_range
+        lim = 0.9 * game.half_width
     for a, mdl in enumerate(models[:2]):
-        s = L * rng.random() if a == 0 else s1 + 1.2 * game.obs_d * (2 * rng.random() - 1)
+        if spline:
+            s = s_lo + (s_hi - s_lo) * rng.random() if a == 0 else s1 + 3 * rng.random() * F1_STUDY_VL
+        else:
+            s = L * rng.random() if a == 0 else s1 + 1.2 * game.obs_d * (2 * rng.random() - 1)
         s1 = s if a == 0 else s1
         r = rl.eval(rl.s2t(s))
         ey = max(min(r[8] + (2 * rng.random() - 1), lim), -lim)

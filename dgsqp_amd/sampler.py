@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from .tracks import local_to_global_batch
 
 FIRST_SEGMENT, INDEPENDENT, CIRCUIT, MERGE = 0, 1, 2, 3
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -66,7 +67,11 @@ def sampler_spec(game, seed: int) -> SamplerT:
     S.half_width, S.obs_d = float(game.half_width), float(game.obs_d)
     for a in range(_ffi.MAX_AGENTS):
         S.x_nom[a] = _MERGE_X_NOM[a]
-    if S.kind != MERGE:
+    if S.kind != MERGE and getattr(game.track, 'kind', 'arcs') == 'spline':
+        if S.kind != CIRCUIT:
+            raise ValueError("on a spline track the device sampler places cars with the 'circuit' rule only (the others need the first segment of an arc track)")
+        S.n_key = 0                  # the handle's spline (dg_sample_place_spline_kernel)
+    elif S.kind != MERGE:
         kp = np.asarray(game.track.key_pts, dtype=float)
         if not hasattr(game.track, 'key_pts') or kp.shape[0] > _ffi.MAX_SEGS + 1:
             raise ValueError('the device sampler places cars on arc tracks (key points); spline tracks are sampled on the host')
@@ -112,7 +117,7 @@ def place(game, seed: int, cand):
     track, hw, obs_d = game.track, game.half_width, game.obs_d
 
     def put(mdl, s, ey, v, epsi):
-        xy = np.array([track.local_to_global((si, ei, 0.0))[:2] for si, ei in zip(s, ey)]).reshape(-1, 2)
+        xy = local_to_global_batch(track, np.stack([s, ey, np.zeros(n)], axis=1))
         q = np.zeros((n, mdl.n_q))
         q[:, 0], q[:, 1], q[:, 2] = xy[:, 0], xy[:, 1], v
         q[:, mdl.epsi_idx] = epsi
@@ -195,10 +200,51 @@ def raceline_sampler_spec(game, seed: int) -> _ffi.RacelineSamplerT:
     return S
 
 
+def raceline_spline_sampler_spec(game, seed: int) -> _ffi.RacelineSplineSamplerT:
+    """The C-ABI description of the F1 study's placement (include/dgsqp.h: dgsqp_raceline_spline_sampler_t).  Defaults as the study
+    (comparison_study_f1/monte_carlo_sampler.py): s1 in [0, L - 10] -- ``game.s_range`` overrides --, gap in [0, 3 * 0.56], collision
+    distance ``game.collision_d``.  The study clips e_y with 0.9 x the track's width functions; this game has one constant lateral bound,
+    and e_y is clipped to 0.9 x that (stated deviation)."""
+    from .montecarlo import F1_STUDY_VL
+    if getattr(game.track, 'kind', 'arcs') != 'spline':
+        raise ValueError('the spline-track raceline sampler needs a game on a spline track (raceline_sampler_spec places cars on arc tracks)')
+    S = _ffi.RacelineSplineSamplerT()
+    S.seed = int(seed)
+    S.s_lo, S.s_hi = (0.0, float(game.track.track_length) - 10.0) if game.s_range is None else (float(game.s_range[0]), float(game.s_range[1]))
+    S.gap_lo, S.gap_hi = 0.0, 3 * F1_STUDY_VL
+    S.ey_clip, S.collision_d = 0.9 * float(game.half_width), float(game.collision_d)
+    return S
+
+
+def _place_raceline_spline(game, seed: int, cand):
+    """comparison_study_f1/monte_carlo_sampler.py:25-55 with the counter-based uniforms: the arithmetic of dg_raceline_place_spline_kernel."""
+    U = lambda k: uniform(seed, cand, k)
+    S = raceline_spline_sampler_spec(game, seed)
+    rl, track = game.raceline, game.track
+    models = game.joint_model.dynamics_models
+    s1 = S.s_lo + (S.s_hi - S.s_lo) * U(0)
+    q0, xy = [], []
+    for a, mdl in enumerate(models[:2]):
+        s = s1 if a == 0 else s1 + S.gap_lo + (S.gap_hi - S.gap_lo) * U(3)
+        r = rl.eval(rl.s2t(s))
+        ey = np.maximum(np.minimum(r[:, 8] + (2 * U(3 * a + 1) - 1), S.ey_clip), -S.ey_clip)
+        v = r[:, 3] + (1.5 * U(3 * a + 2) - 0.75)
+        p = local_to_global_batch(track, np.stack([s, ey, np.zeros(len(cand))], axis=1))[:, :2]
+        q = np.zeros((len(cand), mdl.n_q))
+        q[:, 0], q[:, 1], q[:, 2] = p[:, 0], p[:, 1], v
+        q[:, mdl.epsi_idx], q[:, mdl.s_idx], q[:, mdl.ey_idx] = r[:, 6], s, ey
+        q0.append(q); xy.append(p)
+    d = xy[0] - xy[1]
+    return np.concatenate(q0, axis=1), S.collision_d ** 2 - (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+
+
 def place_raceline(game, seed: int, cand):
     """monte_carlo_sampler_dynamic.py:27-57 for the candidates ``cand`` with the counter-based uniforms, six per candidate in the script's
-    order (s1, e_y1, v1, s2, e_y2, v2) -> (x0 [n, n_q], margin [n]); a candidate is in collision when margin >= 0."""
+    order (s1, e_y1, v1, s2, e_y2, v2) -> (x0 [n, n_q], margin [n]); a candidate is in collision when margin >= 0.  A game on a spline
+    track is placed by the F1 study's law instead (``raceline_spline_sampler_spec``)."""
     cand = np.asarray(cand, dtype=np.uint64)
+    if getattr(game.track, 'kind', 'arcs') == 'spline':
+        return _place_raceline_spline(game, seed, cand)
     U = lambda k: uniform(seed, cand, k)
     rl, track = game.raceline, game.track
     L, lim = track.track_length, 0.9 * track.half_width

@@ -961,19 +961,51 @@ class DGSQP(AbstractSolver):
         if game.raceline is None:
             raise ValueError("the game carries no raceline (dynamic_racing_game(..., sampler='raceline', raceline=...))")
         self.set_raceline(game.raceline)
-        spec = smp.raceline_sampler_spec(game, seed)
+        spline = getattr(game.track, 'kind', 'arcs') == 'spline'       # the F1 study's placement (dgsqp_sample_raceline_spline_batch)
+        spec = smp.raceline_spline_sampler_spec(game, seed) if spline else smp.raceline_sampler_spec(game, seed)
+        entry = 'dgsqp_sample_raceline_spline_batch' if spline else 'dgsqp_sample_raceline_batch'
         W = raceline_ws(game) if ws is None else ws
         x0 = np.empty((B, self.n_q)) if fetch else None
         u_am = np.empty((B, self.n)) if fetch else None
         used = C.c_int64(0)
-        self._raceline_check(self._lib.dgsqp_sample_raceline_batch(self._h, int(B), C.byref(spec), C.byref(W), _ffi.dptr(x0), _ffi.dptr(u_am),
-                                                                   C.byref(used), 1 if stage else 0), 'dgsqp_sample_raceline_batch')
+        self._raceline_check(getattr(self._lib, entry)(self._h, int(B), C.byref(spec), C.byref(W), _ffi.dptr(x0), _ffi.dptr(u_am),
+                                                       C.byref(used), 1 if stage else 0), entry)
         out = dict(candidates=int(used.value))
         if fetch:
             nua = self.n_u // self.M
             out['x0'] = x0
             out['u_ws'] = np.ascontiguousarray(u_am.reshape(B, self.M, self.N, nua).transpose(0, 2, 1, 3).reshape(B, self.N, self.n_u))
         return out
+
+    # ---- track-frame transforms for batches of points (csrc/dgsqp_track_frame.h) ---------------------
+    def _track_frame(self, track):
+        from .tracks import track_frame_spec
+        return track_frame_spec(self.joint_dynamics.dynamics_models[0].track if track is None else track)
+
+    def local_to_global_batch(self, cl, track=None):
+        """Frenet ``cl`` [n, 3] = (s, e_y, e_psi) -> [n, 3] = (x, y, psi) on the device (``dgsqp_local_to_global_batch``, mirrored by
+        ``tracks.local_to_global_batch``).  ``track``: the game's by default; an arc track's key points travel in the call."""
+        cl = np.ascontiguousarray(cl, np.float64)
+        if cl.ndim != 2 or cl.shape[1] != 3:
+            raise ValueError('cl must be [n, 3]')
+        T = self._track_frame(track)
+        xy = np.empty_like(cl)
+        self._raceline_check(self._lib.dgsqp_local_to_global_batch(self._h, cl.shape[0], C.byref(T), _ffi.dptr(cl), _ffi.dptr(xy)),
+                             'dgsqp_local_to_global_batch')
+        return xy
+
+    def global_to_local_batch(self, xy, track=None):
+        """Global poses ``xy`` [n, 3] = (x, y, psi) -> (cl [n, 3] = (s, e_y, e_psi), resid [n], status [n]) on the device
+        (``dgsqp_global_to_local_batch``, mirrored by ``tracks.global_to_local_batch``: status 0 fine, 1 not finite, 2 off the track)."""
+        xy = np.ascontiguousarray(xy, np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 3:
+            raise ValueError('xy must be [n, 3]')
+        T = self._track_frame(track)
+        n = xy.shape[0]
+        cl, resid, status = np.empty_like(xy), np.empty(n), np.empty(n, np.int32)
+        self._raceline_check(self._lib.dgsqp_global_to_local_batch(self._h, n, C.byref(T), _ffi.dptr(xy), _ffi.dptr(cl), _ffi.dptr(resid),
+                                                                   _ffi.iptr(status)), 'dgsqp_global_to_local_batch')
+        return cl, resid, status
 
     # ---- reference single-scenario surface -----------------------------------------------------
     def solve(self, states: List[VehicleState], parameters: np.ndarray = np.array([])) -> dict:

@@ -8,11 +8,12 @@ reference track classes:
 * the two lookup tables behind ``get_curvature_casadi_fn`` /
   ``get_tangent_angle_casadi_fn`` (:199-225) -- exported as plain arrays that
   the HIP kernels evaluate with CasADi's ``pw_const`` / ``pw_lin`` semantics,
-* ``local_to_global`` (:752-807) used by the initial-condition samplers,
+* ``local_to_global`` (:752-807) used by the initial-condition samplers, and ``global_to_local`` (:644-743; on a spline the
+  foot point the reference's NLP finds) -- both also for batches, as the numpy mirrors of csrc/dgsqp_track_frame.h,
 * the three parametrised shapes of DGSQP/tracks/track_lib.py:14-87 and the
   ``L_track_barc`` circuit.
 
-Plotting, ``global_to_local`` and the NLP projection are not on the path.
+Plotting is not on the path.
 """
 from __future__ import annotations
 
@@ -171,6 +172,15 @@ class RadiusArclengthTrack:
         x, y, psi = self.local_to_global((state.p.s, state.p.x_tran, state.p.e_psi))
         state.x.x, state.x.y, state.e.psi = x, y, psi
 
+    # ---- global -> Frenet (radius_arclength_track.py:644-743) --------------------------------
+    def global_to_local(self, xy_coord):
+        """One point ``(x, y, psi)`` -> ``(s, e_y, e_psi)``, or ``None`` when no segment takes it, as the reference; an array [n, 3] ->
+        [n, 3] with NaN rows for such points (``global_to_local_batch`` also gives their status)."""
+        return _global_to_local(self, xy_coord)
+
+    def global_to_local_typed(self, state):
+        return _global_to_local_typed(self, state)
+
 
 class StraightTrack(RadiusArclengthTrack):
     def __init__(self, length, width, slack, phase_out=False):
@@ -292,6 +302,24 @@ class CubicSplineTrack:
         x, y, psi = self.local_to_global((state.p.s, state.p.x_tran, state.p.e_psi))
         state.x.x, state.x.y, state.e.psi = x, y, psi
 
+    def global_to_local(self, xy_coord):
+        """One point ``(x, y, psi)`` -> ``(s, e_y, e_psi)``; an array [n, 3] -> [n, 3].  The foot point of ``global_to_local_batch``: the
+        reference (casadi_bspline_track.py:106-112, :172-186) reaches it with an NLP started at the closest waypoint."""
+        return _global_to_local(self, xy_coord)
+
+    def global_to_local_typed(self, state):
+        return _global_to_local_typed(self, state)
+
+    def _frame(self, sb):
+        """c, c', c'' at sbar in [0, L] -- the arithmetic of tf_eval (csrc/dgsqp_track_frame.h), on the table ``spline_table`` hands over."""
+        kn = self.knots - self.knots[0]
+        i = np.clip(np.searchsorted(kn, sb, side='right') - 1, 0, len(kn) - 2)
+        t = sb - kn[i]
+        cx, cy = self.cx[i], self.cy[i]
+        return (((cx[:, 3] * t + cx[:, 2]) * t + cx[:, 1]) * t + cx[:, 0], ((cy[:, 3] * t + cy[:, 2]) * t + cy[:, 1]) * t + cy[:, 0],
+                (3 * cx[:, 3] * t + 2 * cx[:, 2]) * t + cx[:, 1], (3 * cy[:, 3] * t + 2 * cy[:, 2]) * t + cy[:, 1],
+                6 * cx[:, 3] * t + 2 * cx[:, 2], 6 * cy[:, 3] * t + 2 * cy[:, 2])
+
     def spline_table(self):
         """[knots (n), x coefficients (n-1) x 4, y coefficients (n-1) x 4] as the C-ABI takes it (dgsqp_problem_t.spline)."""
         return np.ascontiguousarray(np.concatenate([self.knots - self.knots[0], self.cx.ravel(), self.cy.ravel()]))
@@ -320,6 +348,215 @@ def load_mpclab_raceline(file_path, track_name, time_scale=1.0):
     continued linearly outside the table."""
     from .montecarlo import Raceline
     rl = Raceline.from_file(file_path, track_name, time_scale)
+
+    def raceline(t):
+        v = rl.eval(t)
+        return [v[..., c] for c in range(v.shape[-1])]
+
+    def s2t(s):
+        return rl.s2t(s)
+    raceline.table = s2t.table = rl
+    return raceline, s2t, rl.lap_mat
+
+
+# ---- batched track-frame transforms: the numpy mirror of csrc/dgsqp_track_frame.h ----
+def _wrap_pi(a):
+    """Into (-pi, pi] (tf_wrap_pi)."""
+    return a - 2 * np.pi * np.ceil((a - np.pi) / (2 * np.pi))
+
+
+def _wrap_once(a):
+    """``_wrap`` for arrays."""
+    return np.where(a < -np.pi, 2 * np.pi + a, np.where(a > np.pi, a - 2 * np.pi, a))
+
+
+def _points(a, what):
+    a = np.asarray(a, dtype=float)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f'{what} must be [n, 3]')
+    return a
+
+
+def track_frame_spec(track):
+    """The C-ABI description of ``track`` for the batched transforms (include/dgsqp.h: dgsqp_track_frame_t); n_key = 0: the handle's spline."""
+    from . import _ffi
+    T = _ffi.TrackFrameT()
+    T.half_width, T.slack = float(track.track_width) / 2, float(track.slack)
+    if track.kind == 'spline':
+        return T
+    kp = np.asarray(track.key_pts, dtype=float)
+    if kp.shape[0] > _ffi.MAX_SEGS + 1:
+        raise ValueError('track frame: arc tracks of at most %d segments' % _ffi.MAX_SEGS)
+    T.n_key = kp.shape[0]
+    for i in range(kp.shape[0]):
+        for j in range(6):
+            T.key_pts[i][j] = float(kp[i, j])
+    return T
+
+
+def local_to_global_batch(track, cl):
+    """Frenet ``cl`` [n, 3] = (s, e_y, e_psi) -> [n, 3] = (x, y, psi): ``track.local_to_global`` for every row, vectorised -- the arithmetic of
+    dev_spline_local_to_global / dev_arc_local_to_global.  A row whose s is not finite gives NaN."""
+    cl = _points(cl, 'cl')
+    out = np.full(cl.shape, np.nan)
+    m = np.isfinite(cl[:, 0])
+    s, ey, epsi = cl[m, 0], cl[m, 1], cl[m, 2]
+    L = track.track_length
+    sb = np.fmod(np.fmod(s, L) + L, L)
+    if track.kind == 'spline':
+        x, y, dx, dy, _, _ = track._frame(sb)
+        nrm = np.sqrt(dx * dx + dy * dy)          # (as the device: x, y carry its bits; the scalar method's hypot may differ in the last place)
+        out[m] = np.stack([x - ey * dy / nrm, y + ey * dx / nrm, np.arctan2(dy, dx) + epsi], axis=1)
+        return out
+    kp = track.key_pts
+    i0 = np.clip(np.searchsorted(kp[:, 3], sb, side='right') - 1, 0, kp.shape[0] - 2)
+    i1 = i0 + 1
+    xs, ys, psis = kp[i0, 0], kp[i0, 1], kp[i0, 2]
+    xf, yf, psif, curv, seg = kp[i1, 0], kp[i1, 1], kp[i1, 2], kp[i1, 5], kp[i1, 4]
+    d = sb - kp[i0, 3]
+    hp = np.pi / 2
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = 1 / curv
+        sgn = np.where(r >= 0, 1.0, -1.0)
+        ar = np.abs(r)
+        xc, yc = xs + ar * np.cos(psis + sgn * hp), ys + ar * np.sin(psis + sgn * hp)
+        span = d / ar
+        an = _wrap_once(psis + sgn * hp)
+        ang = -np.where(an >= 0, 1.0, -1.0) * (np.pi - np.abs(an))
+        xa, ya = xc + (ar - sgn * ey) * np.cos(ang + sgn * span), yc + (ar - sgn * ey) * np.sin(ang + sgn * span)
+        psia = _wrap_once(_wrap_once(psis + sgn * span) + epsi)
+    st = curv == 0
+    out[m] = np.stack([np.where(st, xs + (xf - xs) * d / seg + ey * np.cos(psif + hp), xa),
+                       np.where(st, ys + (yf - ys) * d / seg + ey * np.sin(psif + hp), ya),
+                       np.where(st, _wrap_once(psif + epsi), psia)], axis=1)
+    return out
+
+
+def _project_spline(track, px, py, psi):
+    """dev_spline_project for finite points: the piece whose start is closest, 30 Newton steps on g(s) = (c(s) - p) . c'(s) clipped to
+    [K_j - 1.5 D, K_j + 1.5 D], no early exit."""
+    kn = track.knots - track.knots[0]
+    L = track.track_length
+    x0, y0 = track.cx[:, 0], track.cy[:, 0]
+    j = np.empty(len(px), dtype=np.int64)
+    for a in range(0, len(px), 4096):                       # (the distance table of a chunk: 4096 x pieces)
+        ax, ay = x0[None, :] - px[a:a + 4096, None], y0[None, :] - py[a:a + 4096, None]
+        j[a:a + 4096] = np.argmin(ax * ax + ay * ay, axis=1)
+    delta = kn[1] - kn[0]
+    lo, hi = kn[j] - 1.5 * delta, kn[j] + 1.5 * delta
+    s = kn[j].copy()
+
+    def at(s):
+        sb = np.fmod(np.fmod(s, L) + L, L) if track.circuit else np.fmin(np.fmax(s, 0.0), L)
+        x, y, dx, dy, ddx, ddy = track._frame(sb)
+        ex, ey = x - px, y - py
+        return sb, x, y, dx, dy, ddx, ddy, ex, ey, ex * dx + ey * dy
+    for _ in range(30):
+        _, _, _, dx, dy, ddx, ddy, ex, ey, g = at(s)
+        h = (dx * dx + dy * dy) + (ex * ddx + ey * ddy)
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            step = np.where(h > 0.0, -(g / h), np.where(g > 0.0, -0.1, np.where(g < 0.0, 0.1, 0.0)))
+        s = np.fmax(np.fmin(s + step, hi), lo)
+    sb, x, y, dx, dy, _, _, _, _, g = at(s)
+    nrm = np.sqrt(dx * dx + dy * dy)
+    return sb, ((py - y) * dx - (px - x) * dy) / nrm, _wrap_pi(psi - np.arctan2(dy, dx)), g
+
+
+def _project_arcs(track, px, py, psi):
+    """dev_arc_project for finite points: the segments in order, the first whose span contains the foot point with |e_y| within half the track
+    width plus the slack.  Returns s, e_y, e_psi (NaN where no segment takes the point) and found [n]."""
+    kp = track.key_pts
+    lim = track.track_width / 2 + track.slack
+    hp = np.pi / 2
+    n = len(px)
+    s_out, ey_out, ep_out = (np.full(n, np.nan) for _ in range(3))
+    found = np.zeros(n, bool)
+    for i in range(1, kp.shape[0]):
+        xs, ys, psis = kp[i - 1, :3]
+        xf, yf, psif = kp[i, :3]
+        curv, seg = kp[i, 5], kp[i, 4]
+        at_s = (px == xs) & (py == ys)
+        at_f = ~at_s & (px == xf) & (py == yf)
+        if curv == 0:
+            wx, wy, vx, vy, ux, uy = xf - xs, yf - ys, px - xs, py - ys, px - xf, py - yf
+            dot = wx * vx + wy * vy
+            lw = np.sqrt(wx * wx + wy * wy)
+            ey = (wx * vy - wy * vx) / lw
+            ok = (dot >= 0.0) & (-(wx * ux + wy * uy) >= 0.0) & (np.abs(ey) <= lim)
+            s = kp[i - 1, 3] + dot / lw
+            ref = np.full(n, psis)
+        else:
+            r = 1 / curv
+            dr = 1.0 if r > 0 else -1.0
+            ar = abs(r)
+            xc, yc = xs + ar * np.cos(psis + dr * hp), ys + ar * np.sin(psis + dr * hp)
+            ax, ay, bx, by = xs - xc, ys - yc, px - xc, py - yc
+            cur = np.arctan2(ax * by - ay * bx, ax * bx + ay * by)
+            ey = -dr * (np.sqrt(bx * bx + by * by) - ar)
+            ok = (cur * dr > 0.0) & (abs(seg / r) >= np.abs(cur)) & (np.abs(ey) <= lim)
+            s = kp[i - 1, 3] + np.abs(cur) * ar
+            ref = psis + cur
+        s = np.where(at_s, kp[i - 1, 3], np.where(at_f, kp[i, 3], s))
+        ey = np.where(at_s | at_f, 0.0, ey)
+        ref = np.where(at_s, psis, np.where(at_f, psif, ref))
+        take = ~found & (at_s | at_f | ok)
+        s_out[take], ey_out[take], ep_out[take] = s[take], ey[take], _wrap_pi(psi - ref)[take]
+        found |= take
+    return s_out, ey_out, ep_out, found
+
+
+def global_to_local_batch(track, xy):
+    """Global poses ``xy`` [n, 3] = (x, y, psi) -> (cl [n, 3] = (s, e_y, e_psi), resid [n], status [n] int32): the numpy mirror of
+    ``dgsqp_global_to_local_batch``.  status 0: fine; 1: an input is not finite (NaN outputs); 2: off the track -- on a spline
+    |e_y| > half_width + slack with the values still returned, on arcs no segment takes the point (NaN outputs).  resid: the final
+    g = (c(s) - p) . c'(s) on a spline, 0 on arcs."""
+    xy = _points(xy, 'xy')
+    n = xy.shape[0]
+    cl, resid, status = np.full((n, 3), np.nan), np.full(n, np.nan), np.ones(n, np.int32)
+    m = np.isfinite(xy).all(axis=1)
+    if not m.any():
+        return cl, resid, status
+    px, py, psi = xy[m, 0], xy[m, 1], xy[m, 2]
+    if track.kind == 'spline':
+        s, ey, ep, g = _project_spline(track, px, py, psi)
+        cl[m], resid[m] = np.stack([s, ey, ep], axis=1), g
+        status[m] = np.where(np.abs(ey) > track.track_width / 2 + track.slack, 2, 0)
+    else:
+        s, ey, ep, found = _project_arcs(track, px, py, psi)
+        cl[m], resid[m] = np.stack([s, ey, ep], axis=1), np.where(found, 0.0, np.nan)
+        status[m] = np.where(found, 0, 2)
+    return cl, resid, status
+
+
+def _global_to_local(track, xy_coord):
+    xy = np.asarray(xy_coord, dtype=float)
+    if xy.ndim == 1:
+        if xy.shape[0] != 3:
+            raise ValueError('xy_coord: (x, y, psi)')
+        cl, _, status = global_to_local_batch(track, xy[None, :])
+        if track.kind == 'arcs' and status[0] == 2:
+            return None
+        return float(cl[0, 0]), float(cl[0, 1]), float(cl[0, 2])
+    return global_to_local_batch(track, xy)[0]
+
+
+def _global_to_local_typed(track, state):
+    cl = _global_to_local(track, (state.x.x, state.x.y, state.e.psi))
+    if cl is None:
+        return -1
+    state.p.s, state.p.x_tran, state.p.e_psi = cl
+    return 0
+
+
+def load_tum_raceline(file_path, track_name, tenth_scale=False, time_scale=1.0, segment=None, resample_resolution=None, solver=None):
+    """Reference DGSQP/tracks/track_lib.py:145-213, its ``segment=None`` branch: the triple of ``load_mpclab_raceline`` from a TUM raceline file
+    (``;``-separated rows s, x, y, psi, kappa, vx, ax).  Every row is projected onto the centre line -- with the numpy mirror, or on the device
+    with ``solver=`` a ``DGSQP`` on that track.  ``segment=`` / ``resample_resolution=`` (the study's track segment) are not built."""
+    if segment is not None or resample_resolution is not None:
+        raise NotImplementedError('load_tum_raceline: segment= / resample_resolution= (a raceline on a track segment) are not built; '
+                                  'the F1 game takes the window as s_range=')
+    from .montecarlo import Raceline
+    rl = Raceline.from_tum(file_path, track_name, tenth_scale=tenth_scale, time_scale=time_scale, solver=solver)
 
     def raceline(t):
         v = rl.eval(t)

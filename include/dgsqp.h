@@ -692,7 +692,8 @@ int dgsqp_pid_warm_start_batch(dgsqp_handle_t h, int64_t B, const double* q0, co
  *   DGSQP_SAMPLER_CIRCUIT        scripts/DGSQP_comp_monte_carlo.py:365-382 (M cars on a closed track)
  *   DGSQP_SAMPLER_MERGE          scripts/DGSQP_merge_monte_carlo.py:429-473 (unicycles, zero warm start)
  * key_pts: the arc track's key points (x, y, psi, cumulative length, segment length, signed curvature of the segment ENDING
- * there), n_key = segments + 1 (radius_arclength_track.py:361-408).
+ * there), n_key = segments + 1 (radius_arclength_track.py:361-408).  n_key = 0 on a spline-track handle: the CIRCUIT sampler places
+ * the cars on the handle's spline (the other kinds need seg0_len and are refused).
  */
 enum { DGSQP_SAMPLER_FIRST_SEGMENT = 0, DGSQP_SAMPLER_INDEPENDENT = 1, DGSQP_SAMPLER_CIRCUIT = 2, DGSQP_SAMPLER_MERGE = 3 };
 typedef struct {
@@ -846,6 +847,46 @@ typedef struct {
 /* x0_out, u_ws_out, candidates, stage: as dgsqp_sample_batch. */
 int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_sampler_t* spec, const dgsqp_raceline_ws_t* ws,
                                 double* x0_out, double* u_ws_out, int64_t* candidates, int stage);
+
+/*
+ * The sampler of scripts/comparison_study_f1/monte_carlo_sampler.py:25-55 on a spline-track handle (two cars), in the same rounds with the
+ * same uniforms: s1 = s_lo + (s_hi - s_lo) u0; s2 = s1 + gap_lo + (gap_hi - gap_lo) u3 (car 2 starts ahead of car 1); per car
+ * e_y = clip(raceline e_y + (2 u - 1), -+ey_clip), v = raceline v_long + (1.5 u - 0.75), e_psi = the raceline's (u1, u2 for car 1; u4, u5
+ * for car 2).  The study clips e_y with the track's width functions; ey_clip is one constant bound (stated deviation).  Rejection as
+ * dgsqp_sample_raceline_batch.  DGSQP_E_ARG, message starting "raceline: ": an arc-track handle, a non-finite entry, s_hi < s_lo,
+ * gap_hi < gap_lo, ey_clip < 0, collision_d < 0, and what dgsqp_sample_raceline_batch refuses.
+ */
+typedef struct {
+  uint64_t seed;
+  double s_lo, s_hi, gap_lo, gap_hi, ey_clip, collision_d;
+} dgsqp_raceline_spline_sampler_t;
+int dgsqp_sample_raceline_spline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_spline_sampler_t* spec, const dgsqp_raceline_ws_t* ws,
+                                       double* x0_out, double* u_ws_out, int64_t* candidates, int stage);
+
+/*
+ * Track-frame transforms for batches of points (csrc/dgsqp_track_frame.h), one lane per point, on the handle's stream.
+ *   n_key = 0   the handle's spline track (dgsqp_problem_t.spline): Frenet -> global is CasadiBSplineTrack.local_to_global; global ->
+ *               Frenet is the foot point reached from the closest piece start K_j by 30 Newton steps on g(s) = (c(s) - p) . c'(s), clipped
+ *               to [K_j - 1.5 D, K_j + 1.5 D] with D = K_1 - K_0 (the reference starts an NLP from the closest waypoint); a table whose ends
+ *               do not meet is not wrapped: s is clipped to [0, L]
+ *   n_key > 0   an arc track given by its key points (as dgsqp_sampler_t.key_pts; the handle's problem does not hold them):
+ *               radius_arclength_track.py:752-807 and :644-743
+ * half_width, slack: a projection with |e_y| > half_width + slack is off the track.
+ * cl [n][3] = (s, e_y, e_psi), xy [n][3] = (x, y, psi).  status [n]: 0 fine; 1 an input is not finite (outputs NaN); 2 off the track
+ * (spline: the values are still returned; arcs: no segment takes the point, outputs NaN).  resid [n] (may be NULL): the final g on a
+ * spline, 0 on arcs.  n = 0: DGSQP_OK.  DGSQP_E_ARG, message starting "track frame: ": n < 0, a NULL pointer, n_key = 0 on an arc-track
+ * handle, n_key > 0 on a spline-track handle, n_key outside 2 .. DGSQP_MAX_SEGS + 1, a non-finite entry, a track length that is not positive.
+ */
+typedef struct {
+  int32_t n_key;
+  int32_t _pad;
+  double half_width, slack;
+  double key_pts[DGSQP_MAX_SEGS + 1][6];
+} dgsqp_track_frame_t;
+int dgsqp_local_to_global_batch(dgsqp_handle_t h, int64_t n, const dgsqp_track_frame_t* t, const double* cl /* [n][3] s, e_y, e_psi */,
+                                double* xy /* [n][3] x, y, psi */);
+int dgsqp_global_to_local_batch(dgsqp_handle_t h, int64_t n, const dgsqp_track_frame_t* t, const double* xy, double* cl,
+                                double* resid /* may be NULL */, int32_t* status);
 
 
 /*
