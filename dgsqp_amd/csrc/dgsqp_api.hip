@@ -281,8 +281,8 @@ enum DgSideBuf {
   SB_V, SB_Q_EST,                                             // estimate noise: v and q_est [T][B][nq]
   SB_MON_SCRATCH, SB_CLEARANCE, SB_BOX_EXCESS, SB_HIT_STEP,   // the monitor: [grid][S][M][3]; clearance and box_excess [T][B], hit_step [B] int32
   SB_KIND, SB_PID, SB_REF, SB_U_REPLAY,                       // the drivers: [B][M] int32, [DGSQP_MAX_AGENTS] dgsqp_pid_t, [B][M][2], [T][B][nu]
-  SB_U_CMD, SB_CMD, SB_PID_STATE,                             // ... u_cmd [T][B][nu]; per workgroup: [grid][n] (2 M used: read as u_t is), [grid][M][3]
-  SB_U_GAME, SB_PLAN_STAGE, SB_GCMD, SB_HOLD_STATE,           // the held plan: u_game [T][B][nu], plan_stage [T][B] int32; per workgroup: [grid][n] as SB_CMD, [grid][2] int32
+  SB_U_CMD, SB_PID_STATE,                                     // ... u_cmd [T][B][nu]; per workgroup: [grid][M][3]
+  SB_U_GAME, SB_PLAN_STAGE, SB_HOLD_STATE,                    // the held plan: u_game [T][B][nu], plan_stage [T][B] int32; per workgroup: [grid][2] int32
   SB_U_PREV,                                                  // the carried input (dgsqp_set_closed_loop_u_prev): u_prev [T][B][nu]
   SB_X_GAME, SB_X_LIFT, SB_Z, SB_TRACK_REF,                   // the cross plant: the game as a dgsqp_plant_t; the game with bounds in the plant's layout; z [T+1][B][nz], track_ref [T][B][M][3]
   DG_SIDE_COUNT
@@ -822,31 +822,31 @@ static int further_check_launch(dgsqp_solver* h, int32_t T, int64_t B) {
     return refuse(h, "estimate noise: ", "launch of T = " + std::to_string(T) + ", B = " + std::to_string(B) + ", the noise was set for T = " + std::to_string(E.est_T) + ", B = " + std::to_string(E.est_B));
   return DGSQP_OK;
 }
+// Every launch with a plant fills all four parts of the one pack: the feedback touches every per-workgroup buffer whatever is set.
+// `wanted` false: the caller asked for no record of that part; its pointers stay null, the kernel skips the stores, and what an earlier
+// launch left behind stays fetchable.
 // the plant: delay lines per workgroup (the kernel clears them when a chain starts) and the u_plant record
-static int plant_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantDev* out) {
+static int plant_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, DgPlantPack* pk) {
   const DgSide& S = h->side;
   { const int rc = side_reserve(h, SB_LINES, sizeof(double) * (size_t)grid * DGSQP_MAX_AGENTS * DGSQP_NUA * DGSQP_MAX_DELAY); if (rc) return rc; }
   { const int rc = side_record(h, SB_U_PLANT, TB * h->plant.host.sim_steps * h->hp.nu, sizeof(double)); if (rc) return rc; }
-  *out = DgPlantDev{S.at<const dgsqp_plant_t>(SB_PLANT), S.at<double>(SB_LINES), S.at<double>(SB_U_PLANT)};
+  pk->B = B; pk->P = S.at<const dgsqp_plant_t>(SB_PLANT); pk->lines = S.at<double>(SB_LINES); pk->u_plant = S.at<double>(SB_U_PLANT);
   return DGSQP_OK;
 }
-// the further settings, whichever are on, around `pd`
-static int further_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, const DgPlantDev& pd, DgEnsembleDev* out) {
+// the further settings, whichever are on (the others stay null and zero)
+static int further_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, DgPlantPack* pk) {
   const DgEnsembleState& E = h->ens;
   DgSide& S = h->side;
-  const int64_t TB = (int64_t)T * B;
-  DgEnsembleDev ex{};
-  ex.pd = pd; ex.B = B;
   if (E.B > 0) {
     if (sizeof(dgsqp_plant_t) * (size_t)grid > S.b[SB_WG_PLANT].bytes) {
       { const int rc = side_reserve(h, SB_WG_PLANT, sizeof(dgsqp_plant_t) * (size_t)grid); if (rc) return rc; }
       HIPCHK(h, hipMemsetAsync(S.b[SB_WG_PLANT].p, 0, S.b[SB_WG_PLANT].bytes, h->stream));
     }
-    ex.vehicles = S.at<const dgsqp_vehicle_t>(SB_VEHICLES); ex.delay = E.has_delay ? S.at<const int32_t>(SB_DELAY) : nullptr; ex.wg_plant = S.at<dgsqp_plant_t>(SB_WG_PLANT);
+    pk->vehicles = S.at<const dgsqp_vehicle_t>(SB_VEHICLES); pk->delay = E.has_delay ? S.at<const int32_t>(SB_DELAY) : nullptr; pk->wg_plant = S.at<dgsqp_plant_t>(SB_WG_PLANT);
   }
   if (E.est_T > 0) {
     { const int rc = side_record(h, SB_Q_EST, TB * h->hp.nq, sizeof(double)); if (rc) return rc; }
-    ex.v = S.at<const double>(SB_V); ex.q_est = S.at<double>(SB_Q_EST);
+    pk->v = S.at<const double>(SB_V); pk->q_est = S.at<double>(SB_Q_EST);
   }
   if (E.monitor) {
     S.left[SB_CLEARANCE] = S.left[SB_BOX_EXCESS] = S.left[SB_HIT_STEP] = 0;      // one record in three arrays: none of it while any can fail
@@ -854,19 +854,18 @@ static int further_for_launch(dgsqp_solver* h, int grid, int64_t B, int32_t T, c
     { const int rc = side_record(h, SB_CLEARANCE, TB, sizeof(double)); if (rc) return rc; }
     { const int rc = side_record(h, SB_BOX_EXCESS, TB, sizeof(double)); if (rc) return rc; }
     { const int rc = side_record(h, SB_HIT_STEP, B, sizeof(int32_t)); if (rc) return rc; }
-    ex.monitor = E.monitor; ex.mon_scratch = S.at<double>(SB_MON_SCRATCH); ex.clearance = S.at<double>(SB_CLEARANCE); ex.box_excess = S.at<double>(SB_BOX_EXCESS);
-    ex.hit_step = S.at<int32_t>(SB_HIT_STEP);
+    pk->monitor = E.monitor; pk->mon_scratch = S.at<double>(SB_MON_SCRATCH); pk->clearance = S.at<double>(SB_CLEARANCE); pk->box_excess = S.at<double>(SB_BOX_EXCESS);
+    pk->hit_step = S.at<int32_t>(SB_HIT_STEP);
   }
-  *out = ex;
   return DGSQP_OK;
 }
-// the drivers, on top of `ex`: the per-workgroup command and PID-state buffers (the kernel writes before it reads them) and the u_cmd record.
-// A launch that holds a plan and has no drivers of the caller's runs with every agent of every chain on DGSQP_DRIVER_GAME: the kinds
-// are built here (all-GAME is the launch without drivers, bit for bit); gains, references and replay are never read then.
-static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, const DgEnsembleDev& ex, DgPlantDriversDev* out) {
+// the drivers: the per-workgroup PID state (the kernel writes before it reads it) and, when `wanted`, the u_cmd record.  A launch without
+// drivers of the caller's runs with every agent of every chain on DGSQP_DRIVER_GAME: the kinds are built here (all-GAME is the launch
+// without drivers, bit for bit); gains, references and replay are never read then.
+static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, DgPlantPack* pk) {
   DgDriversState& R = h->drv;
   DgSide& S = h->side;
-  S.left[SB_U_CMD] = 0;
+  const bool wanted = R.set || h->hold.set || h->cross.set;      // u_cmd null: every agent is GAME under the default hold, which is what the carry relies on
   if (!R.set) {
     static_assert(DGSQP_DRIVER_GAME == 0, "all-GAME kinds are a buffer of zero bytes");
     R.has_ref = R.has_replay = false;
@@ -874,38 +873,37 @@ static int drivers_for_launch(dgsqp_solver* h, int grid, int64_t B, int64_t TB, 
     { const int rc = side_reserve(h, SB_PID, sizeof(dgsqp_pid_t) * DGSQP_MAX_AGENTS); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(S.b[SB_KIND].p, 0, sizeof(int32_t) * (size_t)B * h->hp.M, h->stream));
   }
-  { const int rc = side_reserve(h, SB_CMD, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }
   { const int rc = side_reserve(h, SB_PID_STATE, sizeof(double) * (size_t)grid * h->hp.M * 3); if (rc) return rc; }
-  { const int rc = side_record(h, SB_U_CMD, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
-  DgPlantDriversDev dd{};
-  dd.ex = ex;
-  dd.kind = S.at<const int32_t>(SB_KIND); dd.pid = S.at<const dgsqp_pid_t>(SB_PID);
-  dd.ref = R.has_ref ? S.at<const double>(SB_REF) : nullptr; dd.u_replay = R.has_replay ? S.at<const double>(SB_U_REPLAY) : nullptr;
-  dd.u_cmd = S.at<double>(SB_U_CMD); dd.cmd = S.at<double>(SB_CMD); dd.pid_state = S.at<double>(SB_PID_STATE);
-  *out = dd;
+  if (wanted) {
+    S.left[SB_U_CMD] = 0;
+    { const int rc = side_record(h, SB_U_CMD, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
+    pk->u_cmd = S.at<double>(SB_U_CMD);
+  }
+  pk->kind = S.at<const int32_t>(SB_KIND); pk->pid = S.at<const dgsqp_pid_t>(SB_PID);
+  pk->ref = R.has_ref ? S.at<const double>(SB_REF) : nullptr; pk->u_replay = R.has_replay ? S.at<const double>(SB_U_REPLAY) : nullptr;
+  pk->pid_state = S.at<double>(SB_PID_STATE);
   return DGSQP_OK;
 }
-// the held plan, on top of `dd`: the per-workgroup command and (age, due) buffers (the kernel writes before it reads them) and the u_game
-// and plan_stage records
-static int hold_for_launch(dgsqp_solver* h, int grid, int64_t TB, const DgPlantDriversDev& dd, DgPlantDriversHoldDev* out) {
+// the held plan: the per-workgroup (age, due) (the kernel writes before it reads it) and, when `wanted`, the u_game and plan_stage records.
+// A launch without a hold of the caller's: R = 1 with the reference's rule, which is the launch without the setting, bit for bit.
+static int hold_for_launch(dgsqp_solver* h, int grid, int64_t TB, DgPlantPack* pk) {
   DgSide& S = h->side;
-  S.left[SB_U_GAME] = S.left[SB_PLAN_STAGE] = 0;      // one record in two arrays: none of it while either can fail
-  { const int rc = side_reserve(h, SB_GCMD, sizeof(double) * (size_t)grid * h->hp.n); if (rc) return rc; }
+  const bool wanted = h->hold.set || h->cross.set;
   { const int rc = side_reserve(h, SB_HOLD_STATE, sizeof(int32_t) * (size_t)grid * 2); if (rc) return rc; }
-  { const int rc = side_record(h, SB_U_GAME, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
-  { const int rc = side_record(h, SB_PLAN_STAGE, TB, sizeof(int32_t)); if (rc) return rc; }
-  DgPlantDriversHoldDev hd{};
-  hd.dd = dd;
-  // (a cross-plant launch without a hold of the caller's: R = 1 with the reference's rule, which is the launch without the setting)
+  if (wanted) {
+    S.left[SB_U_GAME] = S.left[SB_PLAN_STAGE] = 0;      // one record in two arrays: none of it while either can fail
+    { const int rc = side_record(h, SB_U_GAME, TB * h->hp.nu, sizeof(double)); if (rc) return rc; }
+    { const int rc = side_record(h, SB_PLAN_STAGE, TB, sizeof(int32_t)); if (rc) return rc; }
+    pk->u_game = S.at<double>(SB_U_GAME); pk->plan_stage = S.at<int32_t>(SB_PLAN_STAGE);
+  }
   const dgsqp_hold_t off{1, DGSQP_HOLD_REFERENCE, (1u << DGSQP_DIVERGED) | (1u << DGSQP_QP_FAIL), 0};
   const dgsqp_hold_t& H = h->hold.set ? h->hold.host : off;
-  hd.replan_every = H.replan_every; hd.on_fail = H.on_fail; hd.fail_mask = H.fail_mask;
-  hd.u_game = S.at<double>(SB_U_GAME); hd.plan_stage = S.at<int32_t>(SB_PLAN_STAGE); hd.gcmd = S.at<double>(SB_GCMD); hd.state = S.at<int32_t>(SB_HOLD_STATE);
-  *out = hd;
+  pk->replan_every = H.replan_every; pk->on_fail = H.on_fail; pk->fail_mask = H.fail_mask;
+  pk->state = S.at<int32_t>(SB_HOLD_STATE);
   return DGSQP_OK;
 }
 // The cross plant.  Before the launch: its shape, x0 = p(z0) bit for bit, no disturbance, and a GAME driver only where the game's inputs
-// mean what the plant's do.  For the launch, on top of `hd`: the z record with z0 in slice 0, and track_ref.
+// mean what the plant's do.  For the launch, in the pack's cross part: the z record with z0 in slice 0, and track_ref.
 static int cross_check_launch(dgsqp_solver* h, int64_t B, const double* x0, const double* w) {
   const DgCrossState& X = h->cross;
   const DgProb& D = h->hp;
@@ -926,21 +924,18 @@ static int cross_check_launch(dgsqp_solver* h, int64_t B, const double* x0, cons
   }
   return DGSQP_OK;
 }
-static int cross_for_launch(dgsqp_solver* h, int64_t B, int32_t T, const DgPlantDriversHoldDev& hd, DgCrossPlantDev* out) {
+static int cross_for_launch(dgsqp_solver* h, int64_t B, int32_t T, DgCrossPack* xp) {
   const DgCrossState& X = h->cross;
   DgSide& S = h->side;
   S.left[SB_Z] = S.left[SB_TRACK_REF] = 0;
   { const int rc = side_record(h, SB_Z, ((int64_t)T + 1) * B * X.nz_all, sizeof(double)); if (rc) return rc; }
   { const int rc = side_record(h, SB_TRACK_REF, (int64_t)T * B * h->hp.M * 3, sizeof(double)); if (rc) return rc; }
   HIPCHK(h, hipMemcpyAsync(S.b[SB_Z].p, X.z0.data(), sizeof(double) * X.z0.size(), hipMemcpyHostToDevice, h->stream));
-  DgCrossPlantDev xp{};
-  xp.hd = hd;
-  for (int a = 0; a < DGSQP_MAX_AGENTS; a++) { xp.mdl[a] = X.mdl[a]; xp.nz[a] = X.nz[a]; xp.zoff[a] = X.zoff[a]; }
-  xp.nz_all = X.nz_all;
-  memcpy(xp.proj, X.proj, sizeof(xp.proj));
-  xp.lift = S.at<const dgsqp_problem_t>(SB_X_LIFT); xp.game = S.at<const dgsqp_plant_t>(SB_X_GAME);
-  xp.z = S.at<double>(SB_Z); xp.track_ref = S.at<double>(SB_TRACK_REF);
-  *out = xp;
+  for (int a = 0; a < DGSQP_MAX_AGENTS; a++) { xp->mdl[a] = X.mdl[a]; xp->nz[a] = X.nz[a]; xp->zoff[a] = X.zoff[a]; }
+  xp->nz_all = X.nz_all;
+  memcpy(xp->proj, X.proj, sizeof(xp->proj));
+  xp->lift = S.at<const dgsqp_problem_t>(SB_X_LIFT); xp->game = S.at<const dgsqp_plant_t>(SB_X_GAME);
+  xp->z = S.at<double>(SB_Z); xp->track_ref = S.at<double>(SB_TRACK_REF);
   return DGSQP_OK;
 }
 // the one launch of dg_closed_loop_kernel, instantiated for the argument pack the settings call for (none: no plant)
@@ -1042,9 +1037,7 @@ int dgsqp_create(const dgsqp_problem_t* prob, const dgsqp_params_t* par, int dev
   if (hipMalloc((void**)&h->d_coop, h->coop_bytes) != hipSuccess) return fail("hipMalloc(coop) failed");
   if (hipMalloc((void**)&h->d_coop_payload, sizeof(double) * 2 * (2 * (size_t)h->hp.n + 2 * (size_t)h->hp.nc) * (size_t)(h->num_cu * 2 + 2)) != hipSuccess) return fail("hipMalloc(coop payload) failed");
   const void* kernels[] = {(const void*)dg_solve_kernel, (const void*)dg_evaluate_kernel, (const void*)dg_qp_kernel, (const void*)dg_closed_loop_kernel<>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDev>, (const void*)dg_closed_loop_kernel<DgEnsembleDev>,
-                           (const void*)dg_closed_loop_kernel<DgPlantDriversDev>, (const void*)dg_closed_loop_kernel<DgPlantDriversHoldDev>,
-                           (const void*)dg_closed_loop_kernel<DgCrossPlantDev>};
+                           (const void*)dg_closed_loop_kernel<DgPlantPack>, (const void*)dg_closed_loop_kernel<DgCrossPack>};
   for (const void* k : kernels) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
@@ -1637,9 +1630,9 @@ int dgsqp_fetch_plan_hold(dgsqp_handle_t h, double* u_game, int32_t* plan_stage,
                     "no closed-loop launch with a plan hold has run", "plan hold: null argument", "u_game", capacity_doubles);
 }
 
-// Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h), with a
-// DgPlantDev argument when the handle has a plant, a DgEnsembleDev when one of the further settings is on as well, a DgPlantDriversDev
-// when drivers are set, a DgPlantDriversHoldDev when a plan is held, and a DgCrossPlantDev when the plant is a cross plant.
+// Closed-loop batch: B chains of T receding-horizon steps in ONE launch of dg_closed_loop_kernel (dgsqp_closed_loop.h): without an
+// argument pack when the handle has no plant, with a DgPlantPack when it has one (every further setting is a field of it), and with a
+// DgCrossPack when the plant is a cross plant.
 int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double* x0, const double* u_ws, const double* w,
                             double* q_out, double* u_ws_out, double* u_out, double* l_out, double* x_out, int32_t* status,
                             int32_t* iters, int32_t* qp_solves, double* cond, double* cost, int32_t* steps_done, dgsqp_timing_t* tm) {
@@ -1651,7 +1644,7 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
   if (!x0 || !u_ws || !q_out || !u_ws_out || !u_out || !status || !iters || !qp_solves || !cond || !cost || !steps_done) {
     h->err = "closed loop: null argument (only w, l_out, x_out and timing may be NULL)"; return DGSQP_E_ARG;
   }
-  const bool cross = h->cross.set, further = h->ens.any(), hold = h->hold.set || cross, drivers = h->drv.set || hold;
+  const bool cross = h->cross.set;
   { const int rc = further_check_plant(h); if (rc) return rc; }
   { const int rc = drivers_check_launch(h, T, B); if (rc) return rc; }
   { const int rc = hold_check_launch(h); if (rc) return rc; }
@@ -1695,26 +1688,21 @@ int dgsqp_closed_loop_batch(dgsqp_handle_t h, int64_t B, int32_t T, const double
     if (U.cl_B > 0) HIPCHK(h, hipMemcpyAsync(cl.up, U.cl_host.data(), slice, hipMemcpyHostToDevice, h->stream));
     else HIPCHK(h, hipMemsetAsync(cl.up, 0, slice, h->stream));
   }
-  DgPlantDev pd{};
-  DgEnsembleDev ex{};
-  if (h->plant.set) { const int rc = plant_for_launch(h, grid, TB, &pd); if (rc) return rc; }
-  DgPlantDriversDev dd{};
-  if (further || drivers) { const int rc = further_for_launch(h, grid, B, T, pd, &ex); if (rc) return rc; }
-  if (drivers) { const int rc = drivers_for_launch(h, grid, B, TB, ex, &dd); if (rc) return rc; }
-  DgPlantDriversHoldDev hd{};
-  if (hold) { const int rc = hold_for_launch(h, grid, TB, dd, &hd); if (rc) return rc; }
-  DgCrossPlantDev xp{};
-  if (cross) { const int rc = cross_for_launch(h, B, T, hd, &xp); if (rc) return rc; }
+  DgCrossPack xp{};      // (its DgPlantPack part is the whole pack of a launch with a plant of the game's class)
+  if (h->plant.set) {
+    { const int rc = plant_for_launch(h, grid, B, TB, &xp); if (rc) return rc; }
+    { const int rc = further_for_launch(h, grid, B, TB, &xp); if (rc) return rc; }
+    { const int rc = drivers_for_launch(h, grid, B, TB, &xp); if (rc) return rc; }
+    { const int rc = hold_for_launch(h, grid, TB, &xp); if (rc) return rc; }
+    if (cross) { const int rc = cross_for_launch(h, B, T, &xp); if (rc) return rc; }
+  }
   {
     std::unique_lock<std::mutex> game_lock;
     { const int rc = begin_launch(h, game_lock); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->ticket, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (cross) launch_closed_loop(h, grid, B, cl, xp);
-    else if (hold) launch_closed_loop(h, grid, B, cl, hd);
-    else if (drivers) launch_closed_loop(h, grid, B, cl, dd);
-    else if (further) launch_closed_loop(h, grid, B, cl, ex);
-    else if (h->plant.set) launch_closed_loop(h, grid, B, cl, pd);
+    else if (h->plant.set) launch_closed_loop<DgPlantPack>(h, grid, B, cl, xp);
     else launch_closed_loop(h, grid, B, cl);
     HIPCHK(h, hipGetLastError());
     h->launch_stream = h->stream;

@@ -1,5 +1,5 @@
 """A plant of another model class than the game's on the device: DGSQP.step_batch(..., plant=PlantModel(..., own_class=True), z0=...) /
-dgsqp_set_cross_plant, dgsqp_fetch_plant_state, dgsqp_fetch_track_ref and DGSQP_DRIVER_TRACK (the DgCrossPlantDev instantiation of
+dgsqp_set_cross_plant, dgsqp_fetch_plant_state, dgsqp_fetch_track_ref and DGSQP_DRIVER_TRACK (the DgCrossPack instantiation of
 dg_closed_loop_kernel, csrc/dgsqp_closed_loop.h).  The plant keeps a state z of its own, the game sees q = p(z); a 'track' driver follows
 the game's plan with the lane follower.  The checks common to every case are those of tests/closed_loop_cross_checks.py."""
 import ctypes

@@ -1,5 +1,5 @@
 """Drivers of closed-loop batches on the device: DGSQP.step_batch(..., drivers=Drivers(...)) / dgsqp_set_drivers, dgsqp_fetch_u_cmd (the
-DgPlantDriversDev instantiation of dg_closed_loop_kernel, csrc/dgsqp_closed_loop.h): per agent and per chain the command that enters the plant
+drivers' fields of DgPlantPack and step 2 of dev_plant_feedback, csrc/dgsqp_closed_loop.h): per agent and per chain the command that enters the plant
 is stage 0 of the game's solution, the PID lane follower run closed-loop on the true state, or a replayed sequence.
 
 The idiom is that of tests/test_closed_loop_ensemble.py, with the helpers of tests/closed_loop_checks.py: TEACHER FORCING, the warm-start

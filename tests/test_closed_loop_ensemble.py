@@ -1,6 +1,6 @@
 """Per-chain plants, state estimates and the safety monitor of closed-loop batches on the device: DGSQP.step_batch(..., plant=PlantModel(
 per_chain_configs=...), estimate_noise=..., monitor=...) / dgsqp_set_plant_ensemble, dgsqp_set_estimate_noise, dgsqp_set_monitor
-(the DgEnsembleDev instantiation of dg_closed_loop_kernel, csrc/dgsqp_closed_loop.h).
+(their fields of DgPlantPack, the pack of every launch with a plant: csrc/dgsqp_closed_loop.h).
 
 The idiom is that of tests/test_closed_loop_plant.py, with the helpers of tests/closed_loop_checks.py: TEACHER FORCING (every step that ran
 is, bit for bit, the ``solve_batch`` solve from the recorded (state the solve started from, u_ws[t]) -- the state is q_est[t] with

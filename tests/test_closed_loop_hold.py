@@ -1,5 +1,5 @@
 """Held plans of closed-loop batches on the device: DGSQP.step_batch(..., hold=PlanHold(...)) / dgsqp_set_plan_hold, dgsqp_fetch_plan_hold (the
-DgPlantDriversHoldDev instantiation of dg_closed_loop_kernel, csrc/dgsqp_closed_loop.h): a chain solves only when a plan is due -- every R-th
+held plan's fields of DgPlantPack, dev_hold_due and dev_hold_next, csrc/dgsqp_closed_loop.h): a chain solves only when a plan is due -- every R-th
 step after an accepted solve -- and otherwise feeds the plant the next stage of the warm start it holds; after a failed solve it does so
 too when on_fail = 'hold'.
 

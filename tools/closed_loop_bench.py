@@ -20,10 +20,10 @@ asserts that both produce identical status, num_iters and q.
 delay per chain), ``estimates`` (that plant, solves from q + 1e-3 N(0, 1)), and the last two with the monitor recording
 (``ensemble+monitor``, ``estimates+monitor``); and two launches with drivers (``closed_loop.Drivers``) on that plant: ``pid`` (car 2 on the
 PID lane follower with its default gains, references from x0) and ``replay`` (car 2 replays the commands the game gave it in the ``plant``
-launch: the same chains as ``plant``, bit for bit, through the drivers' kernel).  ``--carry-u-prev`` adds ``carry-u-prev``: ``plain`` with the command of step t carried into solve t + 1 as the input
+launch: the same chains as ``plant``, bit for bit, with car 2's command read from u_replay).  ``--carry-u-prev`` adds ``carry-u-prev``: ``plain`` with the command of step t carried into solve t + 1 as the input
 before its stage 0 (``step_batch(..., u_prev=True)``) -- other solves, so other chains: its time stands next to the others, not against them.
 ``--kinds ...,hold`` adds ``hold`` (named in ``--kinds`` only): the ``plant`` launch with a held plan (``closed_loop.PlanHold``, on_fail 'reference'), once per value of
-``--replan-every`` (default 1).  R = 1 is the ``plant`` launch's own chains through the held-plan kernel (asserted), so its time stands against ``plant``'s; R > 1 follows each
+``--replan-every`` (default 1).  R = 1 is the ``plant`` launch's own chains with the hold named (asserted), so its time stands against ``plant``'s; R > 1 follows each
 accepted plan for R control steps -- other chains -- and the report counts the solves actually run and the held steps.
 ``--kinds ...,cross`` with ``--model kinematic`` adds ``cross`` (named in ``--kinds`` only): the kinematic curve game (N = 25) on DYNAMIC-bicycle plants of their own state
 (``PlantModel(own_class=True)``: the Pacejka vehicle of configs[1], the ``plant`` launch's integrator, simulation steps and delay; GAME drivers) -- other chains than ``plant``'s,
