@@ -46,6 +46,7 @@ class AgentT(C.Structure):
         ('radius', C.c_double),
         ('w_goal', C.c_double * MAX_NQA), ('goal', C.c_double * MAX_NQA), ('goal_term_mult', C.c_double),
         ('n_lane', C.c_int32), ('_pad2', C.c_int32), ('lane', LaneT * MAX_LANES),
+        ('edge_rows', C.c_int32), ('_pad3', C.c_int32), ('edge_margin', C.c_double),
     ]
 
 
@@ -59,6 +60,7 @@ class ProblemT(C.Structure):
         ('seg_ang', C.c_double * (MAX_SEGS + 1)),
         ('agents', AgentT * MAX_AGENTS),
         ('track_kind', C.c_int32), ('n_knots', C.c_int32), ('spline', C.c_uint64),     # const double*: kept as an integer so that the POD stays copyable / picklable
+        ('n_width', C.c_int32), ('_pad_w', C.c_int32), ('widths', C.c_uint64),         # track width table [n_width][3] (knot, left, right); 0: none
     ]
 
 
@@ -132,7 +134,7 @@ class MpcT(C.Structure):
     _fields_ = [('agent', C.c_int32), ('N', C.c_int32), ('qp_iters', C.c_int32), ('zero_du', C.c_int32), ('damping', C.c_double),
                 ('w_q', C.c_double * MAX_NQA), ('c_N', C.c_double * MAX_NQA), ('w_u', dbl2), ('w_du', dbl2),
                 ('q_ub', C.c_double * MAX_NQA), ('q_lb', C.c_double * MAX_NQA), ('u_ub', dbl2), ('u_lb', dbl2), ('du_ub', dbl2), ('du_lb', dbl2),
-                ('n_soft', C.c_int32), ('reserved_', C.c_int32), ('soft_idx', C.c_int32 * MAX_NQA),
+                ('n_soft', C.c_int32), ('edge_rows', C.c_int32), ('soft_idx', C.c_int32 * MAX_NQA),
                 ('soft_quad', C.c_double * MAX_NQA), ('soft_lin', C.c_double * MAX_NQA), ('obs_r', C.c_double)]
 
 
@@ -172,7 +174,7 @@ class TrackFrameT(C.Structure):
                 ('key_pts', (C.c_double * 6) * (MAX_SEGS + 1))]
 
 
-MPC_ROW_RATE, MPC_ROW_SLACK, MPC_ROW_INPUT, MPC_ROW_STATE, MPC_ROW_SOFT, MPC_ROW_OBS = range(6)     # DGSQP_MPC_ROW_*
+MPC_ROW_RATE, MPC_ROW_SLACK, MPC_ROW_INPUT, MPC_ROW_STATE, MPC_ROW_SOFT, MPC_ROW_OBS, MPC_ROW_EDGE = range(7)     # DGSQP_MPC_ROW_*
 MPC_NMAX = 128                                                                                      # DGSQP_MPC_NMAX
 E_ARG, E_DEVICE, E_NOMEM, E_TOO_LARGE = -1, -2, -3, -4                                              # DGSQP_E_*
 
@@ -252,6 +254,7 @@ SIGNATURES = {
     'dgsqp_fetch_raceline_ref': (C.c_int, [_H, _PD, C.c_int64]),
     'dgsqp_sample_raceline_batch': (C.c_int, [_H, C.c_int64, C.POINTER(RacelineSamplerT), C.POINTER(RacelineWsT), _PD, _PD,
                                               C.POINTER(C.c_int64), C.c_int]),
+    'dgsqp_set_raceline_clip': (C.c_int, [_H, C.c_int, C.c_double]),
     'dgsqp_sample_raceline_spline_batch': (C.c_int, [_H, C.c_int64, C.POINTER(RacelineSplineSamplerT), C.POINTER(RacelineWsT), _PD, _PD,
                                                      C.POINTER(C.c_int64), C.c_int]),
     'dgsqp_local_to_global_batch': (C.c_int, [_H, C.c_int64, C.POINTER(TrackFrameT), _PD, _PD]),

@@ -128,6 +128,7 @@ dg_solve_kernel(const DgProb* __restrict__ D, int64_t B, const double* __restric
 #include "dgsqp_closed_loop.h"
 #include "dgsqp_pid.h"
 #include "dgsqp_sampler.h"
+#include "dgsqp_track_width.h"
 #include "dgsqp_mpc.h"
 #include "dgsqp_raceline.h"
 #include "dgsqp_track_frame.h"
@@ -394,6 +395,8 @@ struct dgsqp_solver {
   DgUPrevState up;                         // the input before stage 0: plain solves and hooks, and closed-loop carry
   DgMpcState mpc;                          // the reference tracker (dgsqp_set_mpc)
   DgRacelineState rl;                      // the raceline (dgsqp_set_raceline)
+  int rl_clip_widths = 0;                  // e_y clip of the spline-track raceline sampler (dgsqp_set_raceline_clip)
+  double rl_clip_scale = 0.0;
   bool in_flight = false;       // a solve launch has been enqueued and not yet waited for
   dgsqp_solver* group_leader = nullptr;   // set while this handle's batch is being solved by another handle's grouped launch
   DgBatch* d_group = nullptr;             // leader: device table of the group's batches (DG_GROUP_MAX entries)
@@ -1860,6 +1863,9 @@ static int mpc_plan(const DgProb& D, const dgsqp_mpc_t& c, dg_mpc::DgMpcDev& M, 
     if (!std::isfinite(c.q_ub[c.soft_idx[i]]) || !std::isfinite(c.q_lb[c.soft_idx[i]])) return bad("a soft state needs finite bounds");
   }
   if (!(c.obs_r >= 0.0) || !std::isfinite(c.obs_r)) return bad("obs_r must be finite and non-negative");
+  if (c.edge_rows != 0 && c.edge_rows != 1) return bad("edge_rows must be 0 or 1");
+  if (c.edge_rows && D.P.n_width < 2) return bad("edge_rows on a handle without a width table (dgsqp_problem_t.widths)");
+  if (c.edge_rows && D.mdl[c.agent] == DG_UNI) return bad("edge_rows need an agent with (s, e_y): agent " + std::to_string(c.agent) + " is a unicycle");
   const int64_t n64 = (int64_t)c.N * nu + 2 * c.n_soft;
   if (n64 > DGSQP_MPC_NMAX) { msg = "mpc: N n_u + 2 n_soft = " + std::to_string(n64) + " condensed variables exceed " + std::to_string(DGSQP_MPC_NMAX); return DGSQP_E_TOO_LARGE; }
   memset(&M, 0, sizeof M);
@@ -1892,6 +1898,7 @@ static int mpc_plan(const DgProb& D, const dgsqp_mpc_t& c, dg_mpc::DgMpcDev& M, 
   for (int s = 0; s < ns; s++)
     for (int k = 1; k <= N; k++) { rows.push_back({DGSQP_MPC_ROW_SOFT, k, s, 1}); rows.push_back({DGSQP_MPC_ROW_SOFT, k, s, -1}); }
   if (c.obs_r > 0.0) for (int k = 1; k <= N; k++) rows.push_back({DGSQP_MPC_ROW_OBS, k, 0, 1});
+  if (c.edge_rows) for (int k = 1; k <= N; k++) { rows.push_back({DGSQP_MPC_ROW_EDGE, k, 0, -1}); rows.push_back({DGSQP_MPC_ROW_EDGE, k, 0, 1}); }   // right, left
   M.nrows = (int)rows.size();
   M.max_steps = 20 * n + 2 * M.nrows + 100;
   // LDS, behind the game's persistent part (the track and atan tables f_c reads)
@@ -1900,6 +1907,7 @@ static int mpc_plan(const DgProb& D, const dgsqp_mpc_t& c, dg_mpc::DgMpcDev& M, 
   M.o_J = take(n * (n + 1) / 2);
   M.o_g = take(n); M.o_y = take(n); M.o_x = take(n); M.o_a = take(n); M.o_d = take(n); M.o_z = take(n); M.o_w = take(n); M.o_r = take(n); M.o_lam = take(n);
   M.o_act = take((n + 2) / 2); M.o_D = take(M.lenD); M.o_Db = take(M.lenD); M.o_P0 = take(nz); M.o_flag = take((M.nrows + 2) / 2);
+  M.o_wid = c.edge_rows ? take(4 * N) : o;      // (w_L, w_L', w_R, w_R') per stage 1..N; a record without edge rows keeps its arena
   M.o_end = o;
   if ((long)o * 8 > DG_LDS_LIMIT) {
     msg = "mpc: the tracker needs " + std::to_string((long)o * 8) + " B of LDS per workgroup (limit " + std::to_string(DG_LDS_LIMIT) + "): N=" + std::to_string(N) + " n=" + std::to_string(n);
@@ -2468,8 +2476,18 @@ int dgsqp_sample_raceline_spline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_
     return refuse(h, "raceline: ", "bad sampler description");
   { const int rc = raceline_check(h, W); if (rc) return rc; }
   return raceline_rounds(h, B, W, [&](int64_t nround, unsigned long long c0, double* dq0, int32_t* dcol) {
-    hipLaunchKernelGGL(dg_raceline_place_spline_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, h->rl.dev, dq0, dcol);
+    hipLaunchKernelGGL(dg_raceline_place_spline_kernel, dim3((unsigned)((nround + 255) / 256)), dim3(256), 0, h->stream, nround, c0, *spec, h->rl_clip_widths, h->rl_clip_scale, h->rl.dev, dq0, dcol);
   }, x0_out, u_ws_out, candidates, stage);
+}
+
+int dgsqp_set_raceline_clip(dgsqp_handle_t h, int clip_widths, double clip_scale) {
+  if (!h) return DGSQP_E_ARG;
+  if (clip_widths != 0 && clip_widths != 1) return refuse(h, "raceline: ", "clip_widths must be 0 or 1");
+  if (clip_widths && h->hp.P.n_width < 2) return refuse(h, "raceline: ", "clip_widths = 1 on a handle without a width table (dgsqp_problem_t.widths)");
+  if (clip_widths && !(std::isfinite(clip_scale) && clip_scale >= 0.0)) return refuse(h, "raceline: ", "clip_scale must be finite and not negative");
+  h->rl_clip_widths = clip_widths;
+  h->rl_clip_scale = clip_widths ? clip_scale : 0.0;
+  return DGSQP_OK;
 }
 
 // ---- track-frame transforms (dgsqp_track_frame.h) ----

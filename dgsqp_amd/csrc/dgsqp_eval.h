@@ -2,6 +2,7 @@
 // Jacobians / Hessians, sensitivities, q, g, packed G and the raw game Hessian Q.
 #pragma once
 #include "dgsqp_device.h"
+#include "dgsqp_track_width.h"
 
 // ------------------------------------------------------------------------------------------------
 // state-dependent part of agent a's cost (chicane.py:239-256, ablation.py:229-262): value and
@@ -679,6 +680,11 @@ __device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it, gptr tang)
             for (int i = 0; i < nqa; i++) val = (i == dd.idx) ? v[i] : val;  // keeps v[] in registers
             gd_store(c, dd.off + t0 * DGSQP_NUA + j, val);
           }
+        } else if (dd.kind == 3) {
+          if (dd.a == a) {     // track edge: -+de_y/du - w'(s_k) ds/du, w' from the record of (a, k) (dev_fill_widths)
+            cgptr wr = c.ws + D.ws_wid + 4 * (a * (D.N + 1) + k);
+            gd_store(c, dd.off + t0 * DGSQP_NUA + j, dd.idx ? v[nqa - 1] - wr[1] * v[nqa - 2] : -v[nqa - 1] - wr[3] * v[nqa - 2]);
+          }
         } else if (dd.kind == 2) {
           if (dd.a == a) {     // lane half-plane: n(p_x) . d p_k / du, the normal is piecewise constant in p_x (merge.py:66-74)
             const auto& ln = ag.lane[dd.idx];
@@ -713,6 +719,23 @@ __device__ inline void dev_chain_item(const Ctx& c, clptr ue, int it, gptr tang)
   }
 }
 
+// Track-edge rows: one record (w_L, w_L', w_R, w_R') per (agent, stage 1..N) at s of the trajectory in e_x, one lane per pair, into the
+// workgroup's scratch.  Called behind a rollout (or a copied / retained trajectory); the caller's barrier publishes it to the rows,
+// the chains and the costate source, none of which searches the table again.
+__device__ __noinline__ void dev_fill_widths(const Ctx& c) {
+  const DgProb& D = dg_prob;
+  clptr x = LP(D.L.e_x);
+  for (int it = TID; it < D.M * D.N; it += NT) {
+    const int a = it / D.N, k = it % D.N + 1;
+    if (!D.P.agents[a].edge_rows) continue;
+    gptr w = c.ws + D.ws_wid + 4 * (a * (D.N + 1) + k);
+    double wL, dwL, wR, dwR;
+    dev_track_width(x[k * D.nq + D.qoff[a] + D.sidx[a]], &wL, &dwL, &wR, &dwR);
+    w[0] = wL; w[1] = dwL; w[2] = wR; w[3] = dwR;
+  }
+  __threadfence_block();
+}
+
 // constraint values (f_Cxu, DGSQP.py:729-821, 911)
 __device__ __noinline__ void dev_constraint_values(const Ctx& c, clptr ue) {
   const DgProb& D = dg_prob;
@@ -745,6 +768,8 @@ __device__ __noinline__ void dev_constraint_values(const Ctx& c, clptr ue) {
         const double nx = hi ? ln.n_hi[0] : ln.n_lo[0], ny = hi ? ln.n_hi[1] : ln.n_lo[1];
         g = nx * (xk[ia] - (ln.anchor[0] - ln.r * nx)) + ny * (xk[ia + 1] - (ln.anchor[1] - ln.r * ny));
       } break;
+      case DG_R_EDGE_R: g = -(c.ws[D.ws_wid + 4 * (R.a * (D.N + 1) + R.k) + 2] - ag.edge_margin) - xk[D.qoff[R.a] + D.eyidx[R.a]]; break;
+      case DG_R_EDGE_L: g = xk[D.qoff[R.a] + D.eyidx[R.a]] - (c.ws[D.ws_wid + 4 * (R.a * (D.N + 1) + R.k)] - ag.edge_margin); break;
       default: g = ag.st_lb[R.idx] - xk[D.qoff[R.a] + R.idx]; break;
     }
     LP(L.g)[r] = g;
@@ -1064,6 +1089,11 @@ __device__ __noinline__ void dev_costates(const Ctx& c, clptr lm) {
         const int ip = D.qoff[R.a];
         const bool hi = xk[ip] >= ln.brk;
         Dx[ip] += lr * (hi ? ln.n_hi[0] : ln.n_lo[0]); Dx[ip + 1] += lr * (hi ? ln.n_hi[1] : ln.n_lo[1]);
+      } else if (R.type == DG_R_EDGE_R || R.type == DG_R_EDGE_L) {      // (-+w'(s), -+1) over (s, e_y): no Hessian of its own
+        cgptr wr = c.ws + D.ws_wid + 4 * (R.a * (N + 1) + k);
+        const int ip = D.qoff[R.a];
+        Dx[ip + D.sidx[R.a]] -= lr * (R.type == DG_R_EDGE_L ? wr[1] : wr[3]);
+        Dx[ip + D.eyidx[R.a]] += R.type == DG_R_EDGE_L ? lr : -lr;
       } else Dx[D.qoff[R.a] + R.idx] -= lr;
     }
   };
@@ -1237,6 +1267,7 @@ __device__ inline void dev_evaluate_point(const Ctx& c, clptr usrc, double alpha
     else dev_rollout(c, ue, LP(L.e_x));
     PROF_END(PH_ROLLOUT, pt_);
   } else newtag = tag;          // same input as the one the scratch was computed for: everything that was valid still is
+  if (D.n_edge) dev_fill_widths(c);
   __syncthreads();
   if (TID == 0) LP(L.scal)[DG_XVALID] = newtag;
   dev_constraint_values(c, ue);

@@ -33,7 +33,7 @@ __host__ __device__ constexpr int dg_model_nq(int mdl) { return mdl == DGSQP_MOD
 #define DG_UNI DGSQP_MODEL_UNICYCLE
 #define DG_PM DGSQP_MODEL_UNICYCLE_COMBINED
 
-enum { DG_R_OBS = 0, DG_R_RATE_UB, DG_R_RATE_LB, DG_R_IN_UB, DG_R_IN_LB, DG_R_ST_UB, DG_R_ST_LB, DG_R_LANE };
+enum { DG_R_OBS = 0, DG_R_RATE_UB, DG_R_RATE_LB, DG_R_IN_UB, DG_R_IN_LB, DG_R_ST_UB, DG_R_ST_LB, DG_R_LANE, DG_R_EDGE_R, DG_R_EDGE_L };
 
 struct DgRow {      // one inequality row
   int8_t type, a, b, idx, sgn;  // sgn: coefficient of the shared dense gradient (+1 / -1)
@@ -42,7 +42,8 @@ struct DgRow {      // one inequality row
 };
 
 struct DgDense {    // one distinct dense gradient: d x^a_k[idx] / du   or the obstacle gradient of pair (a,b) at stage k
-  int8_t kind;      // 0 state row, 1 obstacle, 2 lane half-plane (idx = lane number; n_x dx/du + n_y dy/du)
+  int8_t kind;      // 0 state row, 1 obstacle, 2 lane half-plane (idx = lane number; n_x dx/du + n_y dy/du),
+                    // 3 track edge (idx 0 right: -de_y/du - w_R' ds/du, 1 left: de_y/du - w_L' ds/du)
   int8_t a, b, idx, k;
   uint8_t nt, t0lo, t0hi;  // its chunks in the dot-product task table: nt tasks from index t0lo + 256 t0hi
   int32_t off;      // offset in the packed Gd array; kind 0: 2k entries [t][j]; kind 1: 4k entries, agent a then agent b
@@ -127,6 +128,8 @@ struct DgProb {
   int osqp_namax;   // ... whose polish handles at most this many active rows (what the T slot holds next to the polish vectors)
   int classic_qp;   // the QP runs the classical (J = L^-T) Goldfarb-Idnani kernels of dgsqp_xl.h: XL layout, or a projected Hessian
                     // whose smallest eigenvalue (eig_floor + reg) is below 1e-8 -- the literal reg = 0 formula
+  int n_edge;       // agents with track-edge rows; > 0: every evaluation point fills the width records (ws_wid: (w_L, w_L', w_R, w_R') per
+                    // (agent, stage), in the workgroup's global scratch) behind its rollout
   int big;          // 2: XL layout (n > 128, dgsqp_xl.h).  1: the packed inverse P and the packed Householder reflectors live in the workgroup's global scratch (L2)
                     // instead of LDS: games whose LDS-resident layout exceeds the 160 KB arena
   int lsqr_keeps_eval;  // the dual start's vectors sit ABOVE the evaluation arrays (not over them): the trajectory, A_k, B_k and the Taylor
@@ -143,7 +146,7 @@ struct DgProb {
   int ox_nya, ox_ngi;   // OSQP on the XL layout, wave-interleaved G' table (dgsqp_osqp_xl.h: ox_build_tables): entries of the per-agent multiplier lists; padded entries of the table
   int64_t wsx_gdI, wsx_tabI;   // ... its values, and its index part (group starts, per-agent list starts, the lists)
   int64_t wsx_Y, wsx_S, wsx_E, wsx_dy, wsx_tab, wsx_gdT;   // OSQP on the XL layout: the polish's Y and Schur complement (n x n each), row scaling and delta y (n_c), the transposed index table of G' w
-  int64_t ws_t2, ws_q, ws_base, ws_H, ws_tang, ws_Y, ws_P, ws_V, ws_R, ws_Vp, ws_xM, ws_xJ, ws_xR, ws_bfgs, ws_gd, ws_v2, ws_K, ws_doubles; // global workspace layout (doubles): Taylor tensor, raw Q, watchdog backups,
+  int64_t ws_t2, ws_q, ws_base, ws_H, ws_tang, ws_Y, ws_P, ws_V, ws_R, ws_Vp, ws_xM, ws_xJ, ws_xR, ws_bfgs, ws_gd, ws_v2, ws_K, ws_wid, ws_doubles; // global workspace layout (doubles): Taylor tensor, raw Q, watchdog backups,
                                                              // costate-contracted dynamics Hessians, tangent trajectories
   DgRow rows[DG_NCMAX];
   DgDense dense[DG_NDMAX];
@@ -154,6 +157,7 @@ struct DgProb {
   DgTask dtask[DG_NTASKMAX];
   DgLds L;
   double spl[9 * DGSQP_MAX_KNOTS];   // spline track (P.track_kind == DGSQP_TRACK_SPLINE): knots, x coefficients, y coefficients
+  double wid[3 * DGSQP_MAX_KNOTS];   // track width table (P.n_width > 0): rows (knot, left, right), dgsqp_track_width.h
 };
 
 #include <cmath>
@@ -233,6 +237,8 @@ static inline std::string dg_build_layout(DgProb& D) {
   if (D.gd_global) D.ws_doubles += D.ngd + DG_CHUNK;   // (chunked dots read up to one chunk past the last gradient)
   D.ws_K = D.ws_doubles;
   if (D.tab_const) D.ws_doubles += (int64_t)D.M * (D.N + 1) * D.M * 5;
+  D.ws_wid = D.ws_doubles;
+  if (D.n_edge) D.ws_doubles += 4 * (int64_t)D.M * (D.N + 1);
   D.ws_doubles = (D.ws_doubles + 31) / 32 * 32;
   // ---- LDS arena
   DgLds& L = D.L;
@@ -429,6 +435,16 @@ static inline std::string dg_build(const dgsqp_problem_t& P, const dgsqp_params_
     for (int i = 0; i + 1 < P.n_knots; i++) if (!(P.spline[i + 1] > P.spline[i])) return "spline knots must increase";
     if (P.spline[0] != 0.0 || fabs(P.spline[P.n_knots - 1] - P.track_L) > 1e-9 * P.track_L) return "spline knots must span [0, track_L]";
   } else if (P.track_kind != DGSQP_TRACK_ARCS) return "unknown track kind";
+  D.P.widths = nullptr;          // copied likewise
+  if (P.n_width != 0) {
+    if (P.n_width < 2 || P.n_width > DGSQP_MAX_KNOTS) return "widths: 2 <= n_width <= DGSQP_MAX_KNOTS";
+    if (!P.widths) return "widths: n_width > 0 without a table";
+    for (int i = 0; i < 3 * P.n_width; i++) if (!std::isfinite(P.widths[i])) return "widths: a non-finite entry";
+    if (P.widths[0] != 0.0 || P.widths[3 * (P.n_width - 1)] != P.track_L) return "widths: the knots must run from 0 to track_L";
+    for (int i = 0; i + 1 < P.n_width; i++) if (!(P.widths[3 * (i + 1)] > P.widths[3 * i])) return "widths: the knots must increase strictly";
+    for (int i = 0; i < P.n_width; i++) if (!(P.widths[3 * i + 1] > 0.0 && P.widths[3 * i + 2] > 0.0)) return "widths: the widths must be positive";
+    memcpy(D.wid, P.widths, sizeof(double) * (size_t)(3 * P.n_width));
+  }
   if (P.M < 1 || P.M > DGSQP_MAX_AGENTS) return "unsupported number of agents";
   if (P.N < 1 || P.N > DG_NMAX) return "unsupported horizon";
   if (par.merit_function == DGSQP_MERIT_SUM_OBJ_L1 && par.variant != DGSQP_VARIANT_V2) return "merit function sum_obj_l1 belongs to DG-SQP v2";
@@ -455,6 +471,13 @@ static inline std::string dg_build(const dgsqp_problem_t& P, const dgsqp_params_
     if (mdl == DGSQP_MODEL_UNICYCLE && (P.agents[a].w_prog != 0.0 || P.agents[a].w_comp != 0.0 || P.agents[a].w_block != 0.0))
       return "progress / competition / blocking costs need a Frenet-frame model";
     if (P.agents[a].n_lane < 0 || P.agents[a].n_lane > DGSQP_MAX_LANES) return "bad number of lane rows";
+    if (P.agents[a].edge_rows != 0 && P.agents[a].edge_rows != 1) return "edge rows: edge_rows must be 0 or 1";
+    if (P.agents[a].edge_rows) {
+      if (P.n_width < 2) return "edge rows: the game has no width table (dgsqp_problem_t.widths)";
+      if (mdl == DGSQP_MODEL_UNICYCLE) return "edge rows: the agent's model has no (s, e_y)";
+      if (!std::isfinite(P.agents[a].edge_margin)) return "edge rows: edge_margin must be finite";
+      D.n_edge++;
+    }
     for (int i = 2; i < D.nqa[a] - 2; i++)
       if (P.agents[a].w_goal[i] != 0.0) return "goal-tracking weights are supported on the positions and the last two states";
     // x, y (state 0,1) never enter fc: effective variables are the remaining states and the two inputs
@@ -506,6 +529,14 @@ static inline std::string dg_build(const dgsqp_problem_t& P, const dgsqp_params_
         if (!add_row(DG_R_LANE, k, a, -1, j, 1, nd)) return "too many rows";
         nd++;
       }
+      if (ag.edge_rows && k >= 1)      // right, then left: one dense gradient each
+        for (int j = 0; j < 2; j++) {
+          if (nd >= DG_NDMAX) return "edge rows: too many dense gradients (two per agent and stage; shorten the horizon)";
+          D.dense[nd] = DgDense{3, (int8_t)a, -1, (int8_t)j, (int8_t)k, 0, 0, 0, off, (int16_t)nc, -1};
+          off += 2 * k;
+          if (!add_row(j == 0 ? DG_R_EDGE_R : DG_R_EDGE_L, k, a, -1, j, 1, nd)) return "edge rows: too many rows";
+          nd++;
+        }
       if (k < P.N) {
         for (int j = 0; j < DGSQP_NUA; j++)
           if (ag.in_ub[j] < INFINITY) { D.r_in_ub[a][k][j] = (int16_t)nc; if (!add_row(DG_R_IN_UB, k, a, -1, j, 1, -1)) return "too many rows"; }

@@ -11,12 +11,16 @@
 // affine trajectory, the sensitivities S_k = dq_k / dx [N][n_q][n], and the active-set factor: the orthonormal basis Qm of the active
 // rows' images J a_i (n x n) and the inverse triangular factor Rinv (J A_W' = Qm R).
 //
-// The QP is a dense dual active-set method (Goldfarb-Idnani) over rows `sign * value <= sign * bound` of six kinds (dgsqp.h,
+// The QP is a dense dual active-set method (Goldfarb-Idnani) over rows `sign * value <= sign * bound` of seven kinds (dgsqp.h,
 // DGSQP_MPC_ROW_*): unit rows (rate boxes, slack signs), cumulative-sum rows (input boxes, u_k = u_prev + dt sum_{j<=k} du_j) and
-// dense rows (state boxes, soft-bound rows, obstacle rows: rows of S_k).  Box rows whose bound has magnitude >= 1e9 are not generated
+// dense rows (state boxes, soft-bound rows, obstacle rows, track-edge rows: rows of S_k).  Box rows whose bound has magnitude >= 1e9 are not generated
 // (the host builds the table): they cannot be active.  Every sum runs in a fixed order and nothing is accumulated with atomics: two runs
 // of a batch agree bit for bit.  An infeasible QP, a non-finite value or a Hessian that is not positive definite ends the solve with
 // DGSQP_QP_FAIL.
+//
+// Track-edge rows (edge_rows = 1): e_y - left_width(s) <= 0 and -right_width(s) - e_y <= 0 at stages 1..N, linearised about D as the obstacle
+// row is.  The width functions are looked up once per QP, not per row and column: mpc_condense fills one record (w_L, w_L', w_R, w_R')
+// per stage at the s of D, one lane per stage, into LDS (o_wid, 4 N doubles); rows and gradients read it behind the barriers that follow.
 #pragma once
 
 namespace dg_mpc {
@@ -28,7 +32,7 @@ struct DgMpcDev {
   int nqa, nz, n, ns, nrows, lenD, mdl, spl, max_steps, pad_;
   double dt, omd;                     // the game's dt; 1 - damping
   // LDS offsets (doubles)
-  int o_J, o_g, o_y, o_x, o_a, o_d, o_z, o_w, o_r, o_lam, o_act, o_D, o_Db, o_P0, o_flag, o_end;
+  int o_J, o_g, o_y, o_x, o_a, o_d, o_z, o_w, o_r, o_lam, o_act, o_D, o_Db, o_P0, o_flag, o_wid, o_end;
   // scratch offsets (doubles) of one workgroup
   int64_t ws_AB, ws_f, ws_gk, ws_qbar, ws_S, ws_Qm, ws_Ri, ws_doubles;
   const dgsqp_mpc_row_t* rows;
@@ -104,6 +108,14 @@ __device__ __noinline__ void mpc_condense(const DgMpcDev& M, gptr ws, int64_t b)
   clptr P0 = LP(M.o_P0);
   // A_k | B_k and f_d at (q_k, u_{k-1}), k < N
   for (int it = TID; it < N * nz; it += NT) mpc_lin_any(M, Dl, ws, it / nz, it % nz);
+  if (M.c.edge_rows) {      // the track's widths and their slopes at s_k of D, k = 1..N (record k - 1)
+    lptr wid = LP(M.o_wid);
+    for (int k = TID; k < N; k += NT) {
+      double wL, dwL, wR, dwR;
+      dev_track_width(Dl[(k + 1) * nz + nq - 2], &wL, &dwL, &wR, &dwR);
+      wid[4 * k] = wL; wid[4 * k + 1] = dwL; wid[4 * k + 2] = wR; wid[4 * k + 3] = dwR;
+    }
+  }
   __syncthreads();
   gptr AB = ws + M.ws_AB, gk = ws + M.ws_gk, qbar = ws + M.ws_qbar, S = ws + M.ws_S;
   cgptr f = ws + M.ws_f;
@@ -278,6 +290,12 @@ __device__ inline double mpc_row_res(const DgMpcDev& M, const dgsqp_mpc_row_t R,
       const double v = Db[R.stage * nz + j];
       return R.sign > 0 ? v - Db[sb + R.index] - M.c.q_ub[j] : M.c.q_lb[j] - v - Db[sb + ns + R.index];
     }
+    case DGSQP_MPC_ROW_EDGE: {      // c(q_bar) + grad c (q - q_bar); left (+1): c = e_y - w_L(s), right (-1): c = -w_R(s) - e_y
+      clptr w = LP(M.o_wid) + 4 * (R.stage - 1);
+      const double s0 = Dl[R.stage * nz + nq - 2], e0 = Dl[R.stage * nz + nq - 1];
+      const double ds = Db[R.stage * nz + nq - 2] - s0, de = Db[R.stage * nz + nq - 1] - e0;
+      return R.sign > 0 ? (e0 - w[0]) - w[1] * ds + de : (-w[2] - e0) - w[3] * ds - de;
+    }
     default: {
       const double* p = M.p_obs + (b * N + (R.stage - 1)) * 2;
       const double x0 = Dl[R.stage * nz], y0 = Dl[R.stage * nz + 1], dx = x0 - p[0], dy = y0 - p[1];
@@ -304,6 +322,11 @@ __device__ inline void mpc_row_grad(const DgMpcDev& M, gptr ws, const dgsqp_mpc_
         v = sg * S[((int64_t)(R.stage - 1) * nq + M.c.soft_idx[R.index]) * n + col];
         if (col == ndu + (R.sign > 0 ? 0 : ns) + R.index) v = -1.0;
         break;
+      case DGSQP_MPC_ROW_EDGE: {
+        clptr w = LP(M.o_wid) + 4 * (R.stage - 1);
+        v = sg * S[((int64_t)(R.stage - 1) * nq + nq - 1) * n + col] - (R.sign > 0 ? w[1] : w[3]) * S[((int64_t)(R.stage - 1) * nq + nq - 2) * n + col];
+        break;
+      }
       default: {
         const double* p = M.p_obs + (b * N + (R.stage - 1)) * 2;
         const double dx = Dl[R.stage * nz] - p[0], dy = Dl[R.stage * nz + 1] - p[1];

@@ -198,9 +198,10 @@ __global__ void dg_arc_project_kernel(int64_t n, dgsqp_track_frame_t F, const do
 }
 
 // The placement of scripts/comparison_study_f1/monte_carlo_sampler.py:25-55 on the handle's spline track: car 2 starts AHEAD of car 1, the
-// arclength range is limited; six uniforms per candidate in the script's order (s1, e_y1, v1, gap, e_y2, v2).  One lane per candidate ->
+// arclength range is limited; six uniforms per candidate in the script's order (s1, e_y1, v1, gap, e_y2, v2).  e_y is clipped to +-ey_clip or,
+// with clip_widths, to [-clip_scale right_width(s), clip_scale left_width(s)] (dgsqp_track_width.h).  One lane per candidate ->
 // q0[cand][n_q], collide[cand] (1: the two cars overlap).
-__global__ void dg_raceline_place_spline_kernel(int64_t n, unsigned long long c0, dgsqp_raceline_spline_sampler_t S, DgRaceline R,
+__global__ void dg_raceline_place_spline_kernel(int64_t n, unsigned long long c0, dgsqp_raceline_spline_sampler_t S, int clip_widths, double clip_scale, DgRaceline R,
                                                 double* __restrict__ q0, int32_t* __restrict__ collide) {
   const DgProb& D = dg_prob;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -214,7 +215,13 @@ __global__ void dg_raceline_place_spline_kernel(int64_t n, unsigned long long c0
       const double s = a == 0 ? s1 : s1 + S.gap_lo + (S.gap_hi - S.gap_lo) * dg_uniform(S.seed, c, 3);
       double r[DGSQP_RL_COLS], psi;
       rl_eval(R, rl_s2t(R, s), r);
-      const double ey = fmax(fmin(r[8] + (2 * dg_uniform(S.seed, c, 3 * a + 1) - 1), S.ey_clip), -S.ey_clip);
+      double hi = S.ey_clip, lo = -S.ey_clip;
+      if (clip_widths) {      // the study's clip: the track's width functions at the car's own s
+        double wL, dwL, wR, dwR;
+        dev_track_width(s, &wL, &dwL, &wR, &dwR);
+        hi = clip_scale * wL; lo = -(clip_scale * wR);
+      }
+      const double ey = fmax(fmin(r[8] + (2 * dg_uniform(S.seed, c, 3 * a + 1) - 1), hi), lo);
       const double v = r[3] + (1.5 * dg_uniform(S.seed, c, 3 * a + 2) - 0.75);
       dev_spline_local_to_global(s, ey, 0.0, &px[a], &py[a], &psi);
       double* qa = q + D.qoff[a];

@@ -58,6 +58,35 @@ class InputRateLimits:
 
 
 @dataclass
+class TrackEdges:
+    """The track's edges as rows of an agent: at every stage k = 1..N, in the reference's order vertcat(right, left),
+    ``-(right_width(s_k) - margin) - e_y,k <= 0`` and ``e_y,k - (left_width(s_k) - margin) <= 0``, with the track's width functions
+    (tracks.left_width / right_width).  Needs a model with (s, e_y) on a track that has a width table."""
+    margin: float = 0.0
+
+
+def constraint_records(entry) -> list:
+    """``agent_constraints[a]`` as a list of records: None, one record, or a sequence of records with at most one of each kind."""
+    recs = [] if entry is None else (list(entry) if isinstance(entry, (list, tuple)) else [entry])
+    recs = [r for r in recs if r is not None]
+    kinds = [type(r) for r in recs]
+    if len(set(kinds)) != len(kinds):
+        raise ValueError('agent_constraints: at most one record of each kind per agent')
+    for r in recs:
+        if not isinstance(r, (InputRateLimits, LaneBoundaries, TrackEdges)):
+            raise TypeError(f'agent_constraints: unknown record {type(r).__name__}')
+    return recs
+
+
+def record_of(entry, kind):
+    """The record of type ``kind`` in ``agent_constraints[a]``, or None."""
+    for r in constraint_records(entry):
+        if isinstance(r, kind):
+            return r
+    return None
+
+
+@dataclass
 class CollisionAvoidance:
     """Row for pair (i<j): (r_i+r_j)^2 - |p_i-p_j|^2 <= 0."""
     radii: Sequence[float] = field(default_factory=lambda: [0.2, 0.2])

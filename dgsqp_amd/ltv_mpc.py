@@ -10,6 +10,8 @@ three callers build (scripts/race/car{1,2}_tracking_controller_setup.py, compari
                         0.5 u' diag(input_weight) u, 0.5 du' diag(rate_weight) du
     SoftStateBounds     comes from ``CALTVMPCParams.soft_state_bound_*`` (one soft state)
     ObstacleAvoidance   (2 r)^2 - |(x, y) - p_obs_k|^2 <= 0 at stages 1..N
+    TrackEdgeRows       e_y - left_width(s) <= 0 and -right_width(s) - e_y <= 0 at stages 1..N, the track's width functions
+                        (comparison_study_f1/warm_start.py:112-118); hard rows, linearised about D like the obstacle row
 
 Two stated deviations: the QP is solved exactly where the reference calls OSQP with polish
 (``rate_weight > 0`` is required, so the minimiser is unique); ``state_scaling`` is accepted and ignored -- a change of variables that does
@@ -58,6 +60,12 @@ class ObstacleAvoidance:
     r: float
 
 
+@dataclass
+class TrackEdgeRows:
+    """The track's edges as state constraints of the tracker (margin 0, as the study has them).  Needs a model with (s, e_y) on a track with a
+    width table (every spline track; an arc track after ``set_width_table``): the library refuses the rest ("mpc: ...")."""
+
+
 def check_params(params: CALTVMPCParams) -> None:
     """Everything the device does not implement is refused here, before anything reaches the library.  ``input_scaling`` is among it: the
     callers pass the parameters through ``host_scaling`` first, which lowers it on the host."""
@@ -103,7 +111,7 @@ def rate_scale(input_scaling) -> Optional[np.ndarray]:
 
 def lower(agent: int, n_q: int, cost: TrackingCost, soft: Optional[SoftStateBounds], obstacle: Optional[ObstacleAvoidance],
           q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, N: int, qp_iters: int, damping: float, zero_du: bool = False,
-          input_scaling=None) -> _ffi.MpcT:
+          input_scaling=None, track_edges: Optional[TrackEdgeRows] = None) -> _ffi.MpcT:
     """The dgsqp_mpc_t record (validated again by dgsqp_set_mpc).  ``input_scaling``: the rate cost and the rate box are the reference's, in
     its scaled rate ``du' = Tu du``; the record states them for ``du``: ``w_du Tu^2``, ``du_lb / Tu``, ``du_ub / Tu``."""
     if len(cost.state_weight) != n_q:
@@ -136,6 +144,9 @@ def lower(agent: int, n_q: int, cost: TrackingCost, soft: Optional[SoftStateBoun
         for i, (j, qd, ln) in enumerate(zip(soft.idxs, soft.quad, soft.lin)):
             m.soft_idx[i], m.soft_quad[i], m.soft_lin[i] = int(j), float(qd), float(ln)
     m.obs_r = float(obstacle.r) if obstacle is not None else 0.0
+    if track_edges is not None and not isinstance(track_edges, TrackEdgeRows):
+        raise TypeError('track_edges must be None or a TrackEdgeRows record')
+    m.edge_rows = 1 if track_edges is not None else 0
     return m
 
 
@@ -201,7 +212,8 @@ def run_batch(lib, h, record: _ffi.MpcT, n_q: int, q0, u_ws, du_ws, q_ref, p_obs
 
 def mpc_batch(solver, agent: int, cost: TrackingCost, bounds: dict, q0, u_ws, du_ws, q_ref, p_obs=None, N: Optional[int] = None,
               qp_iters: int = 2, damping: float = 0.75, soft: Optional[SoftStateBounds] = None,
-              obstacle: Optional[ObstacleAvoidance] = None, zero_du: bool = False, log: bool = False, input_scaling=None) -> dict:
+              obstacle: Optional[ObstacleAvoidance] = None, zero_du: bool = False, log: bool = False, input_scaling=None,
+              track_edges: Optional[TrackEdgeRows] = None) -> dict:
     """The tracker for agent ``agent`` of the game of ``solver`` (a ``DGSQP``): its model, vehicle, integrator, dt and track.  ``bounds``:
     ``qu_ub``, ``qu_lb``, ``du_ub``, ``du_lb`` as ``VehicleState`` (the reference's dict).  ``input_scaling`` as in ``CALTVMPCParams``:
     ``du_ws`` and ``du_pred`` are then the reference's scaled rates."""
@@ -213,7 +225,7 @@ def mpc_batch(solver, agent: int, cost: TrackingCost, bounds: dict, q0, u_ws, du
     _, du_ub = mdl.state2qu(bounds['du_ub'])
     _, du_lb = mdl.state2qu(bounds['du_lb'])
     rec = lower(agent, mdl.n_q, cost, soft, obstacle, q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, solver.N if N is None else N, qp_iters, damping, zero_du,
-                input_scaling=input_scaling)
+                input_scaling=input_scaling, track_edges=track_edges)
     Tu = rate_scale(input_scaling)
     out = run_batch(solver._lib, solver._h, rec, mdl.n_q, q0, u_ws, du_ws if Tu is None else np.asarray(du_ws, np.float64) / Tu, q_ref, p_obs, log=log)
     if Tu is not None:
@@ -229,7 +241,7 @@ def shift_warm_start(u_pred: np.ndarray, du_pred: np.ndarray):
 
 class CA_LTV_MPC:
     """The reference's class surface.  ``costs``: a ``TrackingCost``; ``constraints``: ``None``, an ``ObstacleAvoidance`` or a dict with
-    the key ``'obstacle'``; ``bounds``: the reference's dict of ``VehicleState`` (``qu_ub``, ``qu_lb``, ``du_ub``, ``du_lb``).
+    the keys ``'obstacle'`` and ``'track_edges'`` (a ``TrackEdgeRows``); ``bounds``: the reference's dict of ``VehicleState`` (``qu_ub``, ``qu_lb``, ``du_ub``, ``du_lb``).
     ``parameters`` of ``solve`` / ``step`` / ``set_warm_start`` is the reference's ``P`` tail: ``q_ref.ravel()`` ([N+1, n_q]) followed by
     ``p_obs.ravel()`` ([N, 2]) when there is an obstacle row."""
 
@@ -237,15 +249,25 @@ class CA_LTV_MPC:
                  device: int = 0, workgroups_per_cu: int = 1):
         params = control_params if control_params is not None else CALTVMPCParams()
         check_params(host_scaling(params)[0])
+        self.track_edges = None
         if isinstance(constraints, dict):
             if constraints.get('rate') is not None and any(c is not None for c in np.atleast_1d(np.asarray(constraints['rate'], dtype=object))):
                 raise NotImplementedError('CA_LTV_MPC: rate-constraint functions are not supported (the rate box is)')
-            extra = set(constraints) - {'obstacle', 'rate', 'state_input'}
+            extra = set(constraints) - {'obstacle', 'rate', 'state_input', 'track_edges'}
             if extra:
                 raise NotImplementedError(f'CA_LTV_MPC: unknown constraint entries {sorted(extra)}')
             si = constraints.get('state_input')
             if si is not None and any(c is not None for c in np.atleast_1d(np.asarray(si, dtype=object))):
-                raise NotImplementedError("CA_LTV_MPC: 'state_input' functions are not supported: pass ObstacleAvoidance under 'obstacle'")
+                raise NotImplementedError("CA_LTV_MPC: 'state_input' functions are not supported: pass ObstacleAvoidance under 'obstacle', "
+                                          "TrackEdgeRows under 'track_edges'")
+            track_edges = constraints.get('track_edges')
+            if track_edges is not None and not isinstance(track_edges, TrackEdgeRows):
+                raise NotImplementedError("CA_LTV_MPC: 'track_edges' must be None or a TrackEdgeRows record")
+            if track_edges is not None and not (hasattr(dynamics, 's_idx') and hasattr(dynamics, 'ey_idx')):
+                raise ValueError('CA_LTV_MPC: TrackEdgeRows needs a model with (s, e_y)')
+            if track_edges is not None and (getattr(dynamics, 'track', None) is None or dynamics.track.width_table() is None):
+                raise ValueError('CA_LTV_MPC: TrackEdgeRows needs a track with a width table (a spline track, or set_width_table)')
+            self.track_edges = track_edges
             constraints = constraints.get('obstacle')
         if constraints is not None and not isinstance(constraints, ObstacleAvoidance):
             raise NotImplementedError('CA_LTV_MPC: constraints must be None or an ObstacleAvoidance record')
@@ -292,7 +314,8 @@ class CA_LTV_MPC:
 
     def _record(self, qp_iters: int, damping: float, zero_du: bool) -> _ffi.MpcT:
         return lower(0, self.n_q, self.costs, self.soft, self.constraints, self.state_ub, self.state_lb, self.input_ub, self.input_lb,
-                     self.input_rate_ub, self.input_rate_lb, self.N, qp_iters, damping, zero_du, input_scaling=self.params.input_scaling)
+                     self.input_rate_ub, self.input_rate_lb, self.N, qp_iters, damping, zero_du, input_scaling=self.params.input_scaling,
+                     track_edges=self.track_edges)
 
     def initialize(self) -> None:
         return

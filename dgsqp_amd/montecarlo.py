@@ -20,7 +20,7 @@ import numpy as np
 from .dynamics import (CasadiDecoupledMultiAgentDynamicsModel, CasadiDynamicBicycleCombined,
                        CasadiKinematicBicycleCombined, CasadiKinematicUnicycle, CasadiKinematicUnicycleCombined, DynamicBicycleConfig,
                        KinematicBicycleConfig, MultiAgentModelConfig, UnicycleConfig)
-from .game import (CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, LaneHalfPlane, RacingCost)
+from .game import (CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, LaneHalfPlane, RacingCost, TrackEdges, record_of)
 from .solver_types import DGSQPParams, DGSQPV2Params
 from .tracks import ChicaneTrack, CurveTrack, get_track
 from .types import (BodyAngularVelocity, BodyLinearVelocity, OrientationEuler, ParametricPose, Position,
@@ -166,6 +166,8 @@ class Game:
     raceline: object = None             # sampler 'raceline': the ``Raceline`` the cars are drawn around and warm-started along
     collision_d: float = 0.0            # sampler 'raceline': r1 + r2 of the placement's collision check
     s_range: object = None              # sampler 'raceline' on a spline track: (s_lo, s_hi) of car 1's placement instead of (0, L - 10)
+    clip_widths: bool = False           # sampler 'raceline' on a spline track: clip e_y with 0.9 x the track's width functions, not with 0.9 x half_width
+    tracker_edges: bool = False         # sampler 'raceline': the warm-start tracker gets the track's edge rows instead of its e_y box
 
     def solver_args(self):
         return (self.joint_model, self.costs, self.agent_constraints, self.shared_constraints, self.bounds, self.params)
@@ -364,14 +366,20 @@ def point_mass_racing_game(track_kind='barc', N=20, M=2, theta_deg=45) -> Game:
 
 
 def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10, sampler='circuit', raceline=None, time_scale=1.0,
-                   s_range=None) -> Game:
+                   s_range=None, edges='constant') -> Game:
     """BASELINE.json config 4: head-to-head race on the F1 track (``f1_austin_tenth_scale``, a ``CasadiBSplineTrack`` in the
     reference: track_lib.get_track :112-113, scripts/comparison_study_f1), long horizon N = 50.  Costs, rate limits, radii and
     solver parameters are those of the circuit race DGSQP_comp_monte_carlo.py (as ``barc_racing_game``); lateral bounds
     +-(half width - 0.1); ``model='dynamic'`` puts the Pacejka bicycle of the comparison studies on it (rk4).
     ``sampler='raceline'``: the F1 study's own front end (comparison_study_f1/monte_carlo_sampler.py, warm_start.py) around
     ``raceline`` -- a ``Raceline``, or the path of the study's TUM file ``traj_race_cl.csv`` (loaded tenth-scale with ``time_scale``);
-    ``s_range=(s_lo, s_hi)`` limits car 1's arclength (the study's [60, 80] m window, without building a sub-track)."""
+    ``s_range=(s_lo, s_hi)`` limits car 1's arclength (the study's [60, 80] m window, without building a sub-track);
+    ``edges='track'`` races on the track's measured ``left_width(s)`` / ``right_width(s)`` instead of a ribbon of their mean: the game's
+    e_y box is dropped for ``TrackEdges(0.1)`` rows; and with ``sampler='raceline'`` the placement's e_y is clipped with 0.9 x the widths at
+    the car's own s (monte_carlo_sampler.py:29,38) and the warm-start tracker gets the edge rows in place of its e_y box
+    (warm_start.py:112-118).  ``'constant'`` (default) is the game as it always was.  (The circuit sampler does not read the widths.)"""
+    if edges not in ('constant', 'track'):
+        raise ValueError(f"edges {edges!r}: 'constant' or 'track'")
     if sampler not in ('circuit', 'raceline'):
         raise ValueError(f"sampler {sampler!r} does not fit the F1 track ('circuit' or 'raceline')")
     if sampler == 'raceline':
@@ -408,10 +416,12 @@ def f1_racing_game(N=50, M=2, reg=1e-3, model='kinematic', rk4_substeps=10, samp
     params = DGSQPParams(solver_name='DGSQP', dt=dt, N=N, reg=reg, nonmono_ls=True, line_search_iters=50, sqp_iters=50,
                          p_tol=1e-3, d_tol=1e-3, beta=0.01, tau=0.5, verbose=False, merit_function='stat_l1')
     cost = lambda: RacingCost(input_weight=(0.1, 0.1), input_rate_weight=(1.0, 1.0), comp_weights=(0.0, 1.0), comp_type='atan')
-    return Game(joint, [cost() for _ in range(M)], [InputRateLimits((10.0, 4.5), (-10.0, -4.5)) for _ in range(M)],
-                CollisionAvoidance([r] * M), _bounds(H - 0.1, M), params, track, H - 0.1, 2 * r,
+    on_track = edges == 'track'
+    rows = lambda: [InputRateLimits((10.0, 4.5), (-10.0, -4.5)), TrackEdges(0.1)] if on_track else InputRateLimits((10.0, 4.5), (-10.0, -4.5))
+    return Game(joint, [cost() for _ in range(M)], [rows() for _ in range(M)],
+                CollisionAvoidance([r] * M), _bounds(np.inf if on_track else H - 0.1, M), params, track, H - 0.1, 2 * r,
                 name=f'{"kb" if model == "kinematic" else "dyn"}_f1_M{M}_N{N}', sampler=sampler, raceline=raceline,
-                collision_d=F1_STUDY_COLLISION_D if sampler == 'raceline' else 0.0, s_range=s_range)
+                collision_d=F1_STUDY_COLLISION_D if sampler == 'raceline' else 0.0, s_range=s_range, clip_widths=on_track and sampler == 'raceline', tracker_edges=on_track and sampler == 'raceline')
 
 
 _MERGE_GOAL_X = (4.0, 4.5, 4.25, 4.75, 5.25, 5.0)          # merge.py:85-87 for the first three cars
@@ -577,7 +587,7 @@ def sample_scenarios(game: Game, B: int, seed: int = 1, max_rounds: int = 200, s
             q[:, 0], q[:, 1], q[:, 2] = xy[:, 0], xy[:, 1], v
             q[:, mdl.s_idx], q[:, mdl.ey_idx] = s, ey
             q0.append(q)
-        rl = game.agent_constraints[0]
+        rl = record_of(game.agent_constraints[0], InputRateLimits)
         du = (10.0, 4.5) if rl is None else tuple(rl.rate_max)
         if solver is not None:
             dev = solver.pid_warm_start_batch(np.concatenate(q0, axis=1), du_max=du)
@@ -624,7 +634,7 @@ def _sample_scenarios_independent(game: Game, B: int, seed: int, max_rounds: int
             q = np.zeros((n, mdl.n_q))
             q[:, 0], q[:, 1], q[:, 2] = xy[:, 0], xy[:, 1], v
             q[:, mdl.s_idx], q[:, mdl.ey_idx] = s_, ey
-            rl = game.agent_constraints[0]
+            rl = record_of(game.agent_constraints[0], InputRateLimits)
             du = (10.0, 4.5) if rl is None else tuple(rl.rate_max)
             qw, uw = pid_warm_start(mdl, q, N, dt, du=du)
             q0.append(q); q_ws.append(qw); u_ws.append(uw)
@@ -656,7 +666,7 @@ def _sample_scenarios_circuit(game: Game, B: int, seed: int, max_rounds: int):
     radii = list(game.shared_constraints.radii)
     x0s, uws = [], []
     have = 0
-    rl = game.agent_constraints[0]
+    rl = record_of(game.agent_constraints[0], InputRateLimits)
     du = (10.0, 4.5) if rl is None else tuple(rl.rate_max)
     for _ in range(max_rounds):
         if have >= B:
@@ -690,21 +700,25 @@ def _sample_scenarios_circuit(game: Game, B: int, seed: int, max_rounds: int):
     return np.ascontiguousarray(x0), np.ascontiguousarray(u)
 
 
-def study_tracker(game: Game) -> dict:
+def study_tracker(game: Game, track_constraints=None) -> dict:
     """The LTV-MPC tracker of warm_start_dynamic.py:60-127 for a car of ``game``: ``cost`` (Q = diag(1, 0, 0, 1, 1, 1) on (v_long, v_tran,
     psidot, e_psi, s, e_y), input weights 1e-2, rate weights 0.1; x, y carry zero weight), ``bounds`` (:68-81), ``params`` (:115-122:
     state_scaling, input_scaling = [2, 0.45], damping 0.75, qp_iters 5) and ``u_init`` / ``du_init`` = 0.01 (:156-157).  For a game on a
     spline track it is the tracker of comparison_study_f1/warm_start.py instead: state_scaling [100, 100, 7, pi / 2, L, 1], rates +-20 /
-    +-4.5, and the ``e_y`` box at +- the game's lateral bound, which stands in for the study's width functions."""
-    from .ltv_mpc import TrackingCost
+    +-4.5, and the ``e_y`` box at +- the game's lateral bound; with ``track_constraints`` (default: ``game.tracker_edges``) the study's own
+    rows instead: the box on e_y is open and ``track_edges`` holds ``ltv_mpc.TrackEdgeRows()`` (warm_start.py:69,75 and :112-118)."""
+    from .ltv_mpc import TrackEdgeRows, TrackingCost
+    track_constraints = bool(getattr(game, 'tracker_edges', False)) if track_constraints is None else bool(track_constraints)
+    if track_constraints and game.track.width_table() is None:
+        raise ValueError('study_tracker: track_constraints needs a track with a width table')
     from .solver_types import CALTVMPCParams
     mdl = game.joint_model.dynamics_models[0]
     L, H = game.track.track_length, game.track.half_width
     w = [0, 0, 1, 0, 0, 1, 1, 1] if mdl.n_q == 8 else [0, 0, 1, 1, 1, 1]
     if game.track.kind == 'spline':
-        # comparison_study_f1/warm_start.py:66-80, :123-128 (its e_y box is open and the width functions bound e_y: here the game's constant
-        # lateral bound)
-        Hg = game.half_width
+        # comparison_study_f1/warm_start.py:66-80, :123-128 (its e_y box is open and the width functions bound e_y; without
+        # track_constraints the game's constant lateral bound stands in for them)
+        Hg = 1e9 if track_constraints else game.half_width
         ub = VehicleState(x=Position(x=1e9, y=1e9), e=OrientationEuler(psi=1e9), p=ParametricPose(s=2 * L, x_tran=Hg, e_psi=1e9),
                           v=BodyLinearVelocity(v_long=5, v_tran=2), w=BodyAngularVelocity(w_psi=10), u=VehicleActuation(u_a=2.0, u_steer=0.436))
         lb = VehicleState(x=Position(x=-1e9, y=-1e9), e=OrientationEuler(psi=-1e9), p=ParametricPose(s=-2 * L, x_tran=-Hg, e_psi=-1e9),
@@ -714,7 +728,9 @@ def study_tracker(game: Game) -> dict:
         params = CALTVMPCParams(N=game.params.N, state_scaling=[100, 100, 7, np.pi / 2, L, 1.0], input_scaling=[2, 0.45], damping=0.75,
                                 qp_iters=5, delay=None, verbose=False, qp_interface='casadi')
         return dict(cost=TrackingCost(state_weight=w, input_weight=(1e-2, 1e-2), rate_weight=(0.1, 0.1)), bounds=bounds, params=params,
-                    u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5)
+                    u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5, track_edges=TrackEdgeRows() if track_constraints else None)
+    if track_constraints:
+        H = 1e9
     ub = VehicleState(x=Position(x=1e9, y=1e9), e=OrientationEuler(psi=1e9), p=ParametricPose(s=2 * L, x_tran=H, e_psi=1e9),
                       v=BodyLinearVelocity(v_long=5, v_tran=2), w=BodyAngularVelocity(w_psi=10), u=VehicleActuation(u_a=2.0, u_steer=0.436))
     lb = VehicleState(x=Position(x=-1e9, y=-1e9), e=OrientationEuler(psi=-1e9), p=ParametricPose(s=-2 * L, x_tran=-H, e_psi=-1e9),
@@ -724,7 +740,7 @@ def study_tracker(game: Game) -> dict:
     params = CALTVMPCParams(N=game.params.N, state_scaling=[10, 10, 7, np.pi / 2, L, 1.0], input_scaling=[2, 0.45], damping=0.75, qp_iters=5,
                             delay=None, verbose=False, qp_interface='casadi')
     return dict(cost=TrackingCost(state_weight=w, input_weight=(1e-2, 1e-2), rate_weight=(0.1, 0.1)), bounds=bounds, params=params,
-                u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5)
+                u_init=0.01, du_init=0.01, init_iters=2, init_damping=0.5, track_edges=TrackEdgeRows() if track_constraints else None)
 
 
 def raceline_ws(game: Game, tracker: dict = None):
@@ -742,7 +758,7 @@ def raceline_ws(game: Game, tracker: dict = None):
     p = t['params']
     W = _ffi.RacelineWsT()
     W.mpc = ltv_mpc.lower(0, mdl.n_q, t['cost'], None, None, q_ub, q_lb, u_ub, u_lb, du_ub, du_lb, int(p.N), int(p.qp_iters), float(p.damping),
-                          input_scaling=p.input_scaling)
+                          input_scaling=p.input_scaling, track_edges=t.get('track_edges'))
     W.u_init, W.du_init = float(t.get('u_init', 0.01)), float(t.get('du_init', 0.01))
     W.init_iters, W.init_damping = int(t.get('init_iters', 2)), float(t.get('init_damping', 0.5))
     return W
@@ -760,6 +776,7 @@ def place_raceline_sequential(game: Game, rng):
     if spline:          # comparison_study_f1/monte_carlo_sampler.py:25-55: car 2 ahead of car 1, s1 in [0, L - 10] (or game.s_range)
         s_lo, s_hi = (0.0, L - 10.0) if game.s_range is None else game.s_range
         lim = 0.9 * game.half_width
+    hi, lo = lim, -lim
     for a, mdl in enumerate(models[:2]):
         if spline:
             s = s_lo + (s_hi - s_lo) * rng.random() if a == 0 else s1 + 3 * rng.random() * F1_STUDY_VL
@@ -767,7 +784,9 @@ def place_raceline_sequential(game: Game, rng):
             s = L * rng.random() if a == 0 else s1 + 1.2 * game.obs_d * (2 * rng.random() - 1)
         s1 = s if a == 0 else s1
         r = rl.eval(rl.s2t(s))
-        ey = max(min(r[8] + (2 * rng.random() - 1), lim), -lim)
+        if spline and game.clip_widths:      # monte_carlo_sampler.py:29,38
+            hi, lo = 0.9 * float(track.left_width(s)), -0.9 * float(track.right_width(s))
+        ey = max(min(r[8] + (2 * rng.random() - 1), hi), lo)
         v = r[3] + (1.5 * rng.random() - 0.75)
         x, y = track.local_to_global((s, ey, 0.0))[:2]
         qa = np.zeros(mdl.n_q)

@@ -14,6 +14,7 @@ import ctypes as C
 
 import numpy as np
 
+from .game import InputRateLimits, record_of
 from . import _ffi
 from .tracks import local_to_global_batch
 
@@ -151,8 +152,8 @@ def sample_scenarios_counter(game, B: int, seed: int = 1, chunk: int = 512, max_
     M, N, dt = len(models), game.params.N, game.params.dt
     kind = sampler_kind(game)
     radii = list(game.shared_constraints.radii) if game.shared_constraints is not None else [game.obs_d / 2] * M
-    rl = game.agent_constraints[0] if game.agent_constraints else None
-    du = (10.0, 4.5) if (rl is None or not hasattr(rl, 'rate_max')) else tuple(rl.rate_max)
+    rl = record_of(game.agent_constraints[0], InputRateLimits) if game.agent_constraints else None
+    du = (10.0, 4.5) if rl is None else tuple(rl.rate_max)
     x0s, uws, have, c0, used = [], [], 0, 0, 0
     while have < B:
         if c0 >= max_candidates:
@@ -203,8 +204,8 @@ def raceline_sampler_spec(game, seed: int) -> _ffi.RacelineSamplerT:
 def raceline_spline_sampler_spec(game, seed: int) -> _ffi.RacelineSplineSamplerT:
     """The C-ABI description of the F1 study's placement (include/dgsqp.h: dgsqp_raceline_spline_sampler_t).  Defaults as the study
     (comparison_study_f1/monte_carlo_sampler.py): s1 in [0, L - 10] -- ``game.s_range`` overrides --, gap in [0, 3 * 0.56], collision
-    distance ``game.collision_d``.  The study clips e_y with 0.9 x the track's width functions; this game has one constant lateral bound,
-    and e_y is clipped to 0.9 x that (stated deviation)."""
+    distance ``game.collision_d``.  ``game.clip_widths``: the study's clip of e_y with 0.9 x the track's width functions at the car's own s;
+    otherwise e_y is clipped to 0.9 x the game's one constant lateral bound."""
     from .montecarlo import F1_STUDY_VL
     if getattr(game.track, 'kind', 'arcs') != 'spline':
         raise ValueError('the spline-track raceline sampler needs a game on a spline track (raceline_sampler_spec places cars on arc tracks)')
@@ -216,10 +217,19 @@ def raceline_spline_sampler_spec(game, seed: int) -> _ffi.RacelineSplineSamplerT
     return S
 
 
+RACELINE_CLIP_SCALE = 0.9            # comparison_study_f1/monte_carlo_sampler.py:29,38
+
+
+def raceline_clip(game):
+    """(clip_widths, clip_scale) of dgsqp_set_raceline_clip for ``game``."""
+    return (1, RACELINE_CLIP_SCALE) if getattr(game, 'clip_widths', False) else (0, 0.0)
+
+
 def _place_raceline_spline(game, seed: int, cand):
     """comparison_study_f1/monte_carlo_sampler.py:25-55 with the counter-based uniforms: the arithmetic of dg_raceline_place_spline_kernel."""
     U = lambda k: uniform(seed, cand, k)
     S = raceline_spline_sampler_spec(game, seed)
+    widths, scale = raceline_clip(game)
     rl, track = game.raceline, game.track
     models = game.joint_model.dynamics_models
     s1 = S.s_lo + (S.s_hi - S.s_lo) * U(0)
@@ -227,7 +237,8 @@ def _place_raceline_spline(game, seed: int, cand):
     for a, mdl in enumerate(models[:2]):
         s = s1 if a == 0 else s1 + S.gap_lo + (S.gap_hi - S.gap_lo) * U(3)
         r = rl.eval(rl.s2t(s))
-        ey = np.maximum(np.minimum(r[:, 8] + (2 * U(3 * a + 1) - 1), S.ey_clip), -S.ey_clip)
+        hi, lo = (scale * track.left_width(s), -scale * track.right_width(s)) if widths else (S.ey_clip, -S.ey_clip)
+        ey = np.maximum(np.minimum(r[:, 8] + (2 * U(3 * a + 1) - 1), hi), lo)
         v = r[:, 3] + (1.5 * U(3 * a + 2) - 0.75)
         p = local_to_global_batch(track, np.stack([s, ey, np.zeros(len(cand))], axis=1))[:, :2]
         q = np.zeros((len(cand), mdl.n_q))

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _ffi
 from .dynamics import CasadiDecoupledMultiAgentDynamicsModel, INTEGRATORS
-from .game import CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, RacingCost
+from .game import CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, RacingCost, TrackEdges, record_of
 from .solver_types import DGSQPParams, DGSQPV2Params
 from .types import VehiclePrediction, VehicleState
 
@@ -107,6 +107,11 @@ def build_problem(joint_dynamics: CasadiDecoupledMultiAgentDynamicsModel,
         L, seg_s, seg_curv, seg_ang = track.track_length, [0.0, track.track_length], [0.0], [0.0, 0.0]
     else:
         L, seg_s, seg_curv, seg_ang = track.tables()
+    widths = track.width_table() if hasattr(track, 'width_table') else None
+    if widths is not None:                                # left_width(s) / right_width(s): every spline track, arc tracks after set_width_table
+        P.n_width = widths.shape[0]
+        P._widths_keepalive = widths
+        P.widths = widths.ctypes.data
     n_segs = len(seg_curv)
     if n_segs > _ffi.MAX_SEGS:
         raise ValueError(f'track has {n_segs} segments, limit is {_ffi.MAX_SEGS}')
@@ -138,17 +143,28 @@ def build_problem(joint_dynamics: CasadiDecoupledMultiAgentDynamicsModel,
             A.w_prog, A.w_comp = float(cost.comp_weights[0]), float(cost.comp_weights[1])
             A.comp_type = {'atan': 0, 'linear': 1}[cost.comp_type]
             A.w_block, A.w_obs, A.obs_cost_r = float(cost.blocking_weight), float(cost.obs_weight), float(cost.obs_r)
-        rate = agent_constraints[a] if agent_constraints is not None else None
-        if isinstance(rate, LaneBoundaries):
-            if len(rate.lanes) > _ffi.MAX_LANES:
+        entry = agent_constraints[a] if agent_constraints is not None else None
+        rate, lanes, edges = (record_of(entry, kind) for kind in (InputRateLimits, LaneBoundaries, TrackEdges))
+        if lanes is not None and rate is not None:
+            raise ValueError('LaneBoundaries and InputRateLimits exclude one another (the lane rows sit where the rate rows would be)')
+        if edges is not None:
+            if not (hasattr(mdl, 's_idx') and hasattr(mdl, 'ey_idx')) or mdl.model_id == 2:
+                raise ValueError(f'TrackEdges: agent {a} has no (s, e_y): a Frenet-frame model is needed (both bicycles, the point mass)')
+            if widths is None:
+                raise ValueError('TrackEdges: the track has no width table (a spline track has one; an arc track after set_width_table)')
+            if not np.isfinite(float(edges.margin)):
+                raise ValueError('TrackEdges: margin must be finite')
+            A.edge_rows, A.edge_margin = 1, float(edges.margin)
+        if lanes is not None:
+            rate_ = lanes
+            if len(rate_.lanes) > _ffi.MAX_LANES:
                 raise ValueError(f'at most {_ffi.MAX_LANES} lane rows per agent')
-            A.n_lane = len(rate.lanes)
-            for j, ln in enumerate(rate.lanes):
+            A.n_lane = len(rate_.lanes)
+            for j, ln in enumerate(rate_.lanes):
                 hi = ln.n_lo if ln.n_hi is None else ln.n_hi
                 A.lane[j].brk, A.lane[j].r = float(ln.brk), float(ln.r)
                 for i in range(2):
                     A.lane[j].n_lo[i], A.lane[j].n_hi[i], A.lane[j].anchor[i] = float(ln.n_lo[i]), float(hi[i]), float(ln.anchor[i])
-            rate = None
         A.has_rate = 0 if rate is None else 1
         for j in range(2):
             A.rate_ub[j] = 0.0 if rate is None else float(rate.rate_max[j])
@@ -394,6 +410,8 @@ def problem_dims(P: _ffi.ProblemT):
         for a in range(M):
             A = P.agents[a]
             n_c += A.n_lane                      # lane rows sit at every stage, k = 0 and k = N included
+            if k > 0:
+                n_c += 2 * A.edge_rows           # track-edge rows: right, left at k = 1..N
             if k < N:
                 n_c += (4 if A.has_rate else 0) + sum(A.in_ub[j] < np.inf for j in range(2)) + sum(A.in_lb[j] > -np.inf for j in range(2))
             if k > 0:
@@ -886,8 +904,8 @@ class DGSQP(AbstractSolver):
         pid = _ffi.PidT()
         pid.kp_v, pid.kp_s, pid.ki_s, pid.ey_gain, pid.ei_max = 1.0, 1.0, 0.005, 5.0, 100.0
         if du_max is None:
-            rl = game.agent_constraints[0] if game.agent_constraints else None
-            du_max = (10.0, 4.5) if (rl is None or not hasattr(rl, 'rate_max')) else tuple(rl.rate_max)
+            rl = record_of(game.agent_constraints[0], InputRateLimits) if game.agent_constraints else None
+            du_max = (10.0, 4.5) if rl is None else tuple(rl.rate_max)
         pid.u_max[0], pid.u_max[1] = float(u_max[0]), float(u_max[1])
         pid.du_max[0], pid.du_max[1] = float(du_max[0]), float(du_max[1])
         pid.substeps = int(substeps)
@@ -964,6 +982,8 @@ class DGSQP(AbstractSolver):
         spline = getattr(game.track, 'kind', 'arcs') == 'spline'       # the F1 study's placement (dgsqp_sample_raceline_spline_batch)
         spec = smp.raceline_spline_sampler_spec(game, seed) if spline else smp.raceline_sampler_spec(game, seed)
         entry = 'dgsqp_sample_raceline_spline_batch' if spline else 'dgsqp_sample_raceline_batch'
+        if spline:                                                     # the setting is the handle's: state the game's before every call
+            self._raceline_check(self._lib.dgsqp_set_raceline_clip(self._h, *smp.raceline_clip(game)), 'dgsqp_set_raceline_clip')
         W = raceline_ws(game) if ws is None else ws
         x0 = np.empty((B, self.n_q)) if fetch else None
         u_am = np.empty((B, self.n)) if fetch else None

@@ -28,7 +28,73 @@ def _wrap(theta: float) -> float:
     return theta
 
 
-class RadiusArclengthTrack:
+class _WidthFunctions:
+    """``left_width(s)`` / ``right_width(s)`` of a track: the reference's ``pw_lin(sbar, s_waypoints, width)`` on the wrapped arclength
+    (DGSQP/tracks/casadi_bspline_track.py:61-64) over a table of knots -- the numpy mirror of dev_track_width (csrc/dgsqp_track_width.h):
+    piece i is the largest one with K_i <= sbar, the value is ``w_i + (w_{i+1} - w_i) / (K_{i+1} - K_i) * (sbar - K_i)``, every operation
+    rounded once.  A track without a table has constant widths ``half_width`` (radius_arclength_track.py:57)."""
+    _width_table = None
+
+    def set_width_table(self, knots, left, right):
+        """An explicit table: ``knots`` from 0 to the track length, strictly increasing, positive widths at every knot."""
+        from . import _ffi
+        k, l, r = (np.array(v, dtype=float) for v in (knots, left, right))
+        if k.ndim != 1 or l.shape != k.shape or r.shape != k.shape or k.size < 2:
+            raise ValueError('width table: knots, left and right are three vectors of one length, at least 2')
+        if k.size > _ffi.MAX_KNOTS:
+            raise ValueError('width table: %d knots, limit is %d' % (k.size, _ffi.MAX_KNOTS))
+        if not (np.isfinite(k).all() and np.isfinite(l).all() and np.isfinite(r).all()):
+            raise ValueError('width table: a non-finite entry')
+        if k[0] != 0.0 or k[-1] != self.track_length:
+            raise ValueError('width table: the knots must run from 0 to the track length %r' % self.track_length)
+        if not (np.diff(k) > 0).all():
+            raise ValueError('width table: the knots must increase strictly')
+        if not ((l > 0).all() and (r > 0).all()):
+            raise ValueError('width table: the widths must be positive')
+        self._width_table = (k, l, r)
+        return self
+
+    def clear_width_table(self):
+        """Back to constant widths ``half_width``: ``build_problem`` then passes no table (n_width = 0)."""
+        self._width_table = None
+        return self
+
+    def width_table(self):
+        """[n, 3] rows (knot, left, right) as the C-ABI takes them (dgsqp_problem_t.widths), or None for constant widths."""
+        if self._width_table is None:
+            return None
+        return np.ascontiguousarray(np.stack(self._width_table, axis=1))
+
+    def _width_piece(self, s):
+        k = self._width_table[0]
+        sb = self._sbar(np.asarray(s, dtype=float))
+        i = np.clip(np.searchsorted(k, sb, side='right') - 1, 0, len(k) - 2)
+        return i, sb - k[i], k[i + 1] - k[i]
+
+    def _width(self, s, col):
+        if self._width_table is None:
+            return np.full(np.shape(s), float(self.half_width))[()]
+        w = self._width_table[col]
+        i, t, dk = self._width_piece(s)
+        return (w[i + 1] - w[i]) / dk * t + w[i]
+
+    def left_width(self, s):
+        return self._width(s, 1)
+
+    def right_width(self, s):
+        return self._width(s, 2)
+
+    def width_slopes(self, s):
+        """(d left_width / ds, d right_width / ds): the slope of the piece with K_i <= sbar < K_{i+1} (right-continuous at a knot)."""
+        if self._width_table is None:
+            z = np.zeros(np.shape(s))[()]
+            return z, z
+        _, l, r = self._width_table
+        i, _, dk = self._width_piece(s)
+        return (l[i + 1] - l[i]) / dk, (r[i + 1] - r[i]) / dk
+
+
+class RadiusArclengthTrack(_WidthFunctions):
     """Centre line made of constant-curvature segments ``cl_segs[i] = [length, signed radius]``
     (radius 0 = straight)."""
 
@@ -238,7 +304,7 @@ _TRACK_DATA = {
 }
 
 
-class CubicSplineTrack:
+class CubicSplineTrack(_WidthFunctions):
     """Centre line given by cubic-spline interpolants x(s), y(s) through arclength-tagged waypoints -- the reference's
     ``CasadiBSplineTrack`` (DGSQP/tracks/casadi_bspline_track.py:10-71) as the solver sees it:
     curvature = (x'y'' - y'x'') / (x'^2 + y'^2)^1.5 (:122-135), tangent angle = atan2(y', x') (:137-149),
@@ -256,6 +322,7 @@ class CubicSplineTrack:
         self.slack = slack
         self.track_length = float(self.knots[-1] - self.knots[0])
         self.circuit = bool(np.allclose([self.cx[0, 0], self.cy[0, 0]], self._xy(self.knots[-1] - 1e-12), atol=1e-6))
+        self.set_width_table(self.knots - self.knots[0], self.left_width_points, self.right_width_points)       # the measured edges
 
     def _sbar(self, s):
         L = self.track_length

@@ -34,6 +34,8 @@ def main(argv=None):
     ap.add_argument('--raceline', default=str(FIXTURE), help="the study's traj_race_cl.csv (TUM format, full scale)")
     ap.add_argument('--s-range', type=float, nargs=2, default=None, metavar=('S_LO', 'S_HI'),
                     help="raceline front end: car 1's arclength window (the study's track segment: 60 80); default [0, L - 10]")
+    ap.add_argument('--edges', choices=('constant', 'track'), default='constant',
+                    help="'track': the game's e_y box becomes the track's edge rows; the raceline front end clips with 0.9 x the width functions and its tracker gets the edge rows")
     ap.add_argument('--time-scale', type=float, default=1.0, help='raceline front end: the line is driven time_scale times slower')
     ap.add_argument('--seed', type=int, default=0, help='seed of the counter-based sampler (the script seeds its generator with 0)')
     ap.add_argument('--rk4-substeps', type=int, default=10)
@@ -45,7 +47,8 @@ def main(argv=None):
     model = args.model or ('dynamic' if raceline else 'kinematic')
     N = args.N or (25 if model == 'dynamic' else 50)
     game = f1_racing_game(N=N, model=model, rk4_substeps=args.rk4_substeps, sampler=args.front_end, raceline=args.raceline if raceline else None,
-                          time_scale=args.time_scale, s_range=args.s_range if raceline else None)
+                          time_scale=args.time_scale, s_range=args.s_range if raceline else None,
+                          edges=args.edges)
     solver = DGSQP(*game.solver_args(), print_method=None)
     B = args.num_mc
     t0 = time.time()

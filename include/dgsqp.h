@@ -117,6 +117,15 @@ typedef struct {
     double anchor[2];
     double r;
   } lane[DGSQP_MAX_LANES];
+  /* track-edge rows (edge_rows = 1; needs a game with a width table, dgsqp_problem_t.widths, and a model with (s, e_y): both
+     bicycles and the Frenet point mass): two rows at every stage k = 1..N (x_0 is fixed), in the reference's order vertcat(right, left),
+       right  -(right_width(s_k) - edge_margin) - e_y,k <= 0        left  e_y,k - (left_width(s_k) - edge_margin) <= 0
+     placed among the agent's rows of stage k after its rate rows (and lane rows) and before its input and state boxes.  Gradient over
+     (s, e_y): (-+w'(sbar), -+1), w' the slope of the table's piece; no second derivative of their own (the multiplier reaches Q through
+     the costate).  Each row has a dense gradient of its own: two per (agent, stage) where an e_y box costs one. */
+  int32_t edge_rows;
+  int32_t _pad3;
+  double edge_margin;
 } dgsqp_agent_t;
 
 /*
@@ -148,6 +157,17 @@ typedef struct {
   int32_t track_kind;
   int32_t n_knots;
   const double* spline;
+  /* Track width functions (CasadiBSplineTrack.left_width / right_width, casadi_bspline_track.py:61-64):
+       left_width(s) = pw_lin(sbar, knot, left), right_width(s) = pw_lin(sbar, knot, right), sbar as above,
+     the half widths to the left (e_y > 0) and to the right of the centre line.  widths = [n_width][3] rows (knot, left, right);
+     caller-owned, copied by dgsqp_create like spline.  n_width = 0: no table (nothing reads the pointer).  Otherwise dgsqp_create /
+     dgsqp_plan refuse (DGSQP_E_ARG, message starting "widths: "): n_width outside 2 .. DGSQP_MAX_KNOTS, a NULL pointer, a non-finite
+     entry, knot[0] != 0, knot[n_width-1] != track_L, knots that do not increase strictly, a width that is not positive.  Either track
+     kind may carry one.  Read by the spline-track raceline sampler (dgsqp_set_raceline_clip) and by the tracker's edge rows
+     (dgsqp_mpc_t.edge_rows) and by the game's track-edge rows (dgsqp_agent_t.edge_rows). */
+  int32_t n_width;
+  int32_t _pad_w;
+  const double* widths;
 } dgsqp_problem_t;
 
 #define DGSQP_TRACK_ARCS 0
@@ -410,7 +430,8 @@ int dgsqp_fetch_q_est(dgsqp_handle_t h, double* out /* [T][B][n_q] */, int64_t c
      clearance[t][b]  = min over j and pairs i < k of sqrt(dx^2 + dy^2) - (radius_i + radius_k), (dx, dy) the difference of the first two
                         entries of the two agents' state blocks (the positions the obstacle rows read); +inf for M = 1;
      box_excess[t][b] = max over j, agents and state entries with a finite bound of max(z - st_ub, st_lb - z), with the GAME's bounds;
-                        -inf when no entry has one;
+                        -inf when no entry has one (track-edge rows are not read: a game that bounds e_y by dgsqp_agent_t.edge_rows has no
+                        e_y entry here);
    both NaN for a step that never ran and for a step with a non-finite entry in one of its z_j;
      hit_step[b]      = the smallest t * S + j whose pairwise clearance is < 0, or -1.
    In mode 2 chain b ends after the control step of its first hit: steps_done[b] = t + 1, q[t+1][b] is kept, u_ws[t+1][b] is not written
@@ -744,6 +765,11 @@ int dgsqp_synchronize(dgsqp_handle_t h);
  *          generates no row.  The bounds of a soft state are lifted: q_k[j] <= q_ub[j] + s_ub, q_k[j] >= q_lb[j] - s_lb, s >= 0 (one
  *          slack pair over the horizon; n_soft <= 1: with more, the reference's rows of different states overwrite one another).
  *   obs_r > 0: one row per stage k = 1..N, (2 obs_r)^2 - |(x, y)_k - p_obs_k|^2 <= 0, linearised about D.
+ *   edge_rows = 1: two hard rows per stage k = 1..N, the track's edges as the F1 study's tracker has them (comparison_study_f1/
+ *          warm_start.py:112-118, its 'state_input' constraints, vertcat(right, left)):
+ *            right  -right_width(s_k) - e_y,k <= 0        left  e_y,k - left_width(s_k) <= 0
+ *          with the width functions of the handle's table (dgsqp_problem_t.widths), linearised about D as the obstacle row is: value
+ *          c(q_bar_k) + grad c (q_k - q_bar_k), grad c over (s, e_y) = (-w'(s_bar), +-1), w' the slope of the table's piece.
  * zero_du != 0 is the loop of set_warm_start (CA_LTV_MPC.py:174-197): du of D is zeroed after every iteration, and a failed QP leaves
  * the current D as the result.  Otherwise a failed QP (status DGSQP_QP_FAIL) returns the warm start: q_ws, u_ws[1:], du_ws.
  * A u_prev (= u_ws[0]) more than 1e-12 max(1, |bound|) beyond an input bound makes every QP infeasible, as in the reference, where u_-1 is
@@ -754,7 +780,8 @@ typedef struct {
   double damping;
   double w_q[DGSQP_MAX_NQA], c_N[DGSQP_MAX_NQA], w_u[DGSQP_NUA], w_du[DGSQP_NUA];   /* w_du > 0: the QP is strictly convex */
   double q_ub[DGSQP_MAX_NQA], q_lb[DGSQP_MAX_NQA], u_ub[DGSQP_NUA], u_lb[DGSQP_NUA], du_ub[DGSQP_NUA], du_lb[DGSQP_NUA];
-  int32_t n_soft, reserved_;
+  int32_t n_soft;
+  int32_t edge_rows;                                                                 /* 0, or 1: track-edge rows (this field was reserved_) */
   int32_t soft_idx[DGSQP_MAX_NQA];                   /* entries past n_soft (<= 1 today) are reserved: room for more soft states */
   double soft_quad[DGSQP_MAX_NQA], soft_lin[DGSQP_MAX_NQA];
   double obs_r;                                                                      /* 0: no obstacle rows */
@@ -765,12 +792,14 @@ enum { DGSQP_MPC_ROW_RATE = 0,   /* du_stage[index] */
        DGSQP_MPC_ROW_INPUT = 2,  /* u of block `stage` (1..N), i.e. u_{stage-1}[index] */
        DGSQP_MPC_ROW_STATE = 3,  /* q_stage[index] */
        DGSQP_MPC_ROW_SOFT = 4,   /* soft state `index` (slot) at `stage`: sign +1 the upper row, -1 the lower */
-       DGSQP_MPC_ROW_OBS = 5 };  /* obstacle row of `stage` */
+       DGSQP_MPC_ROW_OBS = 5,    /* obstacle row of `stage` */
+       DGSQP_MPC_ROW_EDGE = 6 }; /* track-edge row of `stage`: sign +1 the left edge, -1 the right; after the obstacle rows, right before left */
 typedef struct { int32_t kind, stage, index, sign; } dgsqp_mpc_row_t;
 typedef struct { int32_t n, n_rows, len_D, n_q, lds_bytes, reserved_; int64_t workspace_bytes; } dgsqp_mpc_dims_t;
 #define DGSQP_MPC_NMAX 128   /* condensed variables: N n_u + 2 n_soft */
 /* Validated and copied; NULL clears it.  DGSQP_E_ARG, message starting "mpc: ": agent out of range, N < 1, qp_iters < 1, damping outside
-   [0, 1], w_du <= 0, a negative weight, n_soft outside 0..1 or its index out of range, obs_r < 0, a non-finite entry.
+   [0, 1], w_du <= 0, a negative weight, n_soft outside 0..1 or its index out of range, obs_r < 0, a non-finite entry, edge_rows outside
+   0..1, edge_rows = 1 on a handle without a width table or for a unicycle agent.
    DGSQP_E_TOO_LARGE: N n_u + 2 n_soft > DGSQP_MPC_NMAX, or the workgroup's LDS arena cannot hold it (the 256-thread build has half). */
 int dgsqp_set_mpc(dgsqp_handle_t h, const dgsqp_mpc_t* mpc);
 /* rows: the row table in the order of the multipliers of dgsqp_fetch_mpc_log (may be NULL); row_capacity = what it can hold. */
@@ -852,7 +881,10 @@ int dgsqp_sample_raceline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_racelin
  * The sampler of scripts/comparison_study_f1/monte_carlo_sampler.py:25-55 on a spline-track handle (two cars), in the same rounds with the
  * same uniforms: s1 = s_lo + (s_hi - s_lo) u0; s2 = s1 + gap_lo + (gap_hi - gap_lo) u3 (car 2 starts ahead of car 1); per car
  * e_y = clip(raceline e_y + (2 u - 1), -+ey_clip), v = raceline v_long + (1.5 u - 0.75), e_psi = the raceline's (u1, u2 for car 1; u4, u5
- * for car 2).  The study clips e_y with the track's width functions; ey_clip is one constant bound (stated deviation).  Rejection as
+ * for car 2).  ey_clip is one constant bound.  After dgsqp_set_raceline_clip with clip_widths = 1: the study's clip with the track's width functions
+ * (monte_carlo_sampler.py:29,38; clip_scale = 0.9 there), each car at its own s:
+ *   e_y = max(min(raceline e_y + (2 u - 1), clip_scale left_width(s)), -clip_scale right_width(s))
+ * from the handle's width table (dgsqp_problem_t.widths, csrc/dgsqp_track_width.h); ey_clip is ignored.  Rejection as
  * dgsqp_sample_raceline_batch.  DGSQP_E_ARG, message starting "raceline: ": an arc-track handle, a non-finite entry, s_hi < s_lo,
  * gap_hi < gap_lo, ey_clip < 0, collision_d < 0, and what dgsqp_sample_raceline_batch refuses.
  */
@@ -862,6 +894,11 @@ typedef struct {
 } dgsqp_raceline_spline_sampler_t;
 int dgsqp_sample_raceline_spline_batch(dgsqp_handle_t h, int64_t B, const dgsqp_raceline_spline_sampler_t* spec, const dgsqp_raceline_ws_t* ws,
                                        double* x0_out, double* u_ws_out, int64_t* candidates, int stage);
+/* The e_y clip of the handle's SUBSEQUENT dgsqp_sample_raceline_spline_batch calls (sticky, like dgsqp_set_plant; the record above keeps
+   its 56 bytes).  clip_widths = 0 (the state of a new handle): the constant ey_clip; clip_scale is not read.  clip_widths = 1: the width
+   functions as above.  DGSQP_E_ARG, message starting "raceline: ": clip_widths outside 0 .. 1, clip_widths = 1 on a handle without a width
+   table or with a clip_scale that is negative or not finite; the setting in force is kept then. */
+int dgsqp_set_raceline_clip(dgsqp_handle_t h, int clip_widths, double clip_scale);
 
 /*
  * Track-frame transforms for batches of points (csrc/dgsqp_track_frame.h), one lane per point, on the handle's stream.
