@@ -37,7 +37,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _ffi
-from .dynamics import INTEGRATORS, DynamicBicycleConfig, KinematicBicycleConfig
+from .dynamics import INTEGRATORS, DynamicBicycleConfig, KinematicBicycleConfig, rk_step
 
 DIVERGED, QP_FAIL = 3, 4        # include/dgsqp.h: the exit codes after which step() does not shift the warm start
 NUA = 2                         # every vehicle model has two inputs (DGSQP_NUA)
@@ -133,17 +133,8 @@ def track_reference(model, q_agent, g, method: Optional[str] = None, dt: Optiona
     ``dynamics``) from ``q_agent`` -- the projection of the plant agent's true state -- under the game's command ``g``.  ``method``, ``dt``
     and ``M`` are the joint model's (a game discretises every agent with them); by default the model's own, and the result is then
     ``model.fd(q_agent, g)`` where the model has one.  The references are entries 2 (v), last (lateral) and e_psi of the result."""
-    from .dynamics import CasadiKinematicUnicycle
-    if method is None and dt is None and M is None:
-        return np.asarray(CasadiKinematicUnicycle.fd(model, q_agent, g), dtype=np.float64)
-    import copy
-    m = copy.copy(model)
-    m.model_config = copy.copy(model.model_config)
-    if method is not None:
-        m.model_config.discretization_method = method
-    m.dt = float(model.dt if dt is None else dt)
-    m.M = int(model.M if M is None else M)
-    return np.asarray(CasadiKinematicUnicycle.fd(m, q_agent, g), dtype=np.float64)
+    method = model.model_config.discretization_method if method is None else method
+    return rk_step(lambda z: model.fc(z, g), q_agent, method, float(model.dt if dt is None else dt), int(model.M if M is None else M))
 
 
 @dataclass

@@ -95,8 +95,8 @@ __device__ inline void dev_monitor_store(const dgsqp_agent_t& game, int nqa, con
 
 // S simulation steps of agent a's plant from q (in place).  Simulation step `count` (counted from the chain's start) of a channel with
 // delay d > 0 integrates under entry count % d of its line -- the oldest of the last d -- and then stores u_new there (a deque of
-// length d: read [0], append); d = 0 integrates under u_new.  One plant step is dev_fd_t's arithmetic on f_c with the plant's agent
-// record, step length and sub-step count (euler: one step per simulation step, as the game's model).
+// length d: read [0], append); d = 0 integrates under u_new.  One plant step is DEV_RK_SUBSTEP (dgsqp_device.h) on f_c with the plant's
+// agent record, integrator, step length and sub-step count (euler: one step per simulation step, as the game's model).
 // With a non-null `mon` ([S][M][3], the workgroup's): the agent's monitor record after every simulation step (dev_monitor_store).
 template <int MDL, bool SPL>
 __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_plant_t& pl, int a, int64_t count, const double* u_new,
@@ -104,9 +104,9 @@ __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_pla
   typedef Ty<0> T;
   const dgsqp_agent_t& ag = pl.agents[a];
   const int S = pl.sim_steps, integ = pl.integrator, nsub = integ == DGSQP_INT_EULER ? 1 : pl.substeps;
-  const double hs = P.dt / S, h = hs / nsub;
+  const double h = P.dt / S / nsub;
   constexpr int NQA = dg_model_nq(MDL);
-  T x[NQA], k1[NQA], k2[NQA], t[NQA], u[DGSQP_NUA];
+  T x[NQA], u[DGSQP_NUA];
 #pragma unroll
   for (int i = 0; i < NQA; i++) x[i].c[0] = qa[i];
   for (int j = 0; j < S; j++, count++) {
@@ -123,41 +123,7 @@ __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_pla
     }
     FcPre<0> pre;
     dev_fc_pre<0, MDL>(ag, u, pre);
-    for (int m = 0; m < nsub; m++) {
-      dev_fc<0, MDL, SPL>(P, ag, x, u, pre, k1);
-      if (integ == DGSQP_INT_RK4) {
-#pragma unroll
-        for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * (h / 2);
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * (h / 2); k1[i] = k1[i] + k2[i] * 2.0; }
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) { t[i] = x[i] + k2[i] * h; k1[i] = k1[i] + k2[i] * 2.0; }
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 6.0);
-      } else if (integ == DGSQP_INT_RK3) {
-#pragma unroll
-        for (int i = 0; i < NQA; i++) { k1[i] = k1[i] * h; t[i] = x[i] + k1[i] * 0.5; }
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) { k2[i] = k2[i] * h; t[i] = x[i] - k1[i] + k2[i] * 2.0; }
-        T k3[NQA];
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k3);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i] * 4.0 + k3[i] * h) / 6.0;
-      } else if (integ == DGSQP_INT_RK2) {
-#pragma unroll
-        for (int i = 0; i < NQA; i++) t[i] = x[i] + k1[i] * h;
-        dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-        for (int i = 0; i < NQA; i++) x[i] = x[i] + (k1[i] + k2[i]) * (h / 2);
-      } else {
-#pragma unroll
-        for (int i = 0; i < NQA; i++) x[i] = x[i] + k1[i] * hs;
-      }
-    }
+    for (int m = 0; m < nsub; m++) DEV_RK_SUBSTEP(0, MDL, SPL, integ, P, ag, x, u, pre, h);
     if (mon) {
       double z[NQA];
 #pragma unroll
@@ -169,19 +135,16 @@ __device__ inline void dev_plant_agent(const dgsqp_problem_t& P, const dgsqp_pla
   for (int i = 0; i < NQA; i++) qa[i] = x[i].c[0];
 }
 
-// dev_plant_agent for an agent of model class `mdl` on P's track: the one place where the class becomes a template argument.  Out of
-// line: one body (some 28 k instructions) serves both feedbacks and the TRACK driver's reference step.  That step so has a unicycle arm
-// too; it is never taken there, since the host refuses a TRACK driver for a unicycle.
+// dev_plant_agent for an agent of model class `mdl` on P's track (dev_with_model).  Out of line: one body (some 28 k instructions)
+// serves both feedbacks and the TRACK driver's reference step.  That step so has a unicycle arm too; it is never taken there, since the
+// host refuses a TRACK driver for a unicycle.
 __device__ __noinline__ void dev_plant_model(int mdl, const dgsqp_problem_t& P, const dgsqp_plant_t& pl, int a, int64_t count, const double* u_new,
                                              double* line, double* u_rec, int nu, double* x, double* mon) {
-  if (mdl == DG_UNI) dev_plant_agent<DG_UNI, false>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
-  else if (mdl == DG_PM) dev_plant_agent<DG_PM, false>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
-  else if (P.track_kind == DGSQP_TRACK_SPLINE) {
-    if (mdl == DG_DYN) dev_plant_agent<DG_DYN, true>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
-    else dev_plant_agent<DG_KIN, true>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
-  }
-  else if (mdl == DG_DYN) dev_plant_agent<DG_DYN, false>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
-  else dev_plant_agent<DG_KIN, false>(P, pl, a, count, u_new, line, u_rec, nu, x, mon);
+  // (the command is read here, not through the closure: the compiler then still passes it in registers, as it did before the closure)
+  const double c[DGSQP_NUA] = {u_new[0], u_new[1]};
+  dev_with_model(mdl, P.track_kind == DGSQP_TRACK_SPLINE, [&](auto m) {
+    dev_plant_agent<decltype(m)::MDL, decltype(m)::SPL>(P, pl, a, count, c, line, u_rec, nu, x, mon);
+  });
 }
 
 // A held plan: which row of the table (include/dgsqp.h) step t falls under, from whether it solved and the solve's status.

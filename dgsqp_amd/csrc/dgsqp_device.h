@@ -674,6 +674,62 @@ __device__ inline void dev_fc_pre(const dgsqp_agent_t& ag, const Ty<DEG>* u, FcP
   else dev_fc_pre_kin<DEG>(ag, u, pre);
 }
 
+// One Runge-Kutta sub-step of length h under the input u (pre = dev_fc_pre of it): x (an array of Ty<DEG>) advances in place.  `integ` may
+// be a run-time value -- the plant's integrator is one -- and every arm starts from the same first f_c evaluation; with a constant the
+// other arms fold away.  Euler is x + k1 h.  A macro, not a function: a function is optimised on its own before it is inlined, and f_c's
+// two-product sums (vx cd + vyf sd in the dynamic bicycle's slip angle) then reach the caller with their operands in another order -- another
+// product is fused into the FMA, and the dynamic plant's rk3 / rk4 steps and the PID trajectories move in the last bit (measured).  As text
+// the callers compile to what they computed when each spelled the formulas out.  Expressions and operation order are dev_fd_t's (below),
+// which states them once more for the solve path: its instantiations keep their code only while its text stays what it is.
+#define DEV_RK_SUBSTEP(DEG, MDL, SPL, integ, P, ag, x, u, pre, h)                                                              \
+  do {                                                                                                                         \
+    constexpr int NQA_ = dg_model_nq(MDL);                                                                                     \
+    Ty<DEG> k1_[NQA_], k2_[NQA_], t_[NQA_];                                                                                    \
+    dev_fc<DEG, MDL, SPL>(P, ag, x, u, pre, k1_);                                                                              \
+    if ((integ) == DGSQP_INT_RK4) {                                                                                            \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) t_[i] = x[i] + k1_[i] * ((h) / 2);                                      \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k2_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) { t_[i] = x[i] + k2_[i] * ((h) / 2); k1_[i] = k1_[i] + k2_[i] * 2.0; }  \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k2_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) { t_[i] = x[i] + k2_[i] * (h); k1_[i] = k1_[i] + k2_[i] * 2.0; }        \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k2_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) x[i] = x[i] + (k1_[i] + k2_[i]) * ((h) / 6.0);                          \
+    } else if ((integ) == DGSQP_INT_RK3) {                                                                                     \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) { k1_[i] = k1_[i] * (h); t_[i] = x[i] + k1_[i] * 0.5; }                 \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k2_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) { k2_[i] = k2_[i] * (h); t_[i] = x[i] - k1_[i] + k2_[i] * 2.0; }        \
+      Ty<DEG> k3_[NQA_];                                                                                                       \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k3_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) x[i] = x[i] + (k1_[i] + k2_[i] * 4.0 + k3_[i] * (h)) / 6.0;             \
+    } else if ((integ) == DGSQP_INT_RK2) {                                                                                     \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) t_[i] = x[i] + k1_[i] * (h);                                            \
+      dev_fc<DEG, MDL, SPL>(P, ag, t_, u, pre, k2_);                                                                           \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) x[i] = x[i] + (k1_[i] + k2_[i]) * ((h) / 2);                            \
+    } else {                                                                                                                   \
+      _Pragma("unroll") for (int i = 0; i < NQA_; i++) x[i] = x[i] + k1_[i] * (h);                                             \
+    }                                                                                                                          \
+  } while (0)
+
+// The one place where an agent's model class and the track kind become template arguments, for the one-lane callers outside the solve
+// (the plant, the PID warm start, the tracker's rollout and linearisation): f(DgModelTag<MDL, SPL>()) is called for the instantiation
+// agent class `mdl` runs.  The rules, stated once: the unicycle lives in the global frame and the Frenet point mass on arc tracks only
+// (dg_build refuses it on a spline track), so both are SPL = false whatever the track; the two bicycles run on both kinds.  A caller
+// without an arm for a class skips it with `if constexpr` in f, and nothing is instantiated for it.  (The dispatches inside the solve --
+// dev_rollout_multi, dev_taylor_item -- stay their own: their arms also say what is inlined and what is out of line.)
+template <int MDL_, bool SPL_>
+struct DgModelTag { static constexpr int MDL = MDL_; static constexpr bool SPL = SPL_; };
+template <class F>
+__device__ __forceinline__ void dev_with_model(int mdl, bool spline, F&& f) {
+  if (mdl == DG_UNI) f(DgModelTag<DG_UNI, false>());
+  else if (mdl == DG_PM) f(DgModelTag<DG_PM, false>());
+  else if (spline) {
+    if (mdl == DG_DYN) f(DgModelTag<DG_DYN, true>());
+    else f(DgModelTag<DG_KIN, true>());
+  }
+  else if (mdl == DG_DYN) f(DgModelTag<DG_DYN, false>());
+  else f(DgModelTag<DG_KIN, false>());
+}
+
 // one discrete step of the joint model's integrator (dynamics_models.py:88-99, :188-219).  The integrator is a template
 // parameter so that every instantiation keeps only the stage arrays it needs in registers (rk4: x, k-accumulator, k, t).
 template <int DEG, int MDL, int INTEG, bool SPL = false>

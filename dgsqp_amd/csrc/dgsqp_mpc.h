@@ -83,20 +83,10 @@ __device__ __noinline__ void mpc_lin_item(const DgMpcDev& M, clptr Dl, gptr ws, 
   }
 }
 __device__ inline void mpc_rollout_any(const DgMpcDev& M, lptr Dl) {
-  const int mdl = M.mdl;
-  if (M.spl) { if (mdl == DG_DYN) mpc_rollout<DG_DYN, true>(M, Dl); else mpc_rollout<DG_KIN, true>(M, Dl); }
-  else if (mdl == DG_DYN) mpc_rollout<DG_DYN, false>(M, Dl);
-  else if (mdl == DG_PM) mpc_rollout<DG_PM, false>(M, Dl);
-  else if (mdl == DG_UNI) mpc_rollout<DG_UNI, false>(M, Dl);
-  else mpc_rollout<DG_KIN, false>(M, Dl);
+  dev_with_model(M.mdl, M.spl, [&](auto m) { mpc_rollout<decltype(m)::MDL, decltype(m)::SPL>(M, Dl); });
 }
 __device__ inline void mpc_lin_any(const DgMpcDev& M, clptr Dl, gptr ws, int k, int dir) {
-  const int mdl = M.mdl;
-  if (M.spl) { if (mdl == DG_DYN) mpc_lin_item<DG_DYN, true>(M, Dl, ws, k, dir); else mpc_lin_item<DG_KIN, true>(M, Dl, ws, k, dir); }
-  else if (mdl == DG_DYN) mpc_lin_item<DG_DYN, false>(M, Dl, ws, k, dir);
-  else if (mdl == DG_PM) mpc_lin_item<DG_PM, false>(M, Dl, ws, k, dir);
-  else if (mdl == DG_UNI) mpc_lin_item<DG_UNI, false>(M, Dl, ws, k, dir);
-  else mpc_lin_item<DG_KIN, false>(M, Dl, ws, k, dir);
+  dev_with_model(M.mdl, M.spl, [&](auto m) { mpc_lin_item<decltype(m)::MDL, decltype(m)::SPL>(M, Dl, ws, k, dir); });
 }
 
 __device__ inline int tri(int i) { return i * (i + 1) / 2; }

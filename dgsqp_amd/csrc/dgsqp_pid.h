@@ -1,7 +1,7 @@
 // PID lane-follower warm start and collision rejection of the Monte-Carlo scripts
 // (scripts/DGSQP_ALGAMES_monte_carlo_chicane.py:411-447 with DGSQP/solvers/PID.py; check_collision chicane.py:38-43):
 // what every Monte-Carlo sample runs before DGSQP.solve().  One lane per (scenario, agent); the plant is the agent's own
-// continuous model integrated with rk4 (10 sub-steps per dt by default), the same f_c the solver differentiates.
+// continuous model integrated with rk4 (10 sub-steps per dt by default; DEV_RK_SUBSTEP), the same f_c the solver differentiates.
 #pragma once
 
 // One step of the lane follower (PID.solve): speed P controller on v - v_ref, steering PI on ey_gain (e_y - lat_ref) + e_psi; rate
@@ -24,7 +24,7 @@ __device__ inline void dev_pid_agent(const DgProb& D, int a, cgptr q0, const dgs
   const dgsqp_problem_t& P = D.P;
   const dgsqp_agent_t& ag = P.agents[a];
   constexpr int NQA = dg_model_nq(MDL), V = 2, EPSI = NQA == 8 ? 5 : 3, EY = NQA - 1;      // (the point mass: e_psi, x_tran where the kinematic bicycle has e_psi, e_y)
-  T q[NQA], k1[NQA], k2[NQA], t[NQA], u[2];
+  T q[NQA], u[2];
 #pragma unroll
   for (int i = 0; i < NQA; i++) q[i].c[0] = q0[i];
   if (q_out)
@@ -40,20 +40,7 @@ __device__ inline void dev_pid_agent(const DgProb& D, int a, cgptr q0, const dgs
     u[0].c[0] = ua; u[1].c[0] = us;
     FcPre<0> pre;
     dev_fc_pre<0, MDL>(ag, u, pre);
-    for (int m = 0; m < pid.substeps; m++) {
-      dev_fc<0, MDL, SPL>(P, ag, q, u, pre, k1);
-#pragma unroll
-      for (int i = 0; i < NQA; i++) t[i] = q[i] + k1[i] * (h / 2);
-      dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-      for (int i = 0; i < NQA; i++) { t[i] = q[i] + k2[i] * (h / 2); k1[i] = k1[i] + k2[i] * 2.0; }
-      dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-      for (int i = 0; i < NQA; i++) { t[i] = q[i] + k2[i] * h; k1[i] = k1[i] + k2[i] * 2.0; }
-      dev_fc<0, MDL, SPL>(P, ag, t, u, pre, k2);
-#pragma unroll
-      for (int i = 0; i < NQA; i++) q[i] = q[i] + (k1[i] + k2[i]) * (h / 6.0);
-    }
+    for (int m = 0; m < pid.substeps; m++) DEV_RK_SUBSTEP(0, MDL, SPL, DGSQP_INT_RK4, P, ag, q, u, pre, h);
     if (q_out)
       for (int i = 0; i < NQA; i++) q_out[(int64_t)(k + 1) * D.nq + i] = q[i].c[0];
   }
@@ -70,10 +57,9 @@ dg_pid_kernel(int64_t B, const double* __restrict__ q0, dgsqp_pid_t pid, double*
     cgptr q0a = (cgptr)q0 + b * D.nq + D.qoff[a];
     gptr uo = (gptr)u_ws + b * D.n;
     gptr qo = q_ws ? (gptr)q_ws + b * (int64_t)(D.N + 1) * D.nq + D.qoff[a] : nullptr;
-    if (D.P.track_kind == DGSQP_TRACK_SPLINE) { if (D.mdl[a] == DG_DYN) dev_pid_agent<DG_DYN, true>(D, a, q0a, pid, uo, qo); else dev_pid_agent<DG_KIN, true>(D, a, q0a, pid, uo, qo); }
-    else if (D.mdl[a] == DG_DYN) dev_pid_agent<DG_DYN>(D, a, q0a, pid, uo, qo);
-    else if (D.mdl[a] == DG_PM) dev_pid_agent<DG_PM>(D, a, q0a, pid, uo, qo);
-    else dev_pid_agent<DG_KIN>(D, a, q0a, pid, uo, qo);
+    dev_with_model(D.mdl[a], D.P.track_kind == DGSQP_TRACK_SPLINE, [&](auto m) {      // (no unicycle arm: the host refuses the lane follower for one)
+      if constexpr (decltype(m)::MDL != DG_UNI) dev_pid_agent<decltype(m)::MDL, decltype(m)::SPL>(D, a, q0a, pid, uo, qo);
+    });
   }
 }
 // collide[b] = 1 if any two agents come closer than r_i + r_j at any stage of the warm-start trajectories

@@ -327,6 +327,27 @@ class CasadiDynamicBicycleCombined(_FrenetBicycle):
         return prediction
 
 
+def rk_step(fc, q, method, dt, M):
+    """One discrete step of ``fc`` (a callable of the state alone) from ``q`` (dynamics_models.py:88-125, rk3 :200-211): 'euler' takes
+    one step of ``dt``, 'rk4' | 'rk3' | 'rk2' take ``M`` sub-steps of ``dt / M``.  The host's one statement of the stage formulas: on a
+    state or on rows of states, the same expressions, so that a row equals the scalar call bit for bit."""
+    q = np.asarray(q, float)
+    h = dt / M
+    if method == 'euler':
+        return q + dt * fc(q)
+    for _ in range(M):
+        if method == 'rk4':
+            a1 = fc(q); a2 = fc(q + h / 2 * a1); a3 = fc(q + h / 2 * a2); a4 = fc(q + h * a3)
+            q = q + h * (a1 + 2 * a2 + 2 * a3 + a4) / 6
+        elif method == 'rk3':
+            a1 = h * fc(q); a2 = h * fc(q + a1 / 2); a3 = h * fc(q - a1 + 2 * a2)
+            q = q + (a1 + 4 * a2 + a3) / 6
+        else:
+            a1 = fc(q); a2 = fc(q + h * a1)
+            q = q + h * (a1 + a2) / 2
+    return q
+
+
 class CasadiKinematicUnicycle(_FrenetBicycle):
     """Global-frame kinematic unicycle (dynamics_models.py:306-390): state [x, y, v, psi], input [F, omega].
     The merge script builds it from a plain ``DynamicsConfig`` (DGSQP_merge_monte_carlo.py:95-101), which has no ``mass``
@@ -366,22 +387,8 @@ class CasadiKinematicUnicycle(_FrenetBicycle):
         return prediction
 
     def fd(self, q, u):
-        """One step of the model's own discretisation (dynamics_models.py:88-125, rk3 :200-211)."""
-        q = np.asarray(q, float)
-        meth, h = self.model_config.discretization_method, self.dt / self.M
-        if meth == 'euler':
-            return q + self.dt * self.fc(q, u)
-        for _ in range(self.M):
-            if meth == 'rk4':
-                a1 = self.fc(q, u); a2 = self.fc(q + h / 2 * a1, u); a3 = self.fc(q + h / 2 * a2, u); a4 = self.fc(q + h * a3, u)
-                q = q + h * (a1 + 2 * a2 + 2 * a3 + a4) / 6
-            elif meth == 'rk3':
-                a1 = h * self.fc(q, u); a2 = h * self.fc(q + a1 / 2, u); a3 = h * self.fc(q - a1 + 2 * a2, u)
-                q = q + (a1 + 4 * a2 + a3) / 6
-            else:
-                a1 = self.fc(q, u); a2 = self.fc(q + h * a1, u)
-                q = q + h * (a1 + a2) / 2
-        return q
+        """One step of the model's own discretisation."""
+        return rk_step(lambda z: self.fc(z, u), q, self.model_config.discretization_method, self.dt, self.M)
 
 
 class CasadiKinematicUnicycleCombined(_FrenetBicycle):

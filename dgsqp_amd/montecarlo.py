@@ -19,7 +19,7 @@ import numpy as np
 
 from .dynamics import (CasadiDecoupledMultiAgentDynamicsModel, CasadiDynamicBicycleCombined,
                        CasadiKinematicBicycleCombined, CasadiKinematicUnicycle, CasadiKinematicUnicycleCombined, DynamicBicycleConfig,
-                       KinematicBicycleConfig, MultiAgentModelConfig, UnicycleConfig)
+                       KinematicBicycleConfig, MultiAgentModelConfig, UnicycleConfig, rk_step)
 from .game import (CollisionAvoidance, GoalTrackingCost, InputRateLimits, LaneBoundaries, LaneHalfPlane, RacingCost, TrackEdges, record_of)
 from .solver_types import DGSQPParams, DGSQPV2Params
 from .tracks import ChicaneTrack, CurveTrack, get_track
@@ -508,14 +508,7 @@ def _fc_batch(model, q, u):
 
 
 def _plant_step(model, q, u, dt, substeps=10):
-    h = dt / substeps
-    for _ in range(substeps):
-        k1 = _fc_batch(model, q, u)
-        k2 = _fc_batch(model, q + h / 2 * k1, u)
-        k3 = _fc_batch(model, q + h / 2 * k2, u)
-        k4 = _fc_batch(model, q + h * k3, u)
-        q = q + h * (k1 + 2 * k2 + 2 * k3 + k4) / 6
-    return q
+    return rk_step(lambda z: _fc_batch(model, z, u), q, 'rk4', dt, substeps)
 
 
 def pid_warm_start(model, q0, N, dt, u_max=(2.1, 0.436), du=(10.0, 4.5)):
@@ -867,25 +860,10 @@ def _sample_scenarios_merge(game: Game, B: int, seed: int):
 
 
 def _unicycle_fd_zero_input(mdl, q):
-    """``CasadiKinematicUnicycle.fd`` (dynamics_models.py:88-125, rk3 :200-211) on rows of states with u = 0 -- the same expressions
-    evaluated on arrays, so that a row equals the scalar ``mdl.fd(q_row, 0)`` bit for bit."""
-    meth, h = mdl.model_config.discretization_method, mdl.dt / mdl.M
-
+    """``CasadiKinematicUnicycle.fd`` on rows of states with u = 0: a row equals the scalar ``mdl.fd(q_row, 0)`` bit for bit."""
     def fc(z):
         return np.stack([z[:, 2] * np.cos(z[:, 3]), z[:, 2] * np.sin(z[:, 3]), np.zeros(len(z)) / mdl.m, np.zeros(len(z))], axis=1)
-    if meth == 'euler':
-        return q + mdl.dt * fc(q)
-    for _ in range(mdl.M):
-        if meth == 'rk4':
-            a1 = fc(q); a2 = fc(q + h / 2 * a1); a3 = fc(q + h / 2 * a2); a4 = fc(q + h * a3)
-            q = q + h * (a1 + 2 * a2 + 2 * a3 + a4) / 6
-        elif meth == 'rk3':
-            a1 = h * fc(q); a2 = h * fc(q + a1 / 2); a3 = h * fc(q - a1 + 2 * a2)
-            q = q + (a1 + 4 * a2 + a3) / 6
-        else:
-            a1 = fc(q); a2 = fc(q + h * a1)
-            q = q + h * (a1 + a2) / 2
-    return q
+    return rk_step(fc, q, mdl.model_config.discretization_method, mdl.dt, mdl.M)
 
 
 def _sample_scenarios_merge_scalar(game: Game, B: int, seed: int):

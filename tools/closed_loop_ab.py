@@ -11,6 +11,11 @@ The launches: kb_curve_N10, B = 7, T = 3 through the settings of test_one_handle
 with delays; vehicles and delays per chain; estimates + monitor 'stop'; PID + replay drivers; hold R = 2, on_fail 'hold'; everything at
 once), on ONE solver object in that order; everything at once with B = 600, more chains than workgroups; the kinematic game on dynamic
 plants with one TRACK agent (B = 3, T = 3).  The b256 process runs the plant with delays and everything at once.
+``--models`` runs the one-lane consumers of the vehicle models instead, on the product build: one control step (B = 3) under a plant of each
+integrator (euler, rk2, rk3, rk4 with 2 sub-steps; sim_steps = 2) on kb_curve_N10, dyn_curve_N15, merge_N8, the point-mass curve game
+(N = 10) and the F1 game (N = 12, kinematic); ``pid_warm_start_batch(..., want_trajectories=True)`` (B = 8) on kb_chicane_N15, dyn_curve_N15,
+the point-mass game and the F1 game, kinematic and dynamic; ``mpc_batch`` with the smallest cases of tests/test_ltv_mpc.py (kinematic N = 3,
+dynamic N = 4, point mass N = 3, kinematic on the spline track N = 3; scenario, weights and bounds are that module's own).
 A child that fails ends the run: nothing more is started on the device."""
 import argparse
 import os
@@ -94,6 +99,50 @@ def dump(root, build, out):
     np.savez(out, library=np.array(pathlib.Path(_ffi.library_path(1)).name), **arrays)
 
 
+def dump_models(root, out):
+    sys.path[:0] = [str(root), str(ROOT / 'tests')]
+    import dgsqp_amd
+    from dgsqp_amd import _ffi, closed_loop as cl, montecarlo as mc
+    from dgsqp_amd.solver import DGSQP
+    import test_ltv_mpc as tm                      # scenario, weights, wide_bounds: plain functions of this tree's test module
+    assert pathlib.Path(dgsqp_amd.__file__).resolve().parent.parent == pathlib.Path(root).resolve(), dgsqp_amd.__file__
+    games = dict(kb_curve_N10=lambda: mc.kinematic_racing_game('curve', N=10), kb_chicane_N15=lambda: mc.kinematic_racing_game('chicane', N=15),
+                 dyn_curve_N15=lambda: mc.dynamic_racing_game(N=15, rk4_substeps=4, game_def='curve'), merge_N8=lambda: mc.merge_game(N=8),
+                 pm_curve_N10=lambda: mc.point_mass_racing_game('curve', N=10), pm_curve_N5=lambda: mc.point_mass_racing_game(N=5),
+                 f1_kin_N12=lambda: mc.f1_racing_game(N=12, model='kinematic', rk4_substeps=3),
+                 f1_dyn_N12=lambda: mc.f1_racing_game(N=12, model='dynamic', rk4_substeps=3), f1_kin_N6=lambda: mc.f1_racing_game(N=6))
+    plants = ('kb_curve_N10', 'dyn_curve_N15', 'merge_N8', 'pm_curve_N10', 'f1_kin_N12')
+    pids = ('kb_chicane_N15', 'dyn_curve_N15', 'pm_curve_N10', 'f1_kin_N12', 'f1_dyn_N12')
+    mpcs = dict(kb_curve_N10=('kin', 3, 4, 5, {}), dyn_curve_N15=('dyn', 4, 4, 5, {}), pm_curve_N5=('kin', 3, 3, 29, dict(u=(0.6, 0.2), du=(3.0, 1.0))),
+                f1_kin_N6=('kin', 3, 3, 23, dict(u=(0.6, 0.2), du=(3.0, 1.0))))
+    arrays = {}
+
+    def keep(tag, res):
+        for key, val in res.items():
+            if key not in ('kernel_ms', 'total_ms', 'time', 'timing', 'dims'):      # clocks and the launch's sizes, not results
+                arrays[f'{tag}|{key}'] = np.asarray(val)
+        print(f'{tag}: keys {len(res)}', flush=True)
+
+    for name, make in games.items():
+        g = make()
+        s = DGSQP(*g.solver_args(), print_method=None)
+        if name in plants:
+            x0, u_ws = mc.sample_scenarios(g, 3, seed=31)
+            for method in ('euler', 'rk2', 'rk3', 'rk4'):
+                keep(f'{name}, {method} plant', s.step_batch(x0, u_ws, 1, keep_predictions=True, plant=cl.PlantModel(method=method, M=2, sim_steps=2)))
+        if name in pids:
+            keep(f'{name}, pid_warm_start_batch', s.pid_warm_start_batch(mc.sample_scenarios(g, 8, seed=37)[0], want_trajectories=True))
+        if name in mpcs:
+            kind, N, B, seed, bkw = mpcs[name]
+            q0, u_ws, du_ws, q_ref, idx = tm.scenario(kind, B, N, seed=seed)
+            if name == 'f1_kin_N6':
+                q0[:, idx[1]] += np.array([0.0, 7.3, 21.9])
+                q_ref[:, :, idx[1]] += np.array([0.0, 7.3, 21.9])[:, None]
+            mdl = s.joint_dynamics.dynamics_models[0]
+            keep(f'{name}, mpc_batch {kind} N = {N}', s.mpc_batch(0, tm.weights(kind, idx), tm.wide_bounds(mdl, idx, **bkw), q0, u_ws, du_ws, q_ref, None, log=True, N=N))
+    np.savez(out, library=np.array(pathlib.Path(_ffi.library_path(1)).name), **arrays)
+
+
 def compare(a, b):
     """Lines of the report, and whether everything is equal."""
     A, B = np.load(a), np.load(b)
@@ -120,20 +169,23 @@ def main():
     ap.add_argument('--dump', help='(child) write the results of --root / --build here')
     ap.add_argument('--root', default=str(ROOT))
     ap.add_argument('--build', choices=('512', '256'), default='512')
+    ap.add_argument('--models', action='store_true', help='the one-lane consumers of the vehicle models (plants of every integrator, PID warm starts, the tracker) instead')
     args = ap.parse_args()
     if args.dump:
-        return dump(args.root, args.build, args.dump)
+        return dump_models(args.root, args.dump) if args.models else dump(args.root, args.build, args.dump)
     if not args.parent:
         ap.error('--parent is needed')
-    text, all_ok = ['step_batch, parent checkout against this tree, every result key byte for byte (tools/closed_loop_ab.py)'], True
+    what = 'plants of every integrator, PID warm starts and the tracker' if args.models else 'step_batch'
+    text, all_ok = [f'{what}, parent checkout against this tree, every result key byte for byte (tools/closed_loop_ab.py{" --models" * args.models})'], True
     with tempfile.TemporaryDirectory() as td:
-        for build in ('512', '256'):
+        for build in ('512',) if args.models else ('512', '256'):
             files = []
             for side, root in (('parent', pathlib.Path(args.parent).resolve()), ('tree', ROOT)):
                 lib = root / 'dgsqp_amd' / 'csrc' / ('libdgsqp_hip.so' if build == '512' else 'libdgsqp_hip_b256.so')
                 files.append(f'{td}/{side}_{build}.npz')
                 env = dict(os.environ, DGSQP_HIP_LIB=str(lib))
-                subprocess.run([sys.executable, __file__, '--dump', files[-1], '--root', str(root), '--build', build], env=env, check=True, timeout=240, cwd=str(root))
+                subprocess.run([sys.executable, __file__, '--dump', files[-1], '--root', str(root), '--build', build] + ['--models'] * args.models,
+                               env=env, check=True, timeout=240, cwd=str(root))
             lines, ok = compare(*files)
             text += [f'build {build}:'] + lines
             all_ok = all_ok and ok
